@@ -16,15 +16,21 @@ all 3 axes) over one batch of synthetic waypoints already resident in HBM.
 --config 5 (BASELINE.json configs[4]): ONE batch of 16384 ragged min-snap trajectories through the whole corridor pipeline
   (pipeline.py: boxes from a pillar cloud with the SE(3) robot ellipsoid, <= 5 x (corridor solve + time re-allocation), collision
   check), sharded like config 4; a step = one pass of the pipeline, host-sequenced (no graph).
-In all modes the RCCL all-gather of the solved coefficient shards (uavqp_allgather_coeffs: the ctx-owned communicator of the
-C ABI, device buffers, in place) is run and timed separately and reported under "allgather" (DESIGN.md section 7).
+With --full, in all modes, the RCCL all-gather of the solved coefficient shards (uavqp_allgather_coeffs: the ctx-owned communicator
+of the C ABI, device buffers, in place) is run and timed separately and reported under "allgather" (DESIGN.md section 7).
 
-What is timed: the K steps are replayed as ONE hipGraph of K launches (uavqp_capture_*; --graph 0 = K eager launches), step i
-reads and writes buffer set i mod S where the S sets together exceed the 256 MiB Infinity Cache (no step finds its inputs
-or its output lines in a cache: the roofline figure is an HBM figure at every batch size).  The K-step block is bracketed by
-barrier + synchronize on both sides and by HIP events on the launch stream; it is repeated R >= 10 times and the MEDIAN block
-is reported (`ms_per_step` = block / K), MAX over ranks.  `roofline.achieved` uses the same clock as `value` (the HIP-event
-time of that block), never a different estimator.
+What is timed: the K steps are replayed as ONE hipGraph of K launches (uavqp_capture_*; --graph 0 = K eager launches; above
+GRAPH_STEPS_MAX steps a graph of about that many steps is replayed until K steps have run), step i reads and writes buffer set
+i mod S where the S sets together exceed the 256 MiB Infinity Cache (no step finds its inputs or its output lines in a cache: the
+roofline figure is an HBM figure at every batch size).  The K-step block is bracketed by barrier + synchronize on both sides and by
+HIP events on the launch stream (`ms_per_step` = block / K, MAX over ranks).  `roofline.achieved` uses the same clock as `value`
+(the HIP-event time of that block), never a different estimator.
+
+A plain run sets up, warms up, times the K steps ONCE and prints the line (cpu_baseline, parity and the sub-records null or absent).
+--full adds everything else: the K-step block repeated R >= 10 times with the MEDIAN block reported, cpu_baseline, parity (the last
+timed step's buffers against the oracle), time_modes, pipelined, allgather, host_pointers, the rocprofv3 traffic / FP64 / per-kernel
+passes and, for the default one-GPU config 2, other_configs.  --dump-outputs DIR writes what the last timed step computed as .npy
+files (inputs are seeded: the same arguments give the same inputs on every run).
 
 Prints ONE JSON line on rank 0.
 """
@@ -42,6 +48,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 INFINITY_CACHE_BYTES = 256 << 20  # buffer sets rotate over more than this
+GRAPH_STEPS_MAX = 1024            # more timed steps than this: a graph of about this many steps (a multiple of the buffer sets), replayed
+DUMP_BYTES_MAX = 60 * 10 ** 6     # --dump-outputs: at most this many bytes of arrays in all
 
 
 def parse():
@@ -59,7 +67,8 @@ def parse():
     ap.add_argument("--variant", type=int, default=0, help="kernel variant (0 auto)")
     ap.add_argument("--cpu-sample", type=int, default=-1, help="trajectories in the cpu_baseline sample (0 = skip)")
     ap.add_argument("--parity-sample", type=int, default=-1, help="trajectories of the LAST timed step's output checked against the oracle after the timed region -> `parity` (-1 = auto: all of config 2, 256 of the other configs; 0 = skip)")
-    ap.add_argument("--repeats", type=int, default=0, help="repeats of the K-step block (0 = auto: >= 10, about 0.25 s in total)")
+    ap.add_argument("--repeats", type=int, default=0, help="repeats of the K-step block (0 = auto: 1 in a plain run, i.e. exactly --steps timed steps; "
+                                                           "with --full >= 10, about 0.25 s in total, median reported)")
     ap.add_argument("--graph", type=int, default=1, help="1: the K steps are one hipGraph of K launches (default); 0: K eager launches")
     ap.add_argument("--sets", type=int, default=0, help="distinct in/out buffer sets the steps rotate over (0 = auto: > 256 MiB in total)")
     ap.add_argument("--pipelined-streams", type=int, default=4, help="streams of the `pipelined` sub-record (0 = skip it)")
@@ -71,10 +80,17 @@ def parse():
                     help="initialise torch.distributed and run the barrier / communicator / all-gather code even at world size 1 (self-test)")
     ap.add_argument("--inner", action="store_true", help=argparse.SUPPRESS)  # child run under rocprofv3: kernels only
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default invocation (config 2, one GPU): skip the `other_configs` sub-record (short runs of configs 3, 3 + rows, 4, 5 and the config-1 latency)")
+                    help="--full on the default config 2, one GPU: skip the `other_configs` sub-record (short runs of configs 3, 3 + rows, 4, 5 and the config-1 latency)")
     ap.add_argument("--master-port", type=int, default=0, help="--gpus N > 1 without a launcher: rendezvous port of the ranks this script spawns (0 = a free one)")
     ap.add_argument("--data", default="astar", choices=["astar", "uniform"],
                     help="astar: configs[1] generator; uniform: iid waypoints/times (tuning aid)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: repeated timed blocks, cpu_baseline, parity, time_modes, pipelined, allgather, "
+                         "host_pointers, the rocprofv3 traffic / FP64 / per-kernel passes and other_configs (a plain run sets up, warms up, "
+                         "times the K steps once and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's shard) as DIR/<name>.npy in float64; "
+                         "above DUMP_BYTES_MAX in all, a fixed seeded sample of every array (+ DIR/<name>_index.npy: the flat indices kept)")
     return ap.parse_args()
 
 
@@ -424,6 +440,22 @@ def measure_kernel_times(args, steps):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64.  Above DUMP_BYTES_MAX in all, every array keeps the same fraction of its
+    elements, flattened, at flat indices drawn with a fixed seed (the same on every run of the same arguments); the indices are written
+    next to it as DIR/<name>_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    frac = 1.0 if total <= DUMP_BYTES_MAX else DUMP_BYTES_MAX / (2.0 * total)     # a sampled element costs its value and its index
+    for j, (name, a) in enumerate(sorted(arrays.items())):
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(1000 + j).choice(a.size, size=max(1, int(a.size * frac)), replace=False))
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def run(args):
     """One bench record (a dict on rank 0, None elsewhere and for --inner child runs)."""
     import torch
@@ -593,18 +625,31 @@ def run(args):
     for i in range(max(args.warmup, 1)):       # also sizes the workspaces before any capture
         launch(ctx, i)
     fence()
-    graph = None
+    graph = graph_rest = None
+    G = K
     if args.graph and K > 0:
+        # K steps = K // G replays of one graph of G steps + one graph of the K % G steps left (G = K up to GRAPH_STEPS_MAX); G is then
+        # a multiple of S, so step i still reads and writes buffer set i mod S
+        G = K if K <= GRAPH_STEPS_MAX else S * max(1, GRAPH_STEPS_MAX // S)
         ctx.capture_begin()
-        for i in range(K):
+        for i in range(G):
             launch(ctx, i)
         graph = ctx.capture_end()
         ctx.graph_launch(graph)                # first replay uploads the graph: keep that out of the timed region
+        if K % G:
+            ctx.capture_begin()
+            for i in range(K % G):
+                launch(ctx, i)
+            graph_rest = ctx.capture_end()
+            ctx.graph_launch(graph_rest)
         fence()
 
     def block():
         if graph is not None:
-            ctx.graph_launch(graph)
+            for _ in range(K // G):
+                ctx.graph_launch(graph)
+            if graph_rest is not None:
+                ctx.graph_launch(graph_rest)
         else:
             for i in range(K):
                 launch(ctx, i)
@@ -612,6 +657,8 @@ def run(args):
     # ------------------------------------------------------------------ the timed K-step block, repeated, median
     if args.repeats > 0:
         R = args.repeats
+    elif not args.full:
+        R = 1                                   # a plain run: exactly K timed steps
     else:
         t0 = time.perf_counter()
         block()
@@ -647,13 +694,25 @@ def run(args):
         assert float((d_st[:n_local] == U.UAVQP_SOLVED).double().mean().item()) > 0.99, "rows solve left trajectories unsolved"
     elif n_local > 0:
         assert int((d_st[:n_local] == U.UAVQP_SOLVED).sum().item()) == n_local, "some trajectories were not solved"
+    if args.dump_outputs and rank == 0 and n_local > 0 and K > 0:
+        # what a caller of the timed path receives from the LAST timed step (step K - 1 wrote buffer set (K - 1) mod S)
+        last = sets[(K - 1) % S]
+        if args.config == 5:
+            pr_ = pipe_state["res"]
+            outs = {k: pr_[k] for k in ("coeff", "status", "corr_lo", "corr_hi", "first_hit")}
+            outs["times"] = last["T"]              # the durations after the time re-allocation
+        else:
+            outs = {"coeff": last["out"], "status": d_st[:n_local]}
+            if args.config == 3:
+                outs["iterations"] = d_it[:n_local]
+        dump_outputs(args.dump_outputs, outs)
     if args.inner:
         return None
 
     # ------------------------------------------------------------------ parity capture: the buffers the LAST timed step wrote, copied back now
     # (after the timed region); rank 0 checks them against the oracle when the line is assembled (`parity`)
     cap = None
-    if rank == 0 and args.parity_sample != 0 and n_local > 0 and K > 0:
+    if rank == 0 and args.full and args.parity_sample != 0 and n_local > 0 and K > 0:
         last = sets[(K - 1) % S]
         used = sorted({i % S for i in range(K)})
         cap = {"coef": last["out"].cpu().numpy(), "st": (pipe_state["status"] if args.config == 5 else d_st[:n_local]).cpu().numpy(),
@@ -667,7 +726,7 @@ def run(args):
     # ------------------------------------------------------------------ config 2: the same block on the OTHER time allocation of SURVEY 8-d
     # (reference: T_i = 1.0, test_minimum_jerk.cpp:65-71; distance: T_i = max(0.3, |dp| / 2 m/s)) -- same kernel, same bytes, other numbers
     time_modes = None
-    if args.config == 2 and not args.no_time_modes and args.time_mode in ("reference", "distance") and K > 0:
+    if args.full and args.config == 2 and not args.no_time_modes and args.time_mode in ("reference", "distance") and K > 0:
         other = "reference" if args.time_mode == "distance" else "distance"
         ob = W.uniform_batch(2, B, M, r, time_mode=other, seed=W.SEED0 + 2 + 1000 * rank)
         saved = [(s_["wp"].clone(), s_["T"].clone(), s_["bc"].clone()) for s_ in sets]
@@ -704,7 +763,7 @@ def run(args):
 
     # ------------------------------------------------------------------ pipelined sub-record: the same K steps dealt to P streams
     pipelined = None
-    if args.pipelined_streams > 1 and K > 0:
+    if args.full and args.pipelined_streams > 1 and K > 0:
         P = args.pipelined_streams
         KP = max(K, 200)   # its own step count: at the driver's 20 steps the overlap of four streams does not reach steady state
         slots = [(stream, ctx)] + [make_slot() for _ in range(P - 1)]
@@ -741,7 +800,7 @@ def run(args):
 
     # ------------------------------------------------------------------ the exchange step: all-gather of the coefficient shards
     gather = None
-    if use_dist and not args.no_allgather:
+    if args.full and use_dist and not args.no_allgather:
         tot = sum(c_counts)
         full_out = torch.zeros(tot, dtype=torch.float64, device=dev)
         off = sum(c_counts[:rank])
@@ -861,8 +920,8 @@ def run(args):
         per_launch_s = dt_evt / K
         achieved = bytes_local / per_launch_s / 1e9
         n_cpu = args.cpu_sample if args.cpu_sample >= 0 else 4096
-        cpu = cpu_baseline(batch, r, n_cpu) if (n_cpu > 0 and world == 1 and args.config == 2) else None
-        if n_cpu > 0 and world == 1 and args.config == 3:
+        cpu = cpu_baseline(batch, r, n_cpu) if (args.full and n_cpu > 0 and world == 1 and args.config == 2) else None
+        if args.full and n_cpu > 0 and world == 1 and args.config == 3:
             cpu = cpu_baseline_corridor(batch, r, c_lo, c_hi, rows_np, min(n_cpu, 1024))
         port_coef = cpu.pop("_port_coef", None) if cpu else None
         parity = None
@@ -894,10 +953,10 @@ def run(args):
             parity["buffer_sets_bitwise_equal"] = cap["sets_equal"]
             if world > 1:
                 parity["checked"] += f"; rank 0's shard of {world}"
-        traffic = measure_traffic(args) if (world == 1 and not args.no_traffic) else None
+        traffic = measure_traffic(args) if (args.full and world == 1 and not args.no_traffic) else None
         # FP64 roof ("report FP64 FLOP/s next to GB/s") and per-kernel view, from counters / traces of child runs
         fp64 = kernels = None
-        if world == 1 and (not args.no_fp64 or args.kernels_only):
+        if args.full and world == 1 and (not args.no_fp64 or args.kernels_only):
             prof_steps = 2 if args.config == 5 else (6 if args.config == 3 else 40)
             trace_steps = 2 if args.config == 5 else ((4 if args.rows else 20) if args.config == 3 else 1000)   # the trace is cheap: enough launches that the average is the steady state
             f64 = measure_fp64(args, prof_steps) if not args.no_fp64 else None
@@ -929,7 +988,7 @@ def run(args):
                         "note": "SQ_INSTS_VALU_{ADD,MUL,FMA,TRANS}_F64 wave-instructions x 64 lanes (FMA = 2 FLOP) of every uavqp kernel of a step; "
                                 "issued lane-slots, idle lanes included"}
         host_e2e = None
-        if world == 1 and args.config == 2 and n_cpu > 0:
+        if args.full and world == 1 and args.config == 2 and n_cpu > 0:
             # the same batch from HOST pointers (uavqp_solve_batch_host: staging copies over PCIe, solve, copy back, synchronise):
             # what a caller without device-resident data sees.  Reported next to `value`, never as it.
             hw, hT, hbc = np.asarray(batch["waypoints"]), np.asarray(batch["times"]), np.asarray(batch["bc"])
@@ -963,7 +1022,7 @@ def run(args):
             "timing": {"block_wall_ms_median": dt * 1e3, "block_event_ms_median": dt_evt * 1e3,
                        "block_wall_ms_p10_p90": [float(np.percentile(wall, 10)) * 1e3, float(np.percentile(wall, 90)) * 1e3],
                        "block_wall_ms_min_max": [float(np.min(wall)) * 1e3, float(np.max(wall)) * 1e3], "repeats": R,
-                       "note": "K-step block between barrier + synchronize, repeated; value and ms_per_step from the median wall time (MAX over ranks)"},
+                       "note": f"K-step block between barrier + synchronize, timed {R} time(s); value and ms_per_step from the median wall time (MAX over ranks)"},
             # config 5 is a pipeline of ~20 launches with host synchronisation between rounds: a pipeline-wide HBM fraction says nothing
             #  -- achieved / frac are null there, the per-kernel table (`kernels`) is the content
             "roofline": {"bound": "hbm", "achieved": achieved if args.config != 5 else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -996,8 +1055,9 @@ def run(args):
             out["pipelined"] = pipelined
         if gather:
             out["allgather"] = gather
-    if graph is not None:
-        ctx.graph_destroy(graph)
+    for g_ in (graph, graph_rest):
+        if g_ is not None:
+            ctx.graph_destroy(g_)
     if use_dist:
         dist.destroy_process_group()  # RCCL prints its version banner here: keep the JSON line last
     return out
@@ -1073,7 +1133,7 @@ def other_configs(args):
         a.batch, a.sets, a.repeats, a.cpu_sample = 0, 0, 0, 0
         a.order, a.segments, a.time_mode, a.data, a.variant, a.graph = 4, 8, "distance", "astar", 0, 1
         a.no_traffic, a.no_fp64, a.kernels_only = True, True, True
-        a.pipelined_streams, a.no_allgather, a.force_dist, a.inner = 0, True, False, False
+        a.pipelined_streams, a.no_allgather, a.force_dist, a.inner, a.dump_outputs = 0, True, False, False, None
         t0 = time.perf_counter()
         try:
             rec = run(a)
@@ -1123,7 +1183,7 @@ def main():
     out = run(args)
     rank = int(os.environ.get("RANK", "0"))
     if rank == 0 and out is not None:
-        if args.config == 2 and out["n_gpus"] == 1 and not args.no_other_configs and args.batch <= 0:
+        if args.full and args.config == 2 and out["n_gpus"] == 1 and not args.no_other_configs and args.batch <= 0:
             out["other_configs"] = other_configs(args)
         # RCCL (NCCL_DEBUG=VERSION on the GPU boxes) leaves its banner in the C stdio buffer; flush it so that
         # the JSON line is the last line of stdout

@@ -145,3 +145,54 @@ def test_bench_spawns_its_ranks_and_appends_the_other_configs():
     assert 'out["other_configs"] = other_configs(args)' in src and "args.config == 2 and out[\"n_gpus\"] == 1" in src
     for key in ("config3_corridor", "config3_rows2", "config4_ragged", "config5_pipeline", "config1_latency"):
         assert f'"{key}"' in src, key
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def test_plain_run_times_the_steps_once_and_full_carries_the_rest():
+    """A plain run does what its headline needs (set up, warm up, K timed steps, the line); every other measurement or check sits behind
+    --full, and --dump-outputs is an option of its own."""
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert re.search(r'"--full", action="store_true"', src) and re.search(r'"--dump-outputs", metavar="DIR", default=None', src)
+    assert "elif not args.full:\n        R = 1" in src
+    body = src[src.index("def run(args):"):]
+    for gate in ("if rank == 0 and args.full and args.parity_sample != 0", "if args.full and args.config == 2 and not args.no_time_modes",
+                 "if args.full and args.pipelined_streams > 1", "if args.full and use_dist and not args.no_allgather",
+                 "cpu_baseline(batch, r, n_cpu) if (args.full and", "if args.full and n_cpu > 0 and world == 1 and args.config == 3:",
+                 "measure_traffic(args) if (args.full and", "if args.full and world == 1 and (not args.no_fp64 or args.kernels_only):",
+                 "if args.full and world == 1 and args.config == 2 and n_cpu > 0:"):
+        assert gate in body, gate
+    assert 'if args.full and args.config == 2 and out["n_gpus"] == 1' in src
+    # the outputs are dumped after the timed block
+    assert body.index("dump_outputs(args.dump_outputs, outs)") > body.index("evt.append(e0.elapsed_time(e1) * 1e-3)")
+
+
+def test_dump_outputs_writes_float64_and_samples_above_the_limit(tmp_path):
+    import numpy as np
+    b = _bench_module()
+    coef = np.arange(24.0).reshape(4, 6)
+    st = np.array([1, 1, 2, 1], dtype=np.int32)
+    b.dump_outputs(str(tmp_path / "all"), {"coeff": coef, "status": st})
+    got = np.load(tmp_path / "all" / "coeff.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, coef)
+    s = np.load(tmp_path / "all" / "status.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, st) and not (tmp_path / "all" / "coeff_index.npy").exists()
+    # above the limit: the same seeded sample on every call, indices next to the values, within the limit
+    b.DUMP_BYTES_MAX = 8 * 64
+    big = np.random.default_rng(0).normal(size=(100, 30))
+    for tag in ("x", "y"):
+        b.dump_outputs(str(tmp_path / tag), {"coeff": big, "status": np.ones(100, dtype=np.int32)})
+    for name in ("coeff", "status"):
+        vx, ix = np.load(tmp_path / "x" / f"{name}.npy"), np.load(tmp_path / "x" / f"{name}_index.npy")
+        assert np.array_equal(vx, np.load(tmp_path / "y" / f"{name}.npy")) and np.array_equal(ix, np.load(tmp_path / "y" / f"{name}_index.npy"))
+        assert vx.dtype == np.float64 and ix.size == vx.size > 0 and np.all(np.diff(ix) > 0)
+    iv = np.load(tmp_path / "x" / "coeff_index.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "x" / "coeff.npy"), big.reshape(-1)[iv])
+    total = sum(os.path.getsize(os.path.join(tmp_path, "x", f)) - 128 for f in os.listdir(tmp_path / "x"))
+    assert total <= b.DUMP_BYTES_MAX

@@ -19,7 +19,7 @@ def test_bench_two_ranks_on_one_gpu(config, port):
     env = dict(os.environ, UAVQP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--config", str(config),
-           "--cpu-sample", "0", "--no-traffic", "--no-fp64", "--repeats", "2"]
+           "--cpu-sample", "0", "--no-traffic", "--no-fp64", "--repeats", "2", "--full"]
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-3000:]
     line = [ln for ln in run.stdout.splitlines() if ln.startswith("{")][-1]
@@ -56,15 +56,15 @@ def test_bench_eight_ranks_rehearsal_in_the_drivers_shape(config):
     """the command the driver will run on its 8-GPU node -- `python3 bench.py --gpus 8 --steps 20 --warmup 5`, no
     launcher: the script spawns its eight ranks -- rehearsed with the eight ranks sharing THIS box's one GPU (UAVQP_BENCH_BACKEND=gloo: RCCL
     refuses two ranks per device).  Exactly one JSON line, n_gpus = 8, `value` = the sum over the ranks, the shard bounds those of
-    uavqp_shard_bounds_ragged, `allgather` with `value_with_gather` (and the keys of the overlapped leg, null on the stand-in).  Nothing about
-    speed is read off it."""
+    uavqp_shard_bounds_ragged, and with --full `allgather` with `value_with_gather` (and the keys of the overlapped leg, null on the stand-in).
+    Nothing about speed is read off it."""
     import numpy as np
 
     from uav_motion_planning_amd import distributed as D
     from uav_motion_planning_amd import workloads as W
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(UAVQP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5"] + (["--config", str(config)] if config != 2 else [])
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--full"] + (["--config", str(config)] if config != 2 else [])
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-3000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
@@ -91,7 +91,7 @@ def test_force_dist_world_one_costs_nothing_and_reports_the_rccl_world():
     """VERDICT r5 item 5(b, d): with torch.distributed + RCCL initialised at world size 1 (`--force-dist`) the headline figure stays within
     3 % of the plain N = 1 run on the same box, the exchange goes through the ctx communicator, RCCL itself reports rank 0 of 1
     (allgather.rccl_world, from ncclCommCount), and the overlapped leg (gather of step i while step i + 1 solves) produces a figure."""
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "200", "--warmup", "20", "--cpu-sample", "0", "--no-traffic", "--no-fp64",
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "200", "--warmup", "20", "--cpu-sample", "0", "--no-traffic", "--no-fp64",
             "--pipelined-streams", "0", "--no-time-modes", "--no-other-configs", "--parity-sample", "0"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29631", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("UAVQP_BENCH_BACKEND", None)

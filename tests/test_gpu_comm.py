@@ -88,7 +88,7 @@ def test_bench_exchange_leg_goes_through_the_ctx_communicator(config):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29600 + config), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("UAVQP_BENCH_BACKEND", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--gpus", "1", "--config", str(config), "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-dist", "--gpus", "1", "--config", str(config), "--steps", "3", "--warmup", "1",
            "--cpu-sample", "0", "--no-traffic", "--no-fp64", "--pipelined-streams", "0", "--no-time-modes"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]

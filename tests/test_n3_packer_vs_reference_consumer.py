@@ -6,7 +6,7 @@ recipe in oracle/Makefile; ROS / message / Eigen headers are stand-ins).  The me
 be the polynomials the solver produced -- evaluated independently by the reference's own PolyTraj on the ORIGINAL
 [axis][segment][2r] layout (oracle.ref_polytraj_eval) and by oracle/poly_eval.c.
 
-The libraries are built in this container (where /root/reference is mounted) and travel to the GPU box prebuilt."""
+The libraries and the program are built by `make -C oracle ref` where the reference sources are present and travel with oracle/_ref/."""
 import os
 import subprocess
 
@@ -17,9 +17,7 @@ from uav_motion_planning_amd import adapters as A
 from uav_motion_planning_amd import workloads as W
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "uav_motion_planning_amd")
-REF = "/root/reference/src/planner"
-EXE = os.path.join(ROOT, "tests", "cpp", "test_traj_adapters")
+EXE = os.path.join(ROOT, "oracle", "_ref", "test_traj_adapters")
 
 
 @pytest.fixture(scope="module")
@@ -79,19 +77,15 @@ def test_exact_minimiser_of_the_reference_qp_arrives_intact_at_the_server(refts)
     assert np.max(np.abs(got[1:])) < 1e-11                      # end velocity and acceleration = 0
 
 
-def test_cpp_adapters_with_the_reference_server_as_consumer():
+def test_cpp_adapters_with_the_reference_server_as_consumer(oracle):
     """cpp/traj_adapters.h in a C++ program that has the reference's poly_traj_server.cpp compiled in (tests/cpp/test_traj_adapters.cpp):
     flattenPaths (+ the RRT* empty-path case), boundaryFromOdometry, packPolynomialTrajectory -> fillMessage -> trajCallback ->
     cmdPubCallback, downsampleDensePath."""
-    if not os.path.exists(os.path.join(REF, "traj_server", "src", "poly_traj_server.cpp")):
-        if not os.path.exists(EXE):
-            pytest.skip("/root/reference not mounted and no prebuilt program")
-    else:
-        import uav_motion_planning_amd as U
-        U.build()
-        subprocess.check_call(["g++", "-O2", "-std=c++14", f"-I{PKG}/cpp", f"-I{ROOT}/oracle/ref_shim/rosmsgs", f"-I{ROOT}/oracle/ref_shim",
-                               f"-I{REF}", f"-I{REF}/traj_utils/include", os.path.join(ROOT, "tests", "cpp", "test_traj_adapters.cpp"),
-                               f"-L{PKG}", "-luavqp", f"-Wl,-rpath,{PKG}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-o", EXE])
+    import uav_motion_planning_amd as U
+    U.build()
+    oracle.build_ref()          # compiles tests/cpp/test_traj_adapters.cpp with the reference's server where its sources are present
+    if not os.path.exists(EXE):
+        pytest.skip(f"{EXE} not built (needs the reference sources)")
     out = subprocess.run([EXE], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "traj_adapters ok" in out.stdout, out.stdout + out.stderr
 

@@ -6,8 +6,9 @@ claim of INTEGRATION.md, executed for both callers the reference has.  Stand-ins
 test-only stubs of tests/cpp/ros_stub (ros, the message types, and the two out-of-scope packages test_minimum_jerk.cpp
 includes: rrt_star.h "finds" a fixed path, grid_map.h is empty; ros::spin() delivers one odometry message and one goal).
 
-CPU part (here, /root/reference mounted, no GPU): they compile, run, and fail LOUDLY through the reference's own messages
--- the product has no CPU fallback.  GPU part (the prebuilt binaries travel): they run to completion without them."""
+The programs are built by `make -C oracle ref` (oracle/Makefile, run by __graft_entry__.build() where the reference sources are
+present) into oracle/_ref/, and travel with it.  CPU part (no GPU): they run and fail LOUDLY through the reference's own messages
+-- the product has no CPU fallback.  GPU part: they run to completion without them."""
 import os
 import re
 import subprocess
@@ -15,16 +16,8 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/src/planner/test/src"
-PKG = os.path.join(ROOT, "uav_motion_planning_amd")
-PROGRAMS = {"test_qpsolve": os.path.join(ROOT, "tests", "cpp", "ref_test_qpsolve"),
-            "test_minimum_jerk": os.path.join(ROOT, "tests", "cpp", "ref_test_minimum_jerk")}
-
-
-def _build(name):
-    subprocess.check_call(["g++", "-O2", "-std=c++14", f"-I{PKG}/cpp", f"-I{PKG}/cpp/eigen_shim", f"-I{ROOT}/tests/cpp/ros_stub",
-                           os.path.join(REF, name + ".cpp"), f"{PKG}/cpp/minimum_control.cpp", f"-L{PKG}", "-luavqp", f"-Wl,-rpath,{PKG}",
-                           "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-o", PROGRAMS[name]])
+PROGRAMS = {"test_qpsolve": os.path.join(ROOT, "oracle", "_ref", "ref_test_qpsolve"),
+            "test_minimum_jerk": os.path.join(ROOT, "oracle", "_ref", "ref_test_minimum_jerk")}
 
 
 def _has_gpu():
@@ -36,12 +29,12 @@ def _has_gpu():
 
 
 @pytest.mark.parametrize("name", sorted(PROGRAMS))
-def test_reference_program_compiles_unmodified_and_fails_loudly_without_a_gpu(name):
-    if not os.path.exists(os.path.join(REF, name + ".cpp")):
-        pytest.skip("/root/reference not mounted")
+def test_reference_program_compiles_unmodified_and_fails_loudly_without_a_gpu(name, oracle):
     import uav_motion_planning_amd as U
     U.build()
-    _build(name)
+    oracle.build_ref()          # compiles the reference's program where its sources are present
+    if not os.path.exists(PROGRAMS[name]):
+        pytest.skip(f"{PROGRAMS[name]} not built (needs the reference sources)")
     out = subprocess.run([PROGRAMS[name]], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     if not _has_gpu():
@@ -56,7 +49,7 @@ def test_reference_program_compiles_unmodified_and_fails_loudly_without_a_gpu(na
 def test_reference_program_runs_on_the_gpu_backend(name):
     exe = PROGRAMS[name]
     if not os.path.exists(exe):
-        pytest.skip(f"prebuilt {exe} did not travel (built where /root/reference is mounted)")
+        pytest.skip(f"{exe} not built (needs the reference sources)")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "failed" not in out.stdout and "faiure" not in out.stdout

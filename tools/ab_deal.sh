@@ -5,7 +5,7 @@ OUT=${1:-gpurun_out/ab_deal.log}
 : > $OUT
 for t in 0 1 0 1; do
   for c in "3 0" "5 0" "3 2"; do set -- $c
-    UAVQP_DEAL_TICKETS=$t python bench.py --config $1 --rows $2 --steps 6 --warmup 2 --no-fp64 --kernels-only --cpu-sample 0 --no-traffic 2>/dev/null | TAG="tickets=$t config $1 rows $2" python -c '
+    UAVQP_DEAL_TICKETS=$t python bench.py --full --config $1 --rows $2 --steps 6 --warmup 2 --no-fp64 --kernels-only --cpu-sample 0 --no-traffic 2>/dev/null | TAG="tickets=$t config $1 rows $2" python -c '
 import json, os, sys
 x = json.loads(sys.stdin.read().strip().split("\n")[-1])
 print(os.environ["TAG"], round(x["ms_per_step"], 4), x["parity"]["within_tolerance"], [(k["kernel"][:34], round(k["avg_us"], 1)) for k in x.get("kernels", [])[:4]])' >> $OUT

@@ -33,17 +33,17 @@ mkdir -p $O
   echo "commands: see tools/collect_profiles.sh at the commit whose csrc/ hashes to the value above"
 } > $O/MANIFEST.txt
 cd /tmp; export TMPDIR=/tmp
-python $R/bench.py > $O/bench4096.json 2> $O/bench4096.err
-python $R/bench.py --steps 20 --warmup 5 > $O/bench4096_steps20.json 2>> $O/bench4096.err          # the driver's invocation
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof4096 -o b -- python $R/bench.py --cpu-sample 0 --no-traffic --no-fp64 --pipelined-streams 0 --no-other-configs > $O/bench4096_under_prof.json 2>> $O/bench4096.err
+python $R/bench.py --full > $O/bench4096.json 2> $O/bench4096.err
+python $R/bench.py --full --steps 20 --warmup 5 > $O/bench4096_steps20.json 2>> $O/bench4096.err          # the driver's step counts
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof4096 -o b -- python $R/bench.py --full --cpu-sample 0 --no-traffic --no-fp64 --pipelined-streams 0 --no-other-configs > $O/bench4096_under_prof.json 2>> $O/bench4096.err
 cp $(find $O/prof4096 -name "*kernel_stats.csv" | head -1) $O/bench4096_kernel_stats.csv
 for B in 65536 1048576; do
-  python $R/bench.py --batch $B --steps 50 --cpu-sample 0 --pipelined-streams 0 > $O/bench_$B.json 2>> $O/bench4096.err
+  python $R/bench.py --full --batch $B --steps 50 --cpu-sample 0 --pipelined-streams 0 > $O/bench_$B.json 2>> $O/bench4096.err
 done
-timeout 600 python $R/bench.py --config 3 --steps 10 --warmup 3 --cpu-sample 512 > $O/bench_config3.json 2>> $O/bench4096.err
-timeout 600 python $R/bench.py --config 3 --rows 2 --steps 3 --warmup 1 --cpu-sample 0 > $O/bench_config3_rows2.json 2>> $O/bench4096.err
-timeout 600 python $R/bench.py --config 4 --steps 50 --cpu-sample 0 > $O/bench_config4.json 2>> $O/bench4096.err
-timeout 600 python $R/bench.py --config 5 --steps 10 --cpu-sample 0 > $O/bench_config5.json 2>> $O/bench4096.err
+timeout 600 python $R/bench.py --full --config 3 --steps 10 --warmup 3 --cpu-sample 512 > $O/bench_config3.json 2>> $O/bench4096.err
+timeout 600 python $R/bench.py --full --config 3 --rows 2 --steps 3 --warmup 1 --cpu-sample 0 > $O/bench_config3_rows2.json 2>> $O/bench4096.err
+timeout 600 python $R/bench.py --full --config 4 --steps 50 --cpu-sample 0 > $O/bench_config4.json 2>> $O/bench4096.err
+timeout 600 python $R/bench.py --full --config 5 --steps 10 --cpu-sample 0 > $O/bench_config5.json 2>> $O/bench4096.err
 # rocprofv3 --kernel-trace --stats of every other config (the same commands as --inner child runs: kernels only)
 for C in "3 0" "3 2" "4 0" "5 0"; do
   set -- $C

@@ -9,7 +9,7 @@ OUT=${1:-gpurun_out/g2_probe_ab.log}
 for rep in 1 2; do
   for L in uav_motion_planning_amd/libuavqp.so tools/ubench/libuavqp_g2nows.so tools/ubench/libuavqp_g2noout.so tools/ubench/libuavqp_g2none.so; do
     [ -f $L ] || continue
-    UAVQP_LIB_PATH=$(realpath $L) python bench.py --config 4 --steps 50 --warmup 10 --no-fp64 --kernels-only --cpu-sample 0 --no-traffic 2>/dev/null | TAG="$L" python -c '
+    UAVQP_LIB_PATH=$(realpath $L) python bench.py --full --config 4 --steps 50 --warmup 10 --no-fp64 --kernels-only --cpu-sample 0 --no-traffic 2>/dev/null | TAG="$L" python -c '
 import json, os, sys
 x = json.loads(sys.stdin.read().strip().split("\n")[-1])
 print(os.environ["TAG"], "step", round(1e3 * x["ms_per_step"], 2), "us", [(k["kernel"][:40], round(k["avg_us"], 1)) for k in x.get("kernels", [])[:3]])' >> $OUT

@@ -2,11 +2,13 @@
 # usage (on the GPU box): tools/pmc.sh <outname> "<counters>" -- <bench args>
 # Collects PMC counters for the solve kernels in their own rocprofv3 pass (kernel-trace only).
 name=$1; ctrs=$2; shift 3
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+D=$(mktemp -d); trap 'rm -rf "$D"' EXIT     # rocprofv3's CSV files; the summary goes to stdout
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/pmc_$name -o $name -- python $GRAFT_REPO_ROOT/bench.py --cpu-sample 0 --no-fp64 "$@" > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $D/pmc_$name -o $name -- python $ROOT/bench.py --full --cpu-sample 0 --no-fp64 "$@" > /dev/null 2>&1
 python - <<PY
 import csv,collections,glob
-f=glob.glob("$GRAFT_REPO_ROOT/gpurun_out/pmc_$name/*counter_collection.csv")[0]
+f=glob.glob("$D/pmc_$name/*counter_collection.csv")[0]
 acc=collections.defaultdict(lambda: collections.defaultdict(float)); n=collections.Counter()
 for r in csv.DictReader(open(f)):
     k=r["Kernel_Name"][:60]
