@@ -419,8 +419,8 @@ int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_traj, int unif
  *                       (test_kino_astar_searching.launch:49-57: robot 0.4 x 0.1 m, 7 m/s, 10 m/s^2); check_samples = 0 skips
  *                       the check and the repair; check_robot_r / _h > 0 check with another ellipsoid than the boxes were built with
  *   result              (may be NULL) rounds run, repair rounds run, trajectories still stretching at the cap, colliding at the first
- *                       check / of those with a blocked waypoint / colliding at the last check, trajectories not UAVQP_SOLVED, the dt
- *                       of the check grid. */
+ *                       check / of those with a blocked waypoint / colliding at the last check, trajectories not UAVQP_SOLVED, rows
+ *                       placed and kept by a rows repair (0 from this entry point), the dt of the check grid. */
 typedef struct uavqp_pipeline_params {
     int32_t struct_size;
     int32_t max_rounds;
@@ -434,7 +434,7 @@ typedef struct uavqp_pipeline_params {
     double check_robot_r, check_robot_h;
 } uavqp_pipeline_params;
 typedef struct uavqp_pipeline_result {
-    int32_t rounds, repairs, still_stretching, colliding_before_repair, colliding_with_blocked_waypoints, colliding_after, unsolved, reserved_;
+    int32_t rounds, repairs, still_stretching, colliding_before_repair, colliding_with_blocked_waypoints, colliding_after, unsolved, repair_rows;
     double check_dt;
 } uavqp_pipeline_result;
 void uavqp_default_pipeline_params(uavqp_pipeline_params* out);
@@ -449,6 +449,44 @@ int uavqp_corridor_pipeline_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_
                                  const double* waypoints, double* times, const double* bc, const double* obstacles, int n_obs,
                                  const uavqp_pipeline_params* params, double* coeff_out, int32_t* status_out, double* corr_lo,
                                  double* corr_hi, int32_t* first_hit, uavqp_pipeline_result* result);
+
+/* Rows repair of the pipeline: between-knot collisions become position rows instead of shrunken boxes.
+ * uavqp_repair_rows_from_hits_device -- rows from the per-sample verdicts of a check (d_flags [n_traj][n_samples] uint8, the samples
+ *   t_s = t0 + s dt of uavqp_ellipsoid_check_device, segment rule of uavqp_eval_batch_device).  For every segment i with colliding samples:
+ *   s = middle sample of the first colliding run in it, tau = (t_s - t_start_i) / T_i clamped to [1/32, 31/32]; attitude from the
+ *   polynomials' acceleration at t_s (b3 = normalize(acc + 9.81 z), the frame of uavqp_corridor_from_cloud_device), E = Rot diag(robot_r,
+ *   robot_r, robot_h) Rot'; anchor a = p(t_s) pushed out of the cloud: while g(a) = min over ALL points o of |E^-1 (o - a)| is below
+ *   G = 2, at most 4 times, a <- o* + (a - o*) G / g(a) with o* the arg-min point.  If g(a) > 1 at the end the segment gets the row
+ *   a - h <= p_i(tau T_i) <= a + h, h_k = min(h_max, (g(a) - 1) / (3 |E^-1 e_k|)) (the guarantee of the knot boxes: the robot ellipsoid
+ *   anywhere in the row's box holds no point), derivative 0 -- in slot 0, or in slot 1 when slot 0 is taken and |tau - tau_0| > 1/32;
+ *   both taken: no row.  d_waypoints is the batch's [sum(M+1)][3] (checked, not read).
+ *   d_row_tau / d_row_deriv / d_row_lo / d_row_hi  IN / OUT, the rows_per_segment = 2 layout of uavqp_solve_rows_batch_device
+ *   d_new_rows   [n_traj] int32 OUT: rows placed by this call.  Asynchronous on the ctx stream.
+ * uavqp_corridor_pipeline_rows_device / _host -- uavqp_corridor_pipeline_* with the rows repair in place of the box repair (arguments
+ *   of those plus the caller's row arrays [total_segments][2] (tau, deriv) / [total_segments][2][3] (lo, hi): set to unused (deriv -1)
+ *   by the call, on return the rows of the final solve).  A repair round: the check also writes its per-sample verdicts, the rows above
+ *   are placed for every colliding trajectory (blocked waypoints included; not for M = 1 or M > 63) with the CHECK's ellipsoid, the
+ *   trajectories that got one are gathered into a ragged sub-batch (one row per segment when none uses slot 1) and solved by
+ *   uavqp_solve_rows_batch_device with their knot boxes and all their rows; one time re-allocation of the sub-batch and, if it stretched
+ *   anything, a second rows solve (rows are fractions of T_i: they stay attached); what ended UAVQP_SOLVED is written back, the others keep
+ *   coefficients, durations and status and lose the rows of that round.  Knot boxes never change, trajectories never flagged are not
+ *   touched: their output is the repair_rounds = 0 output bit for bit.  result->repair_rows = rows in place on return. */
+int uavqp_repair_rows_from_hits_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
+                                       const double* d_waypoints, const double* d_times, const double* d_coeff, int n_samples, double t0,
+                                       double dt, const uint8_t* d_flags, const double* d_obstacles, int n_obs, double robot_r,
+                                       double robot_h, double h_max, double* d_row_tau, int32_t* d_row_deriv, double* d_row_lo,
+                                       double* d_row_hi, int32_t* d_new_rows);
+int uavqp_corridor_pipeline_rows_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                                        const int32_t* d_seg_offsets, const double* d_waypoints, double* d_times, const double* d_bc,
+                                        const double* d_obstacles, int n_obs, const uavqp_grid* grid, const uavqp_pipeline_params* params,
+                                        double* d_coeff_out, int32_t* d_status_out, double* d_corr_lo, double* d_corr_hi,
+                                        int32_t* d_first_hit, double* d_row_tau, int32_t* d_row_deriv, double* d_row_lo,
+                                        double* d_row_hi, uavqp_pipeline_result* result);
+int uavqp_corridor_pipeline_rows_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                                      const double* waypoints, double* times, const double* bc, const double* obstacles, int n_obs,
+                                      const uavqp_pipeline_params* params, double* coeff_out, int32_t* status_out, double* corr_lo,
+                                      double* corr_hi, int32_t* first_hit, double* row_tau, int32_t* row_deriv, double* row_lo,
+                                      double* row_hi, uavqp_pipeline_result* result);
 
 /* quadrotor_msgs/PolynomialTrajectory packer.  HOST function, no ctx, no device: turns ONE solved
  * trajectory (the [axis][segment][2r] slice of coeff_out that belongs to it) into the arrays of the message the rest of the

@@ -56,6 +56,9 @@ SYMBOLS = (
     "uavqp_default_pipeline_params",
     "uavqp_corridor_pipeline_device",
     "uavqp_corridor_pipeline_host",
+    "uavqp_repair_rows_from_hits_device",
+    "uavqp_corridor_pipeline_rows_device",
+    "uavqp_corridor_pipeline_rows_host",
     "uavqp_pack_polynomial_trajectory",
     "uavqp_shard_bounds",
     "uavqp_shard_bounds_ragged",
@@ -99,7 +102,7 @@ class PipelineResult(ctypes.Structure):
     """uavqp_pipeline_result of include/uavqp.h."""
     _fields_ = [("rounds", ctypes.c_int32), ("repairs", ctypes.c_int32), ("still_stretching", ctypes.c_int32),
                 ("colliding_before_repair", ctypes.c_int32), ("colliding_with_blocked_waypoints", ctypes.c_int32),
-                ("colliding_after", ctypes.c_int32), ("unsolved", ctypes.c_int32), ("reserved_", ctypes.c_int32), ("check_dt", ctypes.c_double)]
+                ("colliding_after", ctypes.c_int32), ("unsolved", ctypes.c_int32), ("repair_rows", ctypes.c_int32), ("check_dt", ctypes.c_double)]
 
 
 def build(force=False):
@@ -169,6 +172,12 @@ def lib():
                                                  dp, ip, dp, dp, ip, ctypes.POINTER(PipelineResult)]
     L.uavqp_corridor_pipeline_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, dp, i32, ctypes.POINTER(PipelineParams), dp, ip, dp, dp,
                                                ip, ctypes.POINTER(PipelineResult)]
+    L.uavqp_repair_rows_from_hits_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, dp, i32, ctypes.c_double, ctypes.c_double, vp, dp, i32,
+                                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, dp, ip, dp, dp, ip]
+    L.uavqp_corridor_pipeline_rows_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, dp, i32, vp, ctypes.POINTER(PipelineParams),
+                                                      dp, ip, dp, dp, ip, dp, ip, dp, dp, ctypes.POINTER(PipelineResult)]
+    L.uavqp_corridor_pipeline_rows_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, dp, i32, ctypes.POINTER(PipelineParams), dp, ip, dp, dp,
+                                                    ip, dp, ip, dp, dp, ctypes.POINTER(PipelineResult)]
     L.uavqp_pack_polynomial_trajectory.argtypes = [i32, i32, dp, dp, dp, dp, dp, dp, vp, vp, vp]
     L.uavqp_shard_bounds.argtypes = [i32, i32, ip]
     L.uavqp_shard_bounds_ragged.argtypes = [ip, i32, i32, ip]

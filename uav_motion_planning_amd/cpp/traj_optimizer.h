@@ -28,6 +28,10 @@
 
 namespace traj_optimization {
 
+// How solvePipeline() repairs a trajectory the final collision check flags (include/uavqp.h): Boxes shrinks its knot boxes towards the
+// waypoints (last round: the waypoint equalities); Rows adds position rows inside the colliding segments and keeps the knot boxes.
+enum class PipelineRepair { Boxes, Rows };
+
 class TrajOptimizer {
   public:
     explicit TrajOptimizer(int order = 4, int device = 0) : order_(order), device_(device) {}
@@ -122,7 +126,10 @@ class TrajOptimizer {
     // corridorLo() / corridorHi() = the boxes of the final solve, firstHit() = first colliding sample per trajectory (check_samples =
     // free), pipelineResult() = the summary.  true iff the call succeeded and every trajectory is SOLVED (collisions are reported, not
     // turned into failure: a planner decides what to do with a colliding candidate).
-    bool solvePipeline(const double* obstacles, int n_obs, const uavqp_pipeline_params* params = nullptr) {
+    // repair = PipelineRepair::Rows: uavqp_corridor_pipeline_rows_host; repairRowTau() / repairRowDeriv() / repairRowLo() / repairRowHi()
+    // then hold the rows of the final solve ([segment][2], [segment][2][3]; deriv -1 = unused), empty after a Boxes call.
+    bool solvePipeline(const double* obstacles, int n_obs, const uavqp_pipeline_params* params = nullptr,
+                       PipelineRepair repair = PipelineRepair::Boxes) {
         if (n_traj_ <= 0 || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_])) return false;
         if (!ensureContext()) return false;
         if (bc_.empty()) bc_.assign(static_cast<size_t>(n_traj_) * 2 * (order_ - 1) * 3, 0.0);
@@ -135,8 +142,17 @@ class TrajOptimizer {
         pipe_hi_.assign(wp_.size(), 0.0);
         first_hit_.assign(n_traj_, pp.check_samples);
         pipe_result_ = uavqp_pipeline_result{};
-        const int rc = uavqp_corridor_pipeline_host(ctx_, order_, n_traj_, 0, 0, seg_offsets_.data(), wp_.data(), T_.data(), bc_.data(), obstacles, n_obs,
-                                                    &pp, coef_.data(), status_.data(), pipe_lo_.data(), pipe_hi_.data(), first_hit_.data(), &pipe_result_);
+        const size_t n_seg = static_cast<size_t>(seg_offsets_[n_traj_]);
+        const bool rows = repair == PipelineRepair::Rows;
+        repair_tau_.assign(rows ? 2 * n_seg : 0, 0.0);
+        repair_deriv_.assign(rows ? 2 * n_seg : 0, -1);
+        repair_lo_.assign(rows ? 6 * n_seg : 0, 0.0);
+        repair_hi_.assign(rows ? 6 * n_seg : 0, 0.0);
+        const int rc = rows ? uavqp_corridor_pipeline_rows_host(ctx_, order_, n_traj_, 0, 0, seg_offsets_.data(), wp_.data(), T_.data(), bc_.data(), obstacles,
+                                                                n_obs, &pp, coef_.data(), status_.data(), pipe_lo_.data(), pipe_hi_.data(), first_hit_.data(),
+                                                                repair_tau_.data(), repair_deriv_.data(), repair_lo_.data(), repair_hi_.data(), &pipe_result_)
+                            : uavqp_corridor_pipeline_host(ctx_, order_, n_traj_, 0, 0, seg_offsets_.data(), wp_.data(), T_.data(), bc_.data(), obstacles, n_obs,
+                                                           &pp, coef_.data(), status_.data(), pipe_lo_.data(), pipe_hi_.data(), first_hit_.data(), &pipe_result_);
         if (rc != UAVQP_OK) {
             std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
             return false;
@@ -148,6 +164,11 @@ class TrajOptimizer {
     const std::vector<double>& corridorHi() const { return pipe_hi_; }
     const std::vector<int32_t>& firstHit() const { return first_hit_; }
     const uavqp_pipeline_result& pipelineResult() const { return pipe_result_; }
+    int repairRows() const { return pipe_result_.repair_rows; }                  // rows placed and kept by the last Rows repair
+    const std::vector<double>& repairRowTau() const { return repair_tau_; }
+    const std::vector<int32_t>& repairRowDeriv() const { return repair_deriv_; }
+    const std::vector<double>& repairRowLo() const { return repair_lo_; }
+    const std::vector<double>& repairRowHi() const { return repair_hi_; }
 
     // ---- multi-GPU: one process (or thread) per GPU, every rank holds the whole batch description, solves its contiguous shard
     // (balanced by segment count) on its device and ends with ALL coefficients: uavqp_shard_bounds_ragged, uavqp_comm_create,
@@ -274,7 +295,8 @@ class TrajOptimizer {
     uavqp_ctx* ctx_ = nullptr;
     std::vector<int32_t> seg_offsets_, status_;
     std::vector<double> wp_, T_, bc_, coef_, lo_, hi_, pipe_lo_, pipe_hi_, row_tau_, row_lo_, row_hi_;
-    std::vector<int32_t> row_deriv_, first_hit_;
+    std::vector<int32_t> row_deriv_, first_hit_, repair_deriv_;
+    std::vector<double> repair_tau_, repair_lo_, repair_hi_;
     int rows_k_ = 0;
     uavqp_pipeline_result pipe_result_{};
 };

@@ -6,7 +6,8 @@
 //   re-allocation) -> SE(3) collision check of the result against a uniform grid over the cloud -> REPAIR: the boxes only bound the
 //   knots and carry the attitude of the first solve, so the check of the final polynomials is the arbiter: the boxes of every
 //   trajectory it flags are halved towards the searcher's waypoints (last round: collapsed onto them = the reference's equality
-//   problem) and the batch is re-solved, at most repair_rounds times.
+//   problem) and the batch is re-solved, at most repair_rounds times -- or, through uavqp_corridor_pipeline_rows_*, its between-knot hits
+//   become position rows of the general-rows solve on a sub-batch (the knot boxes stay; see the rows repair kernels below).
 //
 // The reference has no such loop (constant 1.0 s per segment, test_minimum_jerk.cpp:65-71; every row an equality,
 // minimum_control.cpp:98-125): nothing to mirror, parity is per inner solve (SURVEY.md section 8-a').
@@ -24,9 +25,13 @@ struct PipeCounters {
     unsigned int hit_blocked;    // ... of those: with an interior waypoint the cloud leaves no room around (degenerate box)
     unsigned int hit_repairable; // ... the rest (what a repair round works on)
     unsigned int unsolved;       // trajectories whose status is not UAVQP_SOLVED
-    unsigned int pad_[3];
+    unsigned int gathered;       // rows repair: trajectories that received a row this round (the sub-batch), its segments, its longest
+    unsigned int gathered_segments;
+    unsigned int gathered_max_m;
     unsigned long long tmax_bits;  // max over trajectories of the total duration (bits of a non-negative double: ordered like integers)
-    unsigned long long pad2_[3];
+    unsigned int gathered_slot1; // rows repair: some trajectory of the sub-batch uses row slot 1 (else it is packed one row per segment)
+    unsigned int rows_kept;      // rows repair: rows in place at the end of the call
+    unsigned long long pad2_[2];
 };
 static_assert(sizeof(PipeCounters) == 64, "counter block is one 64-byte record");
 
@@ -166,6 +171,325 @@ __global__ __launch_bounds__(64) void pipe_shrink_kernel(int n, int uniform, con
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Rows repair (uavqp_corridor_pipeline_rows_device): a between-knot hit becomes a position row p_i(tau T_i) in [a - h, a + h] around an
+// anchor a pushed out of the cloud, solved by the general-rows solve on a compact sub-batch of the trajectories that got one.
+// ---------------------------------------------------------------------------------------------------
+constexpr double REPAIR_PUSH_TARGET = 2.0;   // G: the anchor is pushed until its clearance reaches G (docs/measurement_log.md)
+constexpr int REPAIR_PUSH_STEPS = 4;         // at most this many pushes per row
+
+struct RepairRowsArgs {
+    int n_traj, uniform, n_samples, n_obs;
+    const int32_t* seg_offsets;
+    const double* times;
+    const double* coeff;
+    double t0, dt;
+    const unsigned long long* tmax_bits;   // optional (pipeline): dt = (double with these bits) / (n_samples - 1), as the check forms it
+    const uint8_t* flags;                  // [n_traj][n_samples] per-sample verdicts of the check
+    const int32_t* first_hit;              // optional: a trajectory with first_hit >= n_samples is skipped without a scan
+    const double* obs;
+    double robot_r, robot_h, h_max;
+    double* row_tau;                       // [segments][2] IN / OUT
+    int32_t* row_deriv;                    // [segments][2] IN / OUT
+    double* row_lo;                        // [segments][2][3] IN / OUT
+    double* row_hi;
+    int32_t* new_rows;                     // [n_traj] OUT: rows this call placed
+    uint8_t* placed;                       // optional [segments] OUT (bits set, the caller zeroes it): bit j = slot j placed by this call
+    int solvable_only;                     // pipeline: no rows for trajectories the rows solve cannot take (M < 2 or M > 63)
+};
+
+// the segment of sample s and the time in it: the rule of uavqp_eval_batch_device / the check kernels (past the end: the end point)
+__device__ __forceinline__ int repair_sample_segment(const double* T, int M, double t0, double dt, int s, double& t) {
+    t = t0 + s * dt;
+    int idx = 0;
+    while (idx < M && t > T[idx] + 1e-4) { t -= T[idx]; ++idx; }
+    if (idx == M) { --idx; t = T[idx]; }
+    return idx;
+}
+
+// clearance g(a) = min over ALL points of |E^-1 (o - a)| (the metric of the check kernels, frame f = b1, b2, b3) and its arg-min (lowest
+// index on a tie), across the wave; every lane returns the same pair
+__device__ __forceinline__ double repair_clearance(const RepairRowsArgs& a, const double* p, const double* f, double ir, double ih, int& arg) {
+    double m = INFINITY;
+    int im = 0x7fffffff;
+    for (int o = threadIdx.x; o < a.n_obs; o += 64) {
+        const double* q = a.obs + (size_t)o * 3;
+        const double dx = q[0] - p[0], dy = q[1] - p[1], dz = q[2] - p[2];
+        const double e1 = (f[0] * dx + f[1] * dy + f[2] * dz) * ir;
+        const double e2 = (f[3] * dx + f[4] * dy + f[5] * dz) * ir;
+        const double e3 = (f[6] * dx + f[7] * dy + f[8] * dz) * ih;
+        const double v = e1 * e1 + e2 * e2 + e3 * e3;
+        if (v < m) { m = v; im = o; }       // (o ascends per lane: the first of equal values stays)
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double om = __shfl_xor(m, d, 64);
+        const int oi = __shfl_xor(im, d, 64);
+        if (om < m || (om == m && oi < im)) { m = om; im = oi; }
+    }
+    arg = im;
+    return sqrt(m);
+}
+
+// One wave per trajectory.  Lane i finds the first colliding run of samples in segment i (M > 64: in passes of 64 segments) and the
+// frame at its middle sample; the wave then treats those segments one after the other: the clearance is a min over the whole cloud.
+template <int R>
+__global__ __launch_bounds__(64) void repair_rows_kernel(RepairRowsArgs a) {
+    constexpr int NC = 2 * R;
+    const int lane = threadIdx.x;
+    const double dt = a.tmax_bits ? __longlong_as_double((long long)*a.tmax_bits) / (double)(a.n_samples - 1) : a.dt;
+    const double ir = 1.0 / a.robot_r, ih = 1.0 / a.robot_h;
+    for (int b = blockIdx.x; b < a.n_traj; b += gridDim.x) {
+        int s0, M;
+        if (a.uniform > 0) { M = a.uniform; s0 = b * M; } else { s0 = a.seg_offsets[b]; M = a.seg_offsets[b + 1] - s0; }
+        const bool skip = M < 1 || a.n_samples < 1 || (a.solvable_only && (M < 2 || M > 63)) || (a.first_hit && a.first_hit[b] >= a.n_samples);
+        int count = 0;
+        if (!skip) {
+            const double* T = a.times + s0;
+            const uint8_t* fl = a.flags + (size_t)b * a.n_samples;
+            for (int i0 = 0; i0 < M; i0 += 64) {
+                const int i = i0 + lane;
+                int first = -1, last = -1;
+                if (i < M) {
+                    for (int s = 0; s < a.n_samples; ++s) {
+                        double t;
+                        const int idx = repair_sample_segment(T, M, a.t0, dt, s, t);
+                        if (idx < i) continue;
+                        if (idx > i) break;
+                        const bool f = fl[s] != 0;
+                        if (first < 0) {
+                            if (f) first = last = s;
+                        } else if (f) {
+                            last = s;
+                        } else {
+                            break;               // the first run is over
+                        }
+                    }
+                }
+                const bool want = first >= 0;
+                double tau = 0.0, p[3] = {0.0, 0.0, 0.0}, fr[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+                if (want) {
+                    double t;
+                    (void)repair_sample_segment(T, M, a.t0, dt, (first + last) >> 1, t);
+                    tau = fmin(fmax(t / T[i], 1.0 / 32.0), 31.0 / 32.0);
+                    double acc[3];
+#pragma unroll
+                    for (int ax = 0; ax < 3; ++ax) {
+                        const double* ca = a.coeff + (size_t)3 * NC * s0 + ((size_t)ax * M + i) * NC;
+                        double pv = 0.0, av = 0.0;
+#pragma unroll
+                        for (int j = NC - 1; j >= 0; --j) pv = fma(pv, t, ca[j]);
+#pragma unroll
+                        for (int j = NC - 1; j >= 2; --j) av = fma(av, t, (double)(j * (j - 1)) * ca[j]);
+                        p[ax] = pv;
+                        acc[ax] = av;
+                    }
+                    // kino_astar.cpp:724-727, as in the check kernels
+                    const double n3 = sqrt(acc[0] * acc[0] + acc[1] * acc[1] + (acc[2] + 9.81) * (acc[2] + 9.81));
+                    const double b3[3] = {acc[0] / n3, acc[1] / n3, (acc[2] + 9.81) / n3};
+                    const double n2 = sqrt(b3[2] * b3[2] + b3[1] * b3[1]);
+                    const double b2[3] = {0.0, b3[2] / n2, -b3[1] / n2};
+                    const double c1[3] = {b2[1] * b3[2] - b2[2] * b3[1], b2[2] * b3[0] - b2[0] * b3[2], b2[0] * b3[1] - b2[1] * b3[0]};
+                    const double n1 = sqrt(c1[0] * c1[0] + c1[1] * c1[1] + c1[2] * c1[2]);
+#pragma unroll
+                    for (int ax = 0; ax < 3; ++ax) {
+                        fr[ax] = c1[ax] / n1;
+                        fr[3 + ax] = b2[ax];
+                        fr[6 + ax] = b3[ax];
+                    }
+                }
+                unsigned long long todo = __ballot(want);
+                while (todo) {
+                    const int j = __builtin_ctzll(todo);
+                    todo &= todo - 1ull;
+                    double q[3], f[9];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) q[c] = __shfl(p[c], j, 64);
+#pragma unroll
+                    for (int c = 0; c < 9; ++c) f[c] = __shfl(fr[c], j, 64);
+                    // push-out: radially away from the nearest point (in the metric) until the clearance reaches G
+                    int arg = 0;
+                    double g = repair_clearance(a, q, f, ir, ih, arg);
+                    for (int k = 0; k < REPAIR_PUSH_STEPS && g < REPAIR_PUSH_TARGET && g > 0.0; ++k) {
+                        const double* o = a.obs + (size_t)arg * 3;
+                        const double sc = REPAIR_PUSH_TARGET / g;
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) q[c] = o[c] + (q[c] - o[c]) * sc;
+                        g = repair_clearance(a, q, f, ir, ih, arg);
+                    }
+                    if (lane == j && g > 1.0) {
+                        const size_t sg = (size_t)s0 + i;
+                        int slot = -1;
+                        if (a.row_deriv[2 * sg] < 0) slot = 0;
+                        else if (a.row_deriv[2 * sg + 1] < 0 && fabs(tau - a.row_tau[2 * sg]) > 1.0 / 32.0) slot = 1;
+                        if (slot >= 0) {
+                            const size_t rw = 2 * sg + slot;
+                            a.row_tau[rw] = tau;
+                            a.row_deriv[rw] = 0;
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) {
+                                // |E^-1 e_c|^2 = Q_cc: the half-widths of uavqp_corridor_from_cloud_device around the anchor
+                                const double qcc = (f[c] * f[c] + f[3 + c] * f[3 + c]) * ir * ir + f[6 + c] * f[6 + c] * ih * ih;
+                                double h = (g - 1.0) / (3.0 * sqrt(qcc));
+                                h = h < a.h_max ? h : a.h_max;
+                                a.row_lo[3 * rw + c] = q[c] - h;
+                                a.row_hi[3 * rw + c] = q[c] + h;
+                            }
+                            if (a.placed) a.placed[sg] |= (uint8_t)(1u << slot);
+                            ++count;
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) count += __shfl_xor(count, d, 64);
+        if (lane == 0) a.new_rows[b] = count;
+    }
+}
+
+// every row slot unused (deriv -1, zero tau and bounds)
+__global__ __launch_bounds__(256) void pipe_rows_clear_kernel(long long n_slots, double* __restrict__ tau, int32_t* __restrict__ deriv,
+                                                             double* __restrict__ lo, double* __restrict__ hi) {
+    for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < n_slots; k += (long long)gridDim.x * 256) {
+        tau[k] = 0.0;
+        deriv[k] = -1;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { lo[3 * k + c] = 0.0; hi[3 * k + c] = 0.0; }
+    }
+}
+
+// The trajectories with new_rows > 0, in index order: list[k], the exclusive prefix of their segment counts (the sub-batch's CSR offsets,
+// sub_off[count] = its segments) -> the counter block (gathered, gathered_segments, gathered_max_m, gathered_slot1).  One workgroup.
+__global__ __launch_bounds__(1024) void pipe_rows_compact_kernel(int n, int uniform, const int32_t* __restrict__ seg_offsets,
+                                                                 const int32_t* __restrict__ new_rows, const int32_t* __restrict__ deriv,
+                                                                 int32_t* __restrict__ list, int32_t* __restrict__ sub_off, PipeCounters* c) {
+    __shared__ int s_cnt[1024], s_seg[1024];
+    int base_cnt = 0, base_seg = 0, mmax = 0, slot1 = 0;
+    for (int c0 = 0; c0 < n; c0 += 1024) {
+        const int b = c0 + (int)threadIdx.x;
+        int sel = 0, M = 0;
+        if (b < n && new_rows[b] > 0) {
+            int s0;
+            if (uniform > 0) { M = uniform; s0 = b * M; } else { s0 = seg_offsets[b]; M = seg_offsets[b + 1] - s0; }
+            sel = 1;
+            mmax = M > mmax ? M : mmax;
+            for (int i = 0; i < M; ++i) slot1 |= deriv[2 * ((size_t)s0 + i) + 1] >= 0;
+        }
+        s_cnt[threadIdx.x] = sel;
+        s_seg[threadIdx.x] = sel ? M : 0;
+        __syncthreads();
+        for (int d = 1; d < 1024; d <<= 1) {       // inclusive scans
+            const int vc = threadIdx.x >= (unsigned)d ? s_cnt[threadIdx.x - d] : 0;
+            const int vs = threadIdx.x >= (unsigned)d ? s_seg[threadIdx.x - d] : 0;
+            __syncthreads();
+            s_cnt[threadIdx.x] += vc;
+            s_seg[threadIdx.x] += vs;
+            __syncthreads();
+        }
+        if (sel) {
+            const int k = base_cnt + s_cnt[threadIdx.x] - 1;
+            list[k] = b;
+            sub_off[k] = base_seg + s_seg[threadIdx.x] - M;
+        }
+        base_cnt += s_cnt[1023];
+        base_seg += s_seg[1023];
+        __syncthreads();
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int om = __shfl_xor(mmax, d, 64);
+        mmax = om > mmax ? om : mmax;
+        slot1 |= __shfl_xor(slot1, d, 64);
+    }
+    if (threadIdx.x == 0) sub_off[base_cnt] = base_seg;
+    if ((threadIdx.x & 63) == 0) {
+        if (mmax) atomicMax(&c->gathered_max_m, (unsigned)mmax);
+        if (slot1) atomicOr(&c->gathered_slot1, 1u);
+    }
+    if (threadIdx.x == 0) {
+        c->gathered = (unsigned)base_cnt;
+        c->gathered_segments = (unsigned)base_seg;
+    }
+}
+
+// sub-batch k <- trajectory list[k]: waypoints, knot boxes, durations, boundary conditions, its rows (K = 1: slot 0 only).  One wave each.
+__global__ __launch_bounds__(64) void pipe_rows_gather_kernel(int G, int uniform, const int32_t* __restrict__ seg_offsets, int r, int K,
+                                                              const int32_t* __restrict__ list, const int32_t* __restrict__ sub_off,
+                                                              const double* __restrict__ wp, const double* __restrict__ lo, const double* __restrict__ hi,
+                                                              const double* __restrict__ times, const double* __restrict__ bc,
+                                                              const double* __restrict__ tau, const int32_t* __restrict__ deriv,
+                                                              const double* __restrict__ rlo, const double* __restrict__ rhi,
+                                                              double* __restrict__ g_wp, double* __restrict__ g_lo, double* __restrict__ g_hi,
+                                                              double* __restrict__ g_times, double* __restrict__ g_bc, double* __restrict__ g_tau,
+                                                              int32_t* __restrict__ g_deriv, double* __restrict__ g_rlo, double* __restrict__ g_rhi) {
+    for (int k = blockIdx.x; k < G; k += gridDim.x) {
+        const int b = list[k], d0 = sub_off[k];
+        int s0, M;
+        if (uniform > 0) { M = uniform; s0 = b * M; } else { s0 = seg_offsets[b]; M = seg_offsets[b + 1] - s0; }
+        const size_t e0 = 3 * ((size_t)s0 + b), f0 = 3 * ((size_t)d0 + k);
+        for (int i = threadIdx.x; i < 3 * (M + 1); i += 64) {
+            g_wp[f0 + i] = wp[e0 + i];
+            g_lo[f0 + i] = lo[e0 + i];
+            g_hi[f0 + i] = hi[e0 + i];
+        }
+        for (int i = threadIdx.x; i < M; i += 64) g_times[(size_t)d0 + i] = times[(size_t)s0 + i];
+        const int nbc = 2 * (r - 1) * 3;
+        for (int i = threadIdx.x; i < nbc; i += 64) g_bc[(size_t)k * nbc + i] = bc[(size_t)b * nbc + i];
+        for (int q = threadIdx.x; q < M * K; q += 64) {
+            const int i = q / K, j = q - i * K;
+            const size_t src = 2 * ((size_t)s0 + i) + j, dst = (size_t)K * ((size_t)d0 + i) + j;
+            g_tau[dst] = tau[src];
+            g_deriv[dst] = deriv[src];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { g_rlo[3 * dst + c] = rlo[3 * src + c]; g_rhi[3 * dst + c] = rhi[3 * src + c]; }
+        }
+    }
+}
+
+// sub-batch k -> trajectory list[k] when its solve(s) ended UAVQP_SOLVED (st2 may be null: no second solve): coefficients, durations, status.
+// Otherwise the rows this round placed are withdrawn; coefficients, durations and status stay what they were.
+__global__ __launch_bounds__(64) void pipe_rows_scatter_kernel(int G, int uniform, const int32_t* __restrict__ seg_offsets, int r,
+                                                               const int32_t* __restrict__ list, const int32_t* __restrict__ sub_off,
+                                                               const int32_t* __restrict__ st1, const int32_t* __restrict__ st2,
+                                                               const double* __restrict__ g_coeff, const double* __restrict__ g_times,
+                                                               double* __restrict__ coeff, double* __restrict__ times, int32_t* __restrict__ status,
+                                                               const uint8_t* __restrict__ placed, double* __restrict__ tau, int32_t* __restrict__ deriv,
+                                                               double* __restrict__ rlo, double* __restrict__ rhi) {
+    for (int k = blockIdx.x; k < G; k += gridDim.x) {
+        const int b = list[k], d0 = sub_off[k];
+        int s0, M;
+        if (uniform > 0) { M = uniform; s0 = b * M; } else { s0 = seg_offsets[b]; M = seg_offsets[b + 1] - s0; }
+        const bool ok = st1[k] == UAVQP_SOLVED && (!st2 || st2[k] == UAVQP_SOLVED);
+        if (ok) {
+            const int nc = 3 * 2 * r;
+            for (int i = threadIdx.x; i < nc * M; i += 64) coeff[(size_t)nc * s0 + i] = g_coeff[(size_t)nc * d0 + i];
+            for (int i = threadIdx.x; i < M; i += 64) times[(size_t)s0 + i] = g_times[(size_t)d0 + i];
+            if (threadIdx.x == 0) status[b] = UAVQP_SOLVED;
+        } else {
+            for (int q = threadIdx.x; q < 2 * M; q += 64) {
+                const size_t sg = (size_t)s0 + q / 2;
+                if (placed[sg] & (1u << (q & 1))) {
+                    const size_t rw = 2 * sg + (q & 1);
+                    tau[rw] = 0.0;
+                    deriv[rw] = -1;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) { rlo[3 * rw + c] = 0.0; rhi[3 * rw + c] = 0.0; }
+                }
+            }
+        }
+    }
+}
+
+// rows in place (deriv >= 0) -> rows_kept
+__global__ __launch_bounds__(256) void pipe_rows_count_kernel(long long n_slots, const int32_t* __restrict__ deriv, PipeCounters* c) {
+    int nk = 0;
+    for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < n_slots; k += (long long)gridDim.x * 256) nk += deriv[k] >= 0;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) nk += __shfl_xor(nk, d, 64);
+    if ((threadIdx.x & 63) == 0 && nk) atomicAdd(&c->rows_kept, (unsigned)nk);
+}
+
 }  // namespace uavqp
 
 static int ensure_pipe_ws(uavqp_ctx* ctx, size_t bytes) {
@@ -202,11 +526,56 @@ extern "C" void uavqp_default_pipeline_params(uavqp_pipeline_params* p) {
     p->check_robot_h = 0.0;
 }
 
-extern "C" int uavqp_corridor_pipeline_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
-                                              const int32_t* d_seg_offsets, const double* d_waypoints, double* d_times, const double* d_bc,
-                                              const double* d_obstacles, int n_obs, const uavqp_grid* grid,
-                                              const uavqp_pipeline_params* params, double* d_coeff_out, int32_t* d_status_out,
-                                              double* d_corr_lo, double* d_corr_hi, int32_t* d_first_hit, uavqp_pipeline_result* result) {
+// rows from the hits of a check (include/uavqp.h uavqp_repair_rows_from_hits_device); the pipeline's form takes dt from the counter block,
+// skips trajectories the check found free (first_hit) and those the rows solve cannot take, and records the slots it fills
+static int repair_rows_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
+                            const double* d_coeff, int n_samples, double t0, double dt, const unsigned long long* d_tmax_bits,
+                            const uint8_t* d_flags, const int32_t* d_first_hit, const double* d_obstacles, int n_obs, double robot_r,
+                            double robot_h, double h_max, double* d_row_tau, int32_t* d_row_deriv, double* d_row_lo, double* d_row_hi,
+                            int32_t* d_new_rows, uint8_t* d_placed, int solvable_only) {
+    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0 || n_samples < 0 || n_obs < 0 || !(robot_r > 0.0) || !(robot_h > 0.0) ||
+        !(h_max >= 0.0))
+        return UAVQP_ERR_INVALID_ARG;
+    if (n_traj == 0) return UAVQP_OK;
+    if (!d_times || !d_coeff || !d_new_rows || (n_samples > 0 && !d_flags) || (n_obs > 0 && !d_obstacles) || !d_row_tau || !d_row_deriv ||
+        !d_row_lo || !d_row_hi || (uniform_segments == 0 && !d_seg_offsets))
+        return UAVQP_ERR_INVALID_ARG;
+    UAVQP_HIP(hipSetDevice(ctx->device));
+    uavqp::RepairRowsArgs a;
+    a.n_traj = n_traj; a.uniform = uniform_segments; a.n_samples = n_samples; a.n_obs = n_obs;
+    a.seg_offsets = d_seg_offsets; a.times = d_times; a.coeff = d_coeff; a.t0 = t0; a.dt = dt; a.tmax_bits = d_tmax_bits;
+    a.flags = d_flags; a.first_hit = d_first_hit; a.obs = d_obstacles; a.robot_r = robot_r; a.robot_h = robot_h; a.h_max = h_max;
+    a.row_tau = d_row_tau; a.row_deriv = d_row_deriv; a.row_lo = d_row_lo; a.row_hi = d_row_hi; a.new_rows = d_new_rows;
+    a.placed = d_placed; a.solvable_only = solvable_only;
+    const int grid = n_traj < ctx->num_cus * 32 ? n_traj : ctx->num_cus * 32;
+    if (r == 3)
+        hipLaunchKernelGGL(uavqp::repair_rows_kernel<3>, dim3(grid), dim3(64), 0, ctx->stream, a);
+    else
+        hipLaunchKernelGGL(uavqp::repair_rows_kernel<4>, dim3(grid), dim3(64), 0, ctx->stream, a);
+    UAVQP_HIP(hipGetLastError());
+    return UAVQP_OK;
+}
+
+extern "C" int uavqp_repair_rows_from_hits_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
+                                                  const double* d_waypoints, const double* d_times, const double* d_coeff, int n_samples,
+                                                  double t0, double dt, const uint8_t* d_flags, const double* d_obstacles, int n_obs,
+                                                  double robot_r, double robot_h, double h_max, double* d_row_tau, int32_t* d_row_deriv,
+                                                  double* d_row_lo, double* d_row_hi, int32_t* d_new_rows) {
+    if (n_traj > 0 && !d_waypoints) return UAVQP_ERR_INVALID_ARG;
+    return repair_rows_impl(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff, n_samples, t0, dt, nullptr, d_flags, nullptr,
+                            d_obstacles, n_obs, robot_r, robot_h, h_max, d_row_tau, d_row_deriv, d_row_lo, d_row_hi, d_new_rows, nullptr, 0);
+}
+
+// The box path (d_row_deriv == NULL) and the rows path (all four row arrays given) share this body; the box path runs exactly the
+// launches it ran before the rows path existed.
+static int corridor_pipeline_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                                  const int32_t* d_seg_offsets, const double* d_waypoints, double* d_times, const double* d_bc,
+                                  const double* d_obstacles, int n_obs, const uavqp_grid* grid,
+                                  const uavqp_pipeline_params* params, double* d_coeff_out, int32_t* d_status_out,
+                                  double* d_corr_lo, double* d_corr_hi, int32_t* d_first_hit, double* d_row_tau, int32_t* d_row_deriv,
+                                  double* d_row_lo, double* d_row_hi, uavqp_pipeline_result* result) {
+    const bool rows_mode = d_row_deriv != nullptr;
+    if (rows_mode && (!d_row_tau || !d_row_lo || !d_row_hi)) return UAVQP_ERR_INVALID_ARG;
     if (!ctx || !params || params->struct_size != (int32_t)sizeof(uavqp_pipeline_params) || (r != 3 && r != 4) || n_traj < 0 ||
         uniform_segments < 0 || n_obs < 0 || total_segments < 0)
         return UAVQP_ERR_INVALID_ARG;
@@ -251,7 +620,18 @@ extern "C" int uavqp_corridor_pipeline_device(uavqp_ctx* ctx, int r, int n_traj,
     // (two lists: round k compacts round k - 1's into the other one; then their two counts and the per-workgroup counts of a large compaction)
     const size_t o_sc = o_cp + 2 * align256(sizeof(int32_t) * (size_t)n) + 256 + align256(sizeof(int) * (size_t)cblocks);
     const size_t o_gc = o_sc + (g_across ? align256(sizeof(double) * (size_t)n) : 0);
-    const size_t need = o_gc + (g_across ? align256(sizeof(double) * (size_t)n * uavqp::corridor_gcache_stride) : 0);
+    const size_t o_rw = o_gc + (g_across ? align256(sizeof(double) * (size_t)n * uavqp::corridor_gcache_stride) : 0);
+    // rows repair: per-sample flags of the check, new rows per trajectory, slots placed this round, the sub-batch (list, CSR offsets,
+    // inputs, rows, outputs) -- sized for the whole batch
+    const size_t ns_ = (size_t)(checking ? P.check_samples : 0), nt_ = (size_t)n, ts_ = (size_t)total_segments, tr_ = ts_ + nt_;
+    const size_t rw_sz[] = {align256(nt_ * ns_), align256(sizeof(int32_t) * nt_), align256(ts_), 2 * align256(sizeof(int32_t) * (nt_ + 1)),
+                            3 * align256(sizeof(double) * 3 * tr_), align256(sizeof(double) * ts_), align256(sizeof(double) * nt_ * 2 * (r - 1) * 3),
+                            align256(sizeof(double) * 2 * ts_), align256(sizeof(int32_t) * 2 * ts_), 2 * align256(sizeof(double) * 6 * ts_),
+                            align256(sizeof(double) * 3 * 2 * r * ts_), 4 * align256(sizeof(int32_t) * nt_)};
+    size_t rw_total = 0;
+    if (rows_mode)
+        for (size_t x : rw_sz) rw_total += x;
+    const size_t need = o_rw + rw_total;
     int rc = ensure_pipe_ws(ctx, need);
     if (rc != UAVQP_OK) return rc;
     char* base = (char*)ctx->d_pipe;
@@ -270,6 +650,27 @@ extern "C" int uavqp_corridor_pipeline_device(uavqp_ctx* ctx, int r, int n_traj,
     uint8_t* d_roomy = (uint8_t*)(base + o_rm);
     uint8_t* d_flag = (uint8_t*)(base + o_fl);
     uavqp::PipeCounters* h_cnt = (uavqp::PipeCounters*)ctx->h_pipe;
+    char* rp = base + o_rw;
+    auto take = [&](size_t bytes) { char* q = rp; rp += bytes; return q; };
+    uint8_t* d_sflags = rows_mode ? (uint8_t*)take(rw_sz[0]) : nullptr;
+    int32_t* d_newrows = rows_mode ? (int32_t*)take(rw_sz[1]) : nullptr;
+    uint8_t* d_placed = rows_mode ? (uint8_t*)take(rw_sz[2]) : nullptr;
+    int32_t* d_glist = rows_mode ? (int32_t*)take(rw_sz[3] / 2) : nullptr;
+    int32_t* d_goff = rows_mode ? (int32_t*)take(rw_sz[3] / 2) : nullptr;
+    double* d_gwp = rows_mode ? (double*)take(rw_sz[4] / 3) : nullptr;
+    double* d_glo = rows_mode ? (double*)take(rw_sz[4] / 3) : nullptr;
+    double* d_ghi = rows_mode ? (double*)take(rw_sz[4] / 3) : nullptr;
+    double* d_gT = rows_mode ? (double*)take(rw_sz[5]) : nullptr;
+    double* d_gbc = rows_mode ? (double*)take(rw_sz[6]) : nullptr;
+    double* d_gtau = rows_mode ? (double*)take(rw_sz[7]) : nullptr;
+    int32_t* d_gdrv = rows_mode ? (int32_t*)take(rw_sz[8]) : nullptr;
+    double* d_grlo = rows_mode ? (double*)take(rw_sz[9] / 2) : nullptr;
+    double* d_grhi = rows_mode ? (double*)take(rw_sz[9] / 2) : nullptr;
+    double* d_gco = rows_mode ? (double*)take(rw_sz[10]) : nullptr;
+    int32_t* d_gst1 = rows_mode ? (int32_t*)take(rw_sz[11] / 4) : nullptr;
+    int32_t* d_gst2 = rows_mode ? (int32_t*)take(rw_sz[11] / 4) : nullptr;
+    int32_t* d_git = rows_mode ? (int32_t*)take(rw_sz[11] / 4) : nullptr;
+    int32_t* d_gch = rows_mode ? (int32_t*)take(rw_sz[11] / 4) : nullptr;
     int cgrid = (n + 255) / 256;
     if (cgrid > ctx->num_cus * 8) cgrid = ctx->num_cus * 8;
 
@@ -310,6 +711,12 @@ extern "C" int uavqp_corridor_pipeline_device(uavqp_ctx* ctx, int r, int n_traj,
     };
 
     hipLaunchKernelGGL(uavqp::pipe_begin_kernel, dim3(d_scale ? (n + 255) / 256 : 1), dim3(256), 0, s, d_scale, n, d_cnt);
+    if (rows_mode && total_segments > 0) {
+        long long rgrid = (2LL * total_segments + 255) / 256;
+        if (rgrid > (long long)ctx->num_cus * 8) rgrid = (long long)ctx->num_cus * 8;
+        hipLaunchKernelGGL(uavqp::pipe_rows_clear_kernel, dim3((unsigned)rgrid), dim3(256), 0, s, 2LL * total_segments, d_row_tau, d_row_deriv,
+                           d_row_lo, d_row_hi);
+    }
     if (uni == 0) {
         unsigned int last_offset = 0u;
         rc = await_word(4, probe_seq, &last_offset);
@@ -398,6 +805,40 @@ extern "C" int uavqp_corridor_pipeline_device(uavqp_ctx* ctx, int r, int n_traj,
     }
     // 4. check + repair
     int repairs = 0, before = -1, blocked = 0, after = 0, summary_unsolved = -1;
+    // Rows repair round on the sub-batch of the G trajectories that received a row (list + CSR offsets made by the compaction): gather,
+    // general-rows solve with their knot boxes and rows, one re-allocation of the sub-batch and a second solve if it stretched anything,
+    // then write back what ended UAVQP_SOLVED -- the others keep coefficients, durations and status and lose this round's rows.
+    auto rows_repair_round = [&](int G, int Gseg, int Gmax, int K) -> int {
+        int ggrid = G < ctx->num_cus * 32 ? G : ctx->num_cus * 32;
+        hipLaunchKernelGGL(uavqp::pipe_rows_gather_kernel, dim3(ggrid), dim3(64), 0, s, G, uni, d_seg_offsets, r, K, (const int32_t*)d_glist,
+                           (const int32_t*)d_goff, d_waypoints, (const double*)d_corr_lo, (const double*)d_corr_hi, (const double*)d_times, d_bc,
+                           (const double*)d_row_tau, (const int32_t*)d_row_deriv, (const double*)d_row_lo, (const double*)d_row_hi, d_gwp, d_glo,
+                           d_ghi, d_gT, d_gbc, d_gtau, d_gdrv, d_grlo, d_grhi);
+        int rc_ = rows_batch_impl(ctx, r, G, 0, Gmax, d_goff, d_gwp, d_gT, d_gbc, d_glo, d_ghi, K, d_gtau, d_gdrv, d_grlo, d_grhi, d_gco, d_gst1,
+                                  d_git, nullptr, Gseg);
+        if (rc_ != UAVQP_OK) return rc_;
+        rc_ = time_reallocate_impl(ctx, r, G, 0, d_goff, d_gT, d_gco, P.v_max, P.a_max, P.samples_per_seg, P.max_stretch, d_gch, nullptr);
+        if (rc_ != UAVQP_OK) return rc_;
+        hipLaunchKernelGGL(uavqp::pipe_zero_kernel, dim3(1), dim3(64), 0, s, d_cnt);
+        int g2 = (G + 255) / 256;
+        if (g2 > ctx->num_cus * 8) g2 = ctx->num_cus * 8;
+        hipLaunchKernelGGL(uavqp::pipe_count_kernel, dim3(g2), dim3(256), 0, s, (const int32_t*)d_gch, (const int32_t*)nullptr, G, d_cnt);
+        rc_ = read_counters();
+        if (rc_ != UAVQP_OK) return rc_;
+        still = (int)h_cnt->changed;
+        const bool again = still > 0;
+        if (again) {   // rows are fractions of T_i: they stay attached to the stretched segments
+            rc_ = rows_batch_impl(ctx, r, G, 0, Gmax, d_goff, d_gwp, d_gT, d_gbc, d_glo, d_ghi, K, d_gtau, d_gdrv, d_grlo, d_grhi, d_gco, d_gst2,
+                                  d_git, nullptr, Gseg);
+            if (rc_ != UAVQP_OK) return rc_;
+        }
+        hipLaunchKernelGGL(uavqp::pipe_rows_scatter_kernel, dim3(ggrid), dim3(64), 0, s, G, uni, d_seg_offsets, r, (const int32_t*)d_glist,
+                           (const int32_t*)d_goff, (const int32_t*)d_gst1, again ? (const int32_t*)d_gst2 : (const int32_t*)nullptr,
+                           (const double*)d_gco, (const double*)d_gT, d_coeff_out, d_times, d_status_out, (const uint8_t*)d_placed, d_row_tau,
+                           d_row_deriv, d_row_lo, d_row_hi);
+        UAVQP_HIP(hipGetLastError());
+        return UAVQP_OK;
+    };
     double check_dt = 0.0;
     uavqp_grid* own_grid = nullptr;
     if (checking) {
@@ -415,10 +856,20 @@ extern "C" int uavqp_corridor_pipeline_device(uavqp_ctx* ctx, int r, int n_traj,
             hipLaunchKernelGGL(uavqp::pipe_check_prep_kernel, dim3(pgrid), dim3(256), 0, s, n, uni, d_seg_offsets, (const double*)d_times,
                                (const double*)d_corr_lo, (const double*)d_corr_hi, pass == 0 ? d_roomy : (uint8_t*)nullptr, d_fh, P.check_samples, d_cnt);
             rc = ellipsoid_check_grid_impl(ctx, r, n, uni, d_seg_offsets, d_times, d_coeff_out, P.check_samples, 0.0, 0.0, &d_cnt->tmax_bits, grid,
-                                           chk_r, chk_h, d_fh, nullptr);
+                                           chk_r, chk_h, d_fh, d_sflags);
             if (rc != UAVQP_OK) break;
             hipLaunchKernelGGL(uavqp::pipe_hits_kernel, dim3(cgrid), dim3(256), 0, s, n, (const int32_t*)d_fh, P.check_samples, (const uint8_t*)d_roomy, d_flag,
                                (const int32_t*)d_status_out, d_cnt);
+            if (rows_mode && repairs < P.repair_rounds) {
+                // rows from the hits (dt from the counter block, as the check formed it) and the sub-batch they make: its size arrives
+                // with the check's counters
+                if (total_segments > 0) UAVQP_HIP(hipMemsetAsync(d_placed, 0, (size_t)total_segments, s));
+                rc = repair_rows_impl(ctx, r, n, uni, d_seg_offsets, d_times, d_coeff_out, P.check_samples, 0.0, 0.0, &d_cnt->tmax_bits, d_sflags,
+                                      d_fh, d_obstacles, n_obs, chk_r, chk_h, P.h_max, d_row_tau, d_row_deriv, d_row_lo, d_row_hi, d_newrows, d_placed, 1);
+                if (rc != UAVQP_OK) break;
+                hipLaunchKernelGGL(uavqp::pipe_rows_compact_kernel, dim3(1), dim3(1024), 0, s, n, uni, d_seg_offsets, (const int32_t*)d_newrows,
+                                   (const int32_t*)d_row_deriv, d_glist, d_goff, d_cnt);
+            }
             rc = read_counters();
             if (rc != UAVQP_OK) break;
             double tmax;
@@ -429,6 +880,14 @@ extern "C" int uavqp_corridor_pipeline_device(uavqp_ctx* ctx, int r, int n_traj,
             if (before < 0) {
                 before = (int)h_cnt->hit;
                 blocked = (int)h_cnt->hit_blocked;
+            }
+            if (rows_mode) {
+                if (h_cnt->hit == 0 || repairs >= P.repair_rounds || h_cnt->gathered == 0) break;
+                rc = rows_repair_round((int)h_cnt->gathered, (int)h_cnt->gathered_segments, (int)h_cnt->gathered_max_m, h_cnt->gathered_slot1 ? 2 : 1);
+                if (rc != UAVQP_OK) break;
+                summary_unsolved = -1;
+                ++repairs;
+                continue;
             }
             if (h_cnt->hit_repairable == 0 || repairs >= P.repair_rounds) break;
             // halve the boxes of the flagged trajectories towards their waypoints (last round: the waypoint equalities), re-solve
@@ -459,8 +918,17 @@ extern "C" int uavqp_corridor_pipeline_device(uavqp_ctx* ctx, int r, int n_traj,
         if (rc != UAVQP_OK) return rc;
         summary_unsolved = (int)h_cnt->unsolved;
     }
+    int rows_kept = 0;
+    if (rows_mode && total_segments > 0) {
+        hipLaunchKernelGGL(uavqp::pipe_zero_kernel, dim3(1), dim3(64), 0, s, d_cnt);
+        hipLaunchKernelGGL(uavqp::pipe_rows_count_kernel, dim3(cgrid), dim3(256), 0, s, 2LL * total_segments, (const int32_t*)d_row_deriv, d_cnt);
+        rc = read_counters();
+        if (rc != UAVQP_OK) return rc;
+        rows_kept = (int)h_cnt->rows_kept;
+    }
     UAVQP_HIP(hipGetLastError());
     if (result) {
+        result->repair_rows = rows_kept;
         result->rounds = rounds;
         result->repairs = repairs;
         result->still_stretching = still;
@@ -473,11 +941,34 @@ extern "C" int uavqp_corridor_pipeline_device(uavqp_ctx* ctx, int r, int n_traj,
     return UAVQP_OK;
 }
 
-extern "C" int uavqp_corridor_pipeline_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments,
-                                            const int32_t* seg_offsets, const double* waypoints, double* times, const double* bc,
-                                            const double* obstacles, int n_obs, const uavqp_pipeline_params* params, double* coeff_out,
-                                            int32_t* status_out, double* corr_lo, double* corr_hi, int32_t* first_hit,
-                                            uavqp_pipeline_result* result) {
+extern "C" int uavqp_corridor_pipeline_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                                              const int32_t* d_seg_offsets, const double* d_waypoints, double* d_times, const double* d_bc,
+                                              const double* d_obstacles, int n_obs, const uavqp_grid* grid,
+                                              const uavqp_pipeline_params* params, double* d_coeff_out, int32_t* d_status_out,
+                                              double* d_corr_lo, double* d_corr_hi, int32_t* d_first_hit, uavqp_pipeline_result* result) {
+    return corridor_pipeline_impl(ctx, r, n_traj, uniform_segments, max_segments, total_segments, d_seg_offsets, d_waypoints, d_times, d_bc,
+                                  d_obstacles, n_obs, grid, params, d_coeff_out, d_status_out, d_corr_lo, d_corr_hi, d_first_hit, nullptr, nullptr,
+                                  nullptr, nullptr, result);
+}
+
+extern "C" int uavqp_corridor_pipeline_rows_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                                                   const int32_t* d_seg_offsets, const double* d_waypoints, double* d_times, const double* d_bc,
+                                                   const double* d_obstacles, int n_obs, const uavqp_grid* grid,
+                                                   const uavqp_pipeline_params* params, double* d_coeff_out, int32_t* d_status_out,
+                                                   double* d_corr_lo, double* d_corr_hi, int32_t* d_first_hit, double* d_row_tau,
+                                                   int32_t* d_row_deriv, double* d_row_lo, double* d_row_hi, uavqp_pipeline_result* result) {
+    if (n_traj > 0 && (!d_row_tau || !d_row_deriv || !d_row_lo || !d_row_hi)) return UAVQP_ERR_INVALID_ARG;
+    return corridor_pipeline_impl(ctx, r, n_traj, uniform_segments, max_segments, total_segments, d_seg_offsets, d_waypoints, d_times, d_bc,
+                                  d_obstacles, n_obs, grid, params, d_coeff_out, d_status_out, d_corr_lo, d_corr_hi, d_first_hit, d_row_tau,
+                                  d_row_deriv, d_row_lo, d_row_hi, result);
+}
+
+static int corridor_pipeline_host_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments,
+                                       const int32_t* seg_offsets, const double* waypoints, double* times, const double* bc,
+                                       const double* obstacles, int n_obs, const uavqp_pipeline_params* params, double* coeff_out,
+                                       int32_t* status_out, double* corr_lo, double* corr_hi, int32_t* first_hit, double* row_tau,
+                                       int32_t* row_deriv, double* row_lo, double* row_hi, uavqp_pipeline_result* result) {
+    const bool rows_mode = row_deriv != nullptr;
     if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0 || n_obs < 0) return UAVQP_ERR_INVALID_ARG;
     if (result) *result = uavqp_pipeline_result{};
     if (n_traj == 0) return UAVQP_OK;
@@ -506,7 +997,9 @@ extern "C" int uavqp_corridor_pipeline_host(uavqp_ctx* ctx, int r, int n_traj, i
     const size_t b_obs = align256(sizeof(double) * 3 * (size_t)(n_obs > 0 ? n_obs : 1));
     const size_t b_out = align256(sizeof(double) * 3 * 2 * r * (size_t)total_seg);
     const size_t b_st = align256(sizeof(int32_t) * (size_t)n_traj);
-    int rc = ensure_stage(ctx, b_off + 3 * b_wp + b_t + b_bc + b_obs + b_out + 2 * b_st);
+    const size_t b_rt = rows_mode ? align256(sizeof(double) * 2 * (size_t)total_seg) : 0, b_rd = rows_mode ? align256(sizeof(int32_t) * 2 * (size_t)total_seg) : 0;
+    const size_t b_rb = rows_mode ? align256(sizeof(double) * 6 * (size_t)total_seg) : 0;
+    int rc = ensure_stage(ctx, b_off + 3 * b_wp + b_t + b_bc + b_obs + b_out + 2 * b_st + b_rt + b_rd + 2 * b_rb);
     if (rc != UAVQP_OK) return rc;
     char* p = (char*)ctx->d_stage;
     int32_t* d_off = uniform_segments > 0 ? nullptr : (int32_t*)p; p += b_off;
@@ -518,7 +1011,11 @@ extern "C" int uavqp_corridor_pipeline_host(uavqp_ctx* ctx, int r, int n_traj, i
     double* d_obs = (double*)p; p += b_obs;
     double* d_out = (double*)p; p += b_out;
     int32_t* d_st = (int32_t*)p; p += b_st;
-    int32_t* d_fh = (int32_t*)p;
+    int32_t* d_fh = (int32_t*)p; p += b_st;
+    double* d_rt = rows_mode ? (double*)p : nullptr; p += b_rt;
+    int32_t* d_rd = rows_mode ? (int32_t*)p : nullptr; p += b_rd;
+    double* d_rl = rows_mode ? (double*)p : nullptr; p += b_rb;
+    double* d_rh = rows_mode ? (double*)p : nullptr;
     hipStream_t s = ctx->stream;
     if (d_off) UAVQP_HIP(hipMemcpyAsync(d_off, seg_offsets, sizeof(int32_t) * (size_t)(n_traj + 1), hipMemcpyHostToDevice, s));
     UAVQP_HIP(hipMemcpyAsync(d_wp, waypoints, sizeof(double) * n_wp, hipMemcpyHostToDevice, s));
@@ -526,9 +1023,15 @@ extern "C" int uavqp_corridor_pipeline_host(uavqp_ctx* ctx, int r, int n_traj, i
     UAVQP_HIP(hipMemcpyAsync(d_bc, bc, sizeof(double) * (size_t)n_traj * 2 * (r - 1) * 3, hipMemcpyHostToDevice, s));
     if (n_obs > 0) UAVQP_HIP(hipMemcpyAsync(d_obs, obstacles, sizeof(double) * 3 * (size_t)n_obs, hipMemcpyHostToDevice, s));
     UAVQP_HIP(hipMemsetAsync(d_out, 0, sizeof(double) * 3 * 2 * r * (size_t)total_seg, s));   // an invalid trajectory comes back as zeros
-    rc = uavqp_corridor_pipeline_device(ctx, r, n_traj, uniform_segments, Mmax, (int)total_seg, d_off, d_wp, d_t, d_bc, d_obs, n_obs, nullptr, params,
-                                        d_out, d_st, d_lo, d_hi, d_fh, result);
+    rc = corridor_pipeline_impl(ctx, r, n_traj, uniform_segments, Mmax, (int)total_seg, d_off, d_wp, d_t, d_bc, d_obs, n_obs, nullptr, params,
+                                d_out, d_st, d_lo, d_hi, d_fh, d_rt, d_rd, d_rl, d_rh, result);
     if (rc != UAVQP_OK) return rc;
+    if (rows_mode && total_seg > 0) {
+        UAVQP_HIP(hipMemcpyAsync(row_tau, d_rt, sizeof(double) * 2 * (size_t)total_seg, hipMemcpyDeviceToHost, s));
+        UAVQP_HIP(hipMemcpyAsync(row_deriv, d_rd, sizeof(int32_t) * 2 * (size_t)total_seg, hipMemcpyDeviceToHost, s));
+        UAVQP_HIP(hipMemcpyAsync(row_lo, d_rl, sizeof(double) * 6 * (size_t)total_seg, hipMemcpyDeviceToHost, s));
+        UAVQP_HIP(hipMemcpyAsync(row_hi, d_rh, sizeof(double) * 6 * (size_t)total_seg, hipMemcpyDeviceToHost, s));
+    }
     if (total_seg > 0) {
         UAVQP_HIP(hipMemcpyAsync(coeff_out, d_out, sizeof(double) * 3 * 2 * r * (size_t)total_seg, hipMemcpyDeviceToHost, s));
         UAVQP_HIP(hipMemcpyAsync(times, d_t, sizeof(double) * (size_t)total_seg, hipMemcpyDeviceToHost, s));   // stretched by the re-allocation
@@ -539,4 +1042,23 @@ extern "C" int uavqp_corridor_pipeline_host(uavqp_ctx* ctx, int r, int n_traj, i
     if (first_hit && params && params->check_samples > 0) UAVQP_HIP(hipMemcpyAsync(first_hit, d_fh, sizeof(int32_t) * (size_t)n_traj, hipMemcpyDeviceToHost, s));
     UAVQP_HIP(hipStreamSynchronize(s));
     return UAVQP_OK;
+}
+
+extern "C" int uavqp_corridor_pipeline_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments,
+                                            const int32_t* seg_offsets, const double* waypoints, double* times, const double* bc,
+                                            const double* obstacles, int n_obs, const uavqp_pipeline_params* params, double* coeff_out,
+                                            int32_t* status_out, double* corr_lo, double* corr_hi, int32_t* first_hit,
+                                            uavqp_pipeline_result* result) {
+    return corridor_pipeline_host_impl(ctx, r, n_traj, uniform_segments, max_segments, seg_offsets, waypoints, times, bc, obstacles, n_obs, params,
+                                       coeff_out, status_out, corr_lo, corr_hi, first_hit, nullptr, nullptr, nullptr, nullptr, result);
+}
+
+extern "C" int uavqp_corridor_pipeline_rows_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments,
+                                                 const int32_t* seg_offsets, const double* waypoints, double* times, const double* bc,
+                                                 const double* obstacles, int n_obs, const uavqp_pipeline_params* params, double* coeff_out,
+                                                 int32_t* status_out, double* corr_lo, double* corr_hi, int32_t* first_hit, double* row_tau,
+                                                 int32_t* row_deriv, double* row_lo, double* row_hi, uavqp_pipeline_result* result) {
+    if (n_traj > 0 && (!row_tau || !row_deriv || !row_lo || !row_hi)) return UAVQP_ERR_INVALID_ARG;
+    return corridor_pipeline_host_impl(ctx, r, n_traj, uniform_segments, max_segments, seg_offsets, waypoints, times, bc, obstacles, n_obs, params,
+                                       coeff_out, status_out, corr_lo, corr_hi, first_hit, row_tau, row_deriv, row_lo, row_hi, result);
 }

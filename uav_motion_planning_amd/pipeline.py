@@ -10,7 +10,7 @@ section 8-a').  torch is used here for ONE thing: allocating the output buffers 
 
 def corridor_pipeline_device(ctx, r, seg_offsets, waypoints, times, bc, obstacles, max_segments, robot_r=0.4, robot_h=0.1,
                              h_max=0.8, v_max=7.0, a_max=10.0, max_rounds=5, samples_per_seg=16, max_stretch=2.0,
-                             check_samples=100, grid=None, repair_rounds=2, check_robot=None, out=None):
+                             check_samples=100, grid=None, repair_rounds=2, check_robot=None, out=None, repair="boxes"):
     """All array arguments are torch CUDA tensors on the ctx's device (float64 / int32), ragged layout of include/uavqp.h:
     seg_offsets [n+1] int32, waypoints [sum(M+1), 3], times [sum M] (UPDATED IN PLACE by the re-allocation), bc [n, 2, r-1, 3],
     obstacles [n_obs, 3].  robot / limit defaults: test_kino_astar_searching.launch:49-57.
@@ -20,8 +20,14 @@ def corridor_pipeline_device(ctx, r, seg_offsets, waypoints, times, bc, obstacle
     Returns dict(coeff, status, corr_lo, corr_hi (the boxes of the final solve), first_hit (of the final check, check_samples = none),
     collision_free (bool per trajectory), colliding_before_repair, colliding_with_blocked_waypoints (of those: trajectories with a
     waypoint the cloud leaves no room around -- not repairable by narrower boxes), repairs, rounds, still_stretching, check_dt,
-    check_samples, all_solved); `collision_free` is formed on first access (see _PipelineResult)."""
+    check_samples, all_solved); `collision_free` is formed on first access (see _PipelineResult).
+    repair = "boxes" (default): the boxes of a flagged trajectory shrink towards its waypoints; "rows": its between-knot hits become
+    position rows around anchors pushed out of the cloud, the knot boxes stay (uavqp_corridor_pipeline_rows_device; INTEGRATION.md says
+    when to choose which).  In "rows" mode the result also carries row_tau / row_deriv [sum M, 2] and row_lo / row_hi [sum M, 2, 3] (the
+    rows of the final solve, deriv -1 = unused; `out` may hold them too) and repair_rows (rows placed and kept)."""
     import torch
+    if repair not in ("boxes", "rows"):
+        raise ValueError(f"repair must be 'boxes' or 'rows', not {repair!r}")
     n = seg_offsets.numel() - 1
     rows = waypoints.reshape(-1, 3).shape[0]
     dev = waypoints.device
@@ -34,15 +40,26 @@ def corridor_pipeline_device(ctx, r, seg_offsets, waypoints, times, bc, obstacle
     hi = out.get("corr_hi") if out.get("corr_hi") is not None else torch.zeros((rows, 3), dtype=torch.float64, device=dev)
     first_hit = out.get("first_hit") if out.get("first_hit") is not None else torch.full((n,), int(check_samples), dtype=torch.int32, device=dev)
     chk = (0.0, 0.0) if check_robot is None else check_robot
-    res = ctx.corridor_pipeline_device(r, n, 0, int(max_segments), total_seg, seg_offsets, waypoints, times, bc, obstacles, n_obs, coeff, status,
-                                       lo, hi, first_hit, grid=grid, robot_r=robot_r, robot_h=robot_h, h_max=h_max, v_max=v_max, a_max=a_max,
-                                       max_rounds=int(max_rounds), samples_per_seg=int(samples_per_seg), max_stretch=max_stretch,
-                                       check_samples=int(check_samples), repair_rounds=int(repair_rounds), check_robot_r=float(chk[0]),
-                                       check_robot_h=float(chk[1]))
+    params = dict(grid=grid, robot_r=robot_r, robot_h=robot_h, h_max=h_max, v_max=v_max, a_max=a_max, max_rounds=int(max_rounds),
+                  samples_per_seg=int(samples_per_seg), max_stretch=max_stretch, check_samples=int(check_samples),
+                  repair_rounds=int(repair_rounds), check_robot_r=float(chk[0]), check_robot_h=float(chk[1]))
+    extra = {}
+    if repair == "rows":
+        def buf(key, shape, dtype):
+            return out.get(key) if out.get(key) is not None else torch.empty(shape, dtype=dtype, device=dev)
+        extra = dict(row_tau=buf("row_tau", (total_seg, 2), torch.float64), row_deriv=buf("row_deriv", (total_seg, 2), torch.int32),
+                     row_lo=buf("row_lo", (total_seg, 2, 3), torch.float64), row_hi=buf("row_hi", (total_seg, 2, 3), torch.float64))
+        res = ctx.corridor_pipeline_rows_device(r, n, 0, int(max_segments), total_seg, seg_offsets, waypoints, times, bc, obstacles, n_obs, coeff,
+                                                status, lo, hi, extra["row_tau"], extra["row_deriv"], extra["row_lo"], extra["row_hi"], first_hit,
+                                                **params)
+        extra["repair_rows"] = res["repair_rows"]
+    else:
+        res = ctx.corridor_pipeline_device(r, n, 0, int(max_segments), total_seg, seg_offsets, waypoints, times, bc, obstacles, n_obs, coeff, status,
+                                           lo, hi, first_hit, **params)
     return _PipelineResult(coeff=coeff, status=status, corr_lo=lo, corr_hi=hi, first_hit=first_hit, check_samples=int(check_samples),
                            colliding_before_repair=res["colliding_before_repair"], colliding_with_blocked_waypoints=res["colliding_with_blocked_waypoints"],
                            repairs=res["repairs"], rounds=res["rounds"], still_stretching=res["still_stretching"], check_dt=res["check_dt"],
-                           all_solved=res["unsolved"] == 0)
+                           all_solved=res["unsolved"] == 0, **extra)
 
 
 class _PipelineResult(dict):
@@ -91,3 +108,27 @@ class _PipelineResult(dict):
     def copy(self):
         self._materialise()
         return dict(self)
+
+    def pop(self, key, *default):
+        self._materialise()
+        return dict.pop(self, key, *default)
+
+    def __delitem__(self, key):
+        self._materialise()
+        dict.__delitem__(self, key)
+
+    def setdefault(self, key, default=None):
+        self._materialise()
+        return dict.setdefault(self, key, default)
+
+    def __eq__(self, other):
+        self._materialise()
+        if isinstance(other, _PipelineResult):
+            other._materialise()
+        return dict.__eq__(self, other)
+
+    def __ne__(self, other):
+        eq = self.__eq__(other)
+        return eq if eq is NotImplemented else not eq
+
+    __hash__ = None

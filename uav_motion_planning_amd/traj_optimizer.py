@@ -169,25 +169,60 @@ class Context:
                                                           p(first_hit), p(flags))
         _lib.check(rc, "uavqp_ellipsoid_check_grid_device")
 
-    def corridor_pipeline_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc,
-                                 obstacles, n_obs, coeff_out, status_out, corr_lo, corr_hi, first_hit=None, grid=None, **params):
-        """uavqp_corridor_pipeline_device: BASELINE config 5 as one C-ABI call on device buffers (times is stretched in place).
-        params: fields of uavqp_pipeline_params that differ from uavqp_default_pipeline_params.  Returns the uavqp_pipeline_result
-        fields as a dict.  Synchronous."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)
+    @staticmethod
+    def _pipeline_params(params):
         pp = _lib.PipelineParams()
         _lib.lib().uavqp_default_pipeline_params(ctypes.byref(pp))
         for k, v in params.items():
             if not hasattr(pp, k) or k in ("struct_size", "reserved_"):
                 raise ValueError(f"unknown uavqp_pipeline_params field {k!r}")
             setattr(pp, k, v)
+        return pp
+
+    def corridor_pipeline_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc,
+                                 obstacles, n_obs, coeff_out, status_out, corr_lo, corr_hi, first_hit=None, grid=None, **params):
+        """uavqp_corridor_pipeline_device: BASELINE config 5 as one C-ABI call on device buffers (times is stretched in place).
+        params: fields of uavqp_pipeline_params that differ from uavqp_default_pipeline_params.  Returns the uavqp_pipeline_result
+        fields as a dict (repair_rows is 0: the box repair places no rows).  Synchronous."""
+        def p(x):
+            return x if isinstance(x, int) or x is None else _ptr(x)
+        pp = self._pipeline_params(params)
         res = _lib.PipelineResult()
         rc = _lib.lib().uavqp_corridor_pipeline_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), p(seg_offsets),
                                                        p(waypoints), p(times), p(bc), p(obstacles), int(n_obs), grid, ctypes.byref(pp),
                                                        p(coeff_out), p(status_out), p(corr_lo), p(corr_hi), p(first_hit), ctypes.byref(res))
         _lib.check(rc, "uavqp_corridor_pipeline_device")
-        return {k: getattr(res, k) for k, _ in _lib.PipelineResult._fields_ if k != "reserved_"}
+        return {k: getattr(res, k) for k, _ in _lib.PipelineResult._fields_}
+
+    def corridor_pipeline_rows_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc,
+                                      obstacles, n_obs, coeff_out, status_out, corr_lo, corr_hi, row_tau, row_deriv, row_lo, row_hi,
+                                      first_hit=None, grid=None, **params):
+        """uavqp_corridor_pipeline_rows_device: corridor_pipeline_device with the rows repair (between-knot hits become position rows,
+        knot boxes stay).  row_tau / row_deriv [total_segments, 2], row_lo / row_hi [total_segments, 2, 3] device buffers: set to unused
+        by the call, on return the rows of the final solve.  Returns the uavqp_pipeline_result fields as a dict.  Synchronous."""
+        def p(x):
+            return x if isinstance(x, int) or x is None else _ptr(x)
+        pp = self._pipeline_params(params)
+        res = _lib.PipelineResult()
+        rc = _lib.lib().uavqp_corridor_pipeline_rows_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), p(seg_offsets),
+                                                            p(waypoints), p(times), p(bc), p(obstacles), int(n_obs), grid, ctypes.byref(pp),
+                                                            p(coeff_out), p(status_out), p(corr_lo), p(corr_hi), p(first_hit), p(row_tau),
+                                                            p(row_deriv), p(row_lo), p(row_hi), ctypes.byref(res))
+        _lib.check(rc, "uavqp_corridor_pipeline_rows_device")
+        return {k: getattr(res, k) for k, _ in _lib.PipelineResult._fields_}
+
+    def repair_rows_from_hits_device(self, r, n_traj, uniform_segments, seg_offsets, waypoints, times, coeff, n_samples, t0, dt, flags,
+                                     obstacles, n_obs, robot_r, robot_h, h_max, row_tau, row_deriv, row_lo, row_hi, new_rows):
+        """uavqp_repair_rows_from_hits_device: position rows around pushed-out anchors for the colliding runs of a check's per-sample
+        flags ([n_traj, n_samples] uint8).  Row arrays IN / OUT in the rows_per_segment = 2 layout; new_rows [n_traj] int32 OUT.
+        Device buffers, asynchronous."""
+        def p(x):
+            return x if isinstance(x, int) or x is None else _ptr(x)
+        rc = _lib.lib().uavqp_repair_rows_from_hits_device(self._h, r, n_traj, uniform_segments, p(seg_offsets), p(waypoints), p(times),
+                                                           p(coeff), int(n_samples), float(t0), float(dt), p(flags), p(obstacles), int(n_obs),
+                                                           float(robot_r), float(robot_h), float(h_max), p(row_tau), p(row_deriv), p(row_lo),
+                                                           p(row_hi), p(new_rows))
+        _lib.check(rc, "uavqp_repair_rows_from_hits_device")
 
     # ---- multi-GPU: the ctx owns an RCCL communicator (include/uavqp.h, "Multi-GPU") ----
     @staticmethod
