@@ -302,6 +302,68 @@ int uavqp_time_reallocate_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_
                                  double* d_times, const double* d_coeff, double v_max, double a_max,
                                  int samples_per_seg, double max_stretch, int32_t* d_changed_out);
 
+/* Control cost of solved trajectories and its EXACT gradient with respect to the segment durations (no reference counterpart as a
+ * function: OSQP reports obj_val = 1/2 x' P x per axis, the reference never reads it).  Per trajectory, from the coefficients a solve wrote:
+ *   cost[b] = J_b = sum over axes and segments of integral_0^{T_i} (p_i^(r)(t))^2 dt = c' P c with the reference's P (getHessian,
+ *             minimum_control.cpp:5-19; TWICE OSQP's objective value), by the closed-form blocks of P, not by quadrature;
+ *   grad[seg_offsets[b] + i] = dJ_b / dT_i at the minimiser of the EQUALITY-constrained QP (uavqp_solve_batch_*):  dJ/dT_i = -H_i,
+ *             H_i = (p^(r))^2 + 2 sum_{m=1}^{r-1} (-1)^m p^(r+m) p^(r-m), summed over the three axes, evaluated at the segment's local
+ *             time 0 where p^(k)(0) = k! c_k (H is constant along a segment).  r = 3: H = j^2 - 2 s a + 2 c v with v, a, j, s, c =
+ *             c1, 2 c2, 6 c3, 24 c4, 120 c5.  (Envelope theorem in the knot-derivative variables: the constraints do not depend on T there
+ *             and each segment is the unique degree-(2r-1) interpolant of its two knot states.)
+ * The gradient is that of the OPTIMAL cost: meaningful for coefficients of uavqp_solve_batch_* at d_times (it also holds for knot boxes;
+ * it does NOT hold for rows at a fraction of T_i -- corridor and general-rows solves are out of scope here).  d_cost [n_traj] / d_grad
+ * [sum_b M_b]: either may be NULL.  The order of the additions is fixed: the same bits run to run.  Asynchronous on the ctx stream, no
+ * allocation. */
+int uavqp_cost_time_gradient_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
+                                    const double* d_times, const double* d_coeff, double* d_cost, double* d_grad);
+
+/* Optimisation of the DISTRIBUTION of time over the segments (north-star extension; the reference uses a constant 1.0 s per segment,
+ * test_minimum_jerk.cpp:65-71, and has no such loop -- nothing to mirror, parity is per inner solve).  Per trajectory
+ *       minimise  f(T) = J(T) + time_weight * sum_i T_i     subject to  t_min <= T_i <= t_max,
+ * J(T) the cost above at the minimiser of the equality-constrained QP for durations T.  Method: projected gradient descent in
+ * u_i = log T_i (direction d_i = T_i (dJ/dT_i + time_weight), zero where a bound blocks it; T stays positive and the problem is far better
+ * conditioned than in T: J scales like T^-(2r-1)) with Armijo backtracking: a trial T_i exp(-alpha d_i), clamped into the bounds, is
+ * accepted iff its solve ends UAVQP_SOLVED and f_trial <= f - armijo_c * sum_i d_i (u_i - u_trial_i); accepted: alpha *= grow, rejected:
+ * alpha *= shrink.  The first alpha makes the largest |alpha d_i| equal to initial_step.  f never increases.
+ * Host-side C++ sequencing of   clamp, solve, step, max_iters x { uavqp_solve_batch_device at the trial durations, step }, solve:
+ * the accept / reject decision is taken per trajectory ON THE DEVICE, nothing is read back inside the loop, the number of launches depends
+ * on max_iters alone.  Asynchronous on the ctx stream (a first call of a given size allocates the workspace).
+ *   d_times          [total_segments] IN: the start, OUT: the accepted durations.  A trajectory whose durations are all positive and finite
+ *                    has them projected into [t_min, t_max] first (that point is "the start"); a trajectory that is not UAVQP_SOLVED at the
+ *                    start (e.g. a non-positive duration: UAVQP_INVALID_INPUT) keeps its status and its durations and takes no part.
+ *   d_coeff_out      the solve AT the durations handed back: bit for bit what uavqp_solve_batch_device writes for them
+ *   d_status_out     [n_traj] status of that solve (may be NULL)
+ *   d_objective_out  [n_traj][2]: f at the start, f at the result (NaN, NaN for a trajectory that took no part)
+ *   d_accepted_out   [n_traj] int32 accepted trials (may be NULL)
+ *   params           uavqp_default_time_opt_params fills the defaults; UAVQP_ERR_INVALID_ARG for a wrong struct_size, max_iters < 0,
+ *                    time_weight <= 0, t_min <= 0, t_min > t_max, initial_step <= 0, armijo_c outside (0, 1), shrink outside (0, 1), grow < 1
+ *                    or a non-finite value.  max_iters = 0: the plain solve, both objective columns equal.
+ * Out of scope: corridor and general-rows solves (see above), velocity / acceleration limits inside the optimiser (run
+ * uavqp_time_reallocate_device afterwards: it stretches the whole trajectory by one factor and keeps the distribution), multi-GPU (shard
+ * the batch as for the solve: trajectories are independent). */
+typedef struct uavqp_time_opt_params {
+    int32_t struct_size;
+    int32_t max_iters;      /* trials per trajectory (default 24) */
+    double time_weight;     /* w > 0 (default 50) */
+    double t_min;           /* bounds on every duration (default 0.01 ... 100 s) */
+    double t_max;
+    double initial_step;    /* largest change of log T_i in the first trial (default 0.1) */
+    double armijo_c;        /* sufficient-decrease constant (default 1e-4) */
+    double shrink;          /* step factor after a rejected trial (default 0.5) */
+    double grow;            /* ... after an accepted one (default 2) */
+} uavqp_time_opt_params;
+void uavqp_default_time_opt_params(uavqp_time_opt_params* out);
+int uavqp_time_optimize_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                               const int32_t* d_seg_offsets, const double* d_waypoints, double* d_times, const double* d_bc,
+                               const uavqp_time_opt_params* params, double* d_coeff_out, int32_t* d_status_out,
+                               double* d_objective_out, int32_t* d_accepted_out);
+/* The same from HOST pointers (H2D copy, run, D2H copy, synchronous; times is updated in place; the coefficients of a trajectory that is
+ * not UAVQP_SOLVED come back as they do from uavqp_solve_batch_host). */
+int uavqp_time_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                             const double* waypoints, double* times, const double* bc, const uavqp_time_opt_params* params,
+                             double* coeff_out, int32_t* status_out, double* objective_out, int32_t* accepted_out);
+
 /* Batched evaluation of solved trajectories on a uniform time grid.
  * Replaces, for a whole batch, PolyTraj::evaluatePos / evaluateVel / evaluateAcc
  * (src/planner/traj_utils/include/traj_utils/poly_traj.hpp:74-168) as driven by poly_traj_server's

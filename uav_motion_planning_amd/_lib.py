@@ -46,6 +46,10 @@ SYMBOLS = (
     "uavqp_solve_rows_batch_device",
     "uavqp_solve_rows_batch_host",
     "uavqp_time_reallocate_device",
+    "uavqp_cost_time_gradient_device",
+    "uavqp_default_time_opt_params",
+    "uavqp_time_optimize_device",
+    "uavqp_time_optimize_host",
     "uavqp_eval_batch_device",
     "uavqp_traj_length_device",
     "uavqp_ellipsoid_check_device",
@@ -105,6 +109,13 @@ class PipelineResult(ctypes.Structure):
                 ("colliding_after", ctypes.c_int32), ("unsolved", ctypes.c_int32), ("repair_rows", ctypes.c_int32), ("check_dt", ctypes.c_double)]
 
 
+class TimeOptParams(ctypes.Structure):
+    """uavqp_time_opt_params of include/uavqp.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("max_iters", ctypes.c_int32), ("time_weight", ctypes.c_double), ("t_min", ctypes.c_double),
+                ("t_max", ctypes.c_double), ("initial_step", ctypes.c_double), ("armijo_c", ctypes.c_double), ("shrink", ctypes.c_double),
+                ("grow", ctypes.c_double)]
+
+
 def build(force=False):
     """Compile csrc/*.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
     csrc = os.path.join(_PKG, "csrc")
@@ -156,6 +167,11 @@ def lib():
     L.uavqp_solve_rows_batch_device.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, dp, dp, i32, dp, ip, dp, dp, dp, ip, ip, vp]
     L.uavqp_solve_rows_batch_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, dp, dp, i32, dp, ip, dp, dp, dp, ip, ip]
     L.uavqp_time_reallocate_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ctypes.c_double, ctypes.c_double, i32, ctypes.c_double, ip]
+    L.uavqp_cost_time_gradient_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, dp, dp]
+    L.uavqp_default_time_opt_params.argtypes = [ctypes.POINTER(TimeOptParams)]
+    L.uavqp_default_time_opt_params.restype = None
+    L.uavqp_time_optimize_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, ctypes.POINTER(TimeOptParams), dp, ip, dp, ip]
+    L.uavqp_time_optimize_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, ctypes.POINTER(TimeOptParams), dp, ip, dp, ip]
     L.uavqp_eval_batch_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, i32, dp]
     L.uavqp_traj_length_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ctypes.c_double, dp, dp, ip]
     L.uavqp_ellipsoid_check_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, dp, i32,

@@ -120,6 +120,60 @@ class TrajOptimizer {
     int segOffset(int traj) const { return seg_offsets_[traj]; }
     const std::vector<int32_t>& status() const { return status_; }
 
+    // Optimisation of the time allocation (include/uavqp.h uavqp_time_optimize_host; the reference's equality rows only: false when a
+    // corridor or rows are set): minimises, per trajectory, cost + time_weight * sum T over the durations.  On return timeAllocation() = the
+    // optimised durations, getPolyCoeff() = the solve at them, objective() = [n_traj][2] f at the start / at the result, acceptedTrials() per
+    // trajectory.  params: null = uavqp_default_time_opt_params; time_weight > 0 overrides its weight.
+    bool optimizeTime(double time_weight = 0.0, const uavqp_time_opt_params* params = nullptr) {
+        if (n_traj_ <= 0 || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_])) return false;
+        if (!lo_.empty() || rows_k_ > 0) {
+            std::cout << "solver solve failed! (optimizeTime: corridor and general-rows problems are out of scope)" << std::endl;
+            return false;
+        }
+        if (!ensureContext()) return false;
+        if (bc_.empty()) bc_.assign(static_cast<size_t>(n_traj_) * 2 * (order_ - 1) * 3, 0.0);
+        uavqp_time_opt_params pp;
+        if (params) pp = *params; else uavqp_default_time_opt_params(&pp);
+        if (time_weight > 0.0) pp.time_weight = time_weight;
+        coef_.assign(static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_], 0.0);
+        status_.assign(n_traj_, 0);
+        objective_.assign(static_cast<size_t>(2) * n_traj_, 0.0);
+        accepted_.assign(n_traj_, 0);
+        const int rc = uavqp_time_optimize_host(ctx_, order_, n_traj_, 0, 0, seg_offsets_.data(), wp_.data(), T_.data(), bc_.data(), &pp,
+                                                coef_.data(), status_.data(), objective_.data(), accepted_.data());
+        if (rc != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            return false;
+        }
+        for (int32_t s : status_) if (s != UAVQP_SOLVED) return false;
+        return true;
+    }
+    const std::vector<double>& objective() const { return objective_; }
+    const std::vector<int32_t>& acceptedTrials() const { return accepted_; }
+    // Control cost c' P c (integral of the squared r-th derivative, three axes) per trajectory of the current waypoints at the current
+    // durations: one solve with no iteration and a time weight too small to register in float64 -- the objective then IS the cost.
+    // Equality rows only, like optimizeTime; leaves coefficients and durations as they are.  Empty on failure.
+    std::vector<double> getCost() {
+        std::vector<double> cost;
+        if (n_traj_ <= 0 || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_]) || !lo_.empty() || rows_k_ > 0 || !ensureContext()) return cost;
+        if (bc_.empty()) bc_.assign(static_cast<size_t>(n_traj_) * 2 * (order_ - 1) * 3, 0.0);
+        uavqp_time_opt_params pp;
+        uavqp_default_time_opt_params(&pp);
+        pp.max_iters = 0;
+        pp.time_weight = 1e-300;
+        pp.t_min = 1e-300;
+        pp.t_max = 1e300;
+        std::vector<double> T(T_), coef(static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_], 0.0), obj(static_cast<size_t>(2) * n_traj_, 0.0);
+        if (uavqp_time_optimize_host(ctx_, order_, n_traj_, 0, 0, seg_offsets_.data(), wp_.data(), T.data(), bc_.data(), &pp, coef.data(), nullptr,
+                                     obj.data(), nullptr) != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            return cost;
+        }
+        cost.resize(n_traj_);
+        for (int b = 0; b < n_traj_; ++b) cost[b] = obj[static_cast<size_t>(2) * b + 1];
+        return cost;
+    }
+
     // BASELINE config 5 as one call (include/uavqp.h uavqp_corridor_pipeline_host): plain solve -> corridor boxes from the obstacle cloud
     // (SE(3) robot ellipsoid of KinoAstar::isCollisionFree) -> <= max_rounds x (corridor solve + time re-allocation) -> collision check
     // -> repair.  obstacles [n_obs][3].  On return: getPolyCoeff() = the final polynomials, timeAllocation() = the stretched durations,
@@ -297,6 +351,8 @@ class TrajOptimizer {
     std::vector<double> wp_, T_, bc_, coef_, lo_, hi_, pipe_lo_, pipe_hi_, row_tau_, row_lo_, row_hi_;
     std::vector<int32_t> row_deriv_, first_hit_, repair_deriv_;
     std::vector<double> repair_tau_, repair_lo_, repair_hi_;
+    std::vector<double> objective_;
+    std::vector<int32_t> accepted_;
     int rows_k_ = 0;
     uavqp_pipeline_result pipe_result_{};
 };

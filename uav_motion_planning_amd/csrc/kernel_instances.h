@@ -81,3 +81,11 @@
     UAVQP_INST __global__ void uavqp::cloud_corridor_kernel<R_>(uavqp::CloudCorridorArgs);   \
     UAVQP_INST __global__ void uavqp::ellipsoid_grid_kernel<R_>(uavqp::EllipsoidGridArgs);
 #define UAVQP_INSTANCES_CLOUD UAVQP_CLOUD_R(3) UAVQP_CLOUD_R(4)
+
+// ---- qp_time_opt.h: cost + time gradient of solved trajectories, the steps of the duration optimiser
+#define UAVQP_TIMEOPT_R(R_)                                                               \
+    UAVQP_INST __global__ void uavqp::cost_grad_kernel<R_>(uavqp::CostGradArgs);             \
+    UAVQP_INST __global__ void uavqp::time_opt_clamp_kernel<R_>(uavqp::TimeOptArgs);         \
+    UAVQP_INST __global__ void uavqp::time_opt_step_kernel<R_, true>(uavqp::TimeOptArgs);    \
+    UAVQP_INST __global__ void uavqp::time_opt_step_kernel<R_, false>(uavqp::TimeOptArgs);
+#define UAVQP_INSTANCES_TIMEOPT UAVQP_TIMEOPT_R(3) UAVQP_TIMEOPT_R(4)

@@ -30,6 +30,7 @@
 #include "qp_rows2.h"
 #include "qp_rows_dual.h"
 #include "obstacle_grid.h"
+#include "qp_time_opt.h"
 // Measured-slower alternatives kept as bit-identical cross-checks: `make experiments` (-DUAVQP_EXPERIMENTS) only
 #ifdef UAVQP_EXPERIMENTS
 #include "cloud_grid2d.h"
@@ -51,6 +52,7 @@ UAVQP_INSTANCES_ROWS41
 UAVQP_INSTANCES_ROWS42
 UAVQP_INSTANCES_ROWS_DUAL
 UAVQP_INSTANCES_CLOUD
+UAVQP_INSTANCES_TIMEOPT
 #endif
 
 namespace uavqp {
@@ -171,6 +173,9 @@ struct uavqp_ctx {
     void* d_pipe = nullptr;
     size_t pipe_bytes = 0;
     void* h_pipe = nullptr;
+    // duration optimiser (uavqp_time_opt.h): trial durations, stored gradient and the per-trajectory state of the descent
+    void* d_topt = nullptr;
+    size_t topt_bytes = 0;
     unsigned int pipe_seq = 0;   // sequence number of the last pipeline round enqueued (uavqp_pipeline.h: tags the count a round reports to the host)
 };
 
@@ -326,6 +331,7 @@ extern "C" int uavqp_destroy(uavqp_ctx* ctx) {
     if (ctx->d_stage) (void)hipFree(ctx->d_stage);
     if (ctx->d_pipe) (void)hipFree(ctx->d_pipe);
     if (ctx->h_pipe) (void)hipHostFree(ctx->h_pipe);
+    if (ctx->d_topt) (void)hipFree(ctx->d_topt);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return UAVQP_OK;
@@ -1866,6 +1872,11 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
 // BASELINE config 5 as one call
 // ===================================================================================================
 #include "uavqp_pipeline.h"
+
+// ===================================================================================================
+// Cost, exact time gradient and the duration optimiser
+// ===================================================================================================
+#include "uavqp_time_opt.h"
 
 // ===================================================================================================
 // N3: quadrotor_msgs/PolynomialTrajectory packer (host only)

@@ -102,6 +102,65 @@ class Context:
                                                      float(v_max), float(a_max), int(samples_per_seg), float(max_stretch), p(changed))
         _lib.check(rc, "uavqp_time_reallocate_device")
 
+    def cost_time_gradient_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, cost=None, grad=None):
+        """uavqp_cost_time_gradient_device: cost [n_traj] = c' P c (integral of the squared r-th derivative, 3 axes) and grad [sum M] =
+        d cost / d T_i at the minimiser of the equality-constrained solve (device buffers; either output may be None).  Asynchronous."""
+        def p(x):
+            return x if isinstance(x, int) or x is None else _ptr(x)
+        rc = _lib.lib().uavqp_cost_time_gradient_device(self._h, r, n_traj, uniform_segments, p(seg_offsets), p(times), p(coeff), p(cost), p(grad))
+        _lib.check(rc, "uavqp_cost_time_gradient_device")
+
+    @staticmethod
+    def _time_opt_params(params):
+        pp = _lib.TimeOptParams()
+        _lib.lib().uavqp_default_time_opt_params(ctypes.byref(pp))
+        for k, v in params.items():
+            if not hasattr(pp, k) or k == "struct_size":
+                raise ValueError(f"unknown uavqp_time_opt_params field {k!r}")
+            setattr(pp, k, v)
+        return pp
+
+    def time_optimize_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc,
+                             coeff_out, status_out, objective_out, accepted_out=None, **params):
+        """uavqp_time_optimize_device on device buffers: `times` holds the start and receives the optimised durations, coeff_out the
+        solve at them, objective_out [n_traj][2] f = cost + time_weight * sum T at the start and at the result.
+        params: fields of uavqp_time_opt_params that differ from uavqp_default_time_opt_params.  Asynchronous."""
+        def p(x):
+            return x if isinstance(x, int) or x is None else _ptr(x)
+        pp = self._time_opt_params(params)
+        rc = _lib.lib().uavqp_time_optimize_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), p(seg_offsets),
+                                                   p(waypoints), p(times), p(bc), ctypes.byref(pp), p(coeff_out), p(status_out),
+                                                   p(objective_out), p(accepted_out))
+        _lib.check(rc, "uavqp_time_optimize_device")
+
+    def time_optimize_host(self, r, seg_offsets, waypoints, times, bc, uniform_segments=0, **params):
+        """numpy in / numpy out (synchronous).  Returns (times, coeff_flat, status, objective [n_traj][2], accepted)."""
+        waypoints = np.ascontiguousarray(waypoints, dtype=np.float64)
+        times = np.array(times, dtype=np.float64).ravel()   # a copy: the call updates it in place
+        bc = np.ascontiguousarray(bc, dtype=np.float64)
+        if uniform_segments > 0:
+            n_traj = times.size // uniform_segments
+            so = None
+            total = n_traj * uniform_segments
+            mmax = uniform_segments
+        else:
+            so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+            n_traj = so.size - 1
+            total = int(so[-1]) if n_traj > 0 else 0
+            mmax = int(np.max(np.diff(so))) if n_traj > 0 else 1
+        assert times.size == total
+        assert waypoints.size == 3 * (total + n_traj), "waypoints must hold sum(M_b + 1) xyz rows"
+        assert bc.size == n_traj * 2 * (r - 1) * 3
+        pp = self._time_opt_params(params)
+        coeff = np.zeros(3 * 2 * r * total, dtype=np.float64)
+        status = np.zeros(n_traj, dtype=np.int32)
+        objective = np.zeros((n_traj, 2), dtype=np.float64)
+        accepted = np.zeros(n_traj, dtype=np.int32)
+        rc = _lib.lib().uavqp_time_optimize_host(self._h, r, n_traj, uniform_segments, max(mmax, 1), _ptr(so), _ptr(waypoints), _ptr(times),
+                                                 _ptr(bc), ctypes.byref(pp), _ptr(coeff), _ptr(status), _ptr(objective), _ptr(accepted))
+        _lib.check(rc, "uavqp_time_optimize_host")
+        return times, coeff, status, objective, accepted
+
     def ellipsoid_check_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, n_samples, t0, dt,
                                obstacles, n_obs, robot_r, robot_h, first_hit, flags=None):
         """Batched KinoAstar::isCollisionFree over the samples of solved trajectories (device buffers)."""
@@ -436,6 +495,10 @@ class TrajOptimizer:
                                      tau / deriv [sum M_b][K], lo / hi [sum M_b][K][3]; K = 0 removes them) -- the same method as the
                                      C++ facade's (cpp/traj_optimizer.h)
     solve() -> bool                  True iff every trajectory solved (statuses in .status)
+    optimizeTime(time_weight, ...)   equality-constrained problems only: minimises cost + time_weight * sum T over the durations
+                                     (uavqp_time_optimize_host), stores the optimised allocation (getTimeAllocation) and the
+                                     coefficients at it; objective [n_traj][2] (start, result) in .objective
+    getCost()                        [n_traj] control cost c' P c of the stored coefficients at the stored durations
     getPolyCoeff()                   flat float64 array, trajectory b at 3*2r*seg_offsets[b], [axis][seg][2r]
     """
 
@@ -450,6 +513,7 @@ class TrajOptimizer:
         self._coef = np.zeros(0)
         self.status = np.zeros(0, dtype=np.int32)
         self.iterations = np.zeros(0, dtype=np.int32)
+        self.objective = np.zeros((0, 2))
 
     def setWaypoints(self, xyz, wp_offsets=None, n_waypoints=None):
         self._wp = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
@@ -508,6 +572,45 @@ class TrajOptimizer:
         else:
             self._coef, self.status = self._ctx.solve_batch_host(self._r, self._so, self._wp, self._T, bc)
         return bool(np.all(self.status == _lib.UAVQP_SOLVED))
+
+    def optimizeTime(self, time_weight=None, **params):
+        """Optimises the stored time allocation (the reference's equality rows only: a corridor or rows set raises ValueError).
+        True iff every trajectory is solved at the optimised durations; getPolyCoeff() is the solve at getTimeAllocation()."""
+        if self._lo is not None or self._rows is not None:
+            raise ValueError("optimizeTime: corridor and general-rows problems are out of scope (include/uavqp.h)")
+        if self._wp is None or self._T is None:
+            return False
+        n_traj = self._so.size - 1
+        if self._T.size != int(self._so[-1]):
+            return False
+        bc = self._bc if self._bc is not None else np.zeros((n_traj, 2, self._r - 1, 3))
+        if self._ctx is None:
+            self._ctx = Context(self._device)
+            self._ctx.set_settings(warm_start=1, eps_prim_inf=1e-3, max_iter=1000)
+        if time_weight is not None:
+            params["time_weight"] = float(time_weight)
+        self._T, self._coef, self.status, self.objective, self.iterations = self._ctx.time_optimize_host(
+            self._r, self._so, self._wp, self._T, bc, **params)
+        return bool(np.all(self.status == _lib.UAVQP_SOLVED))
+
+    def getTimeAllocation(self):
+        return self._T.copy()
+
+    def getCost(self):
+        """[n_traj] c' P c of the stored coefficients (after solve() or optimizeTime()); computed on the device."""
+        import torch
+        n_traj = self._so.size - 1
+        if self._ctx is None or self._coef.size != 3 * 2 * self._r * int(self._so[-1]):
+            raise _lib.UavqpError("getCost: no solved coefficients (call solve() or optimizeTime() first)")
+        dev = torch.device("cuda", self._device)
+        so = torch.from_numpy(self._so).to(dev)
+        tt = torch.from_numpy(self._T).to(dev)
+        cf = torch.from_numpy(self._coef).to(dev)
+        cost = torch.zeros(n_traj, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        self._ctx.cost_time_gradient_device(self._r, n_traj, 0, so, tt, cf, cost=cost)
+        self._ctx.synchronize()
+        return cost.cpu().numpy()
 
     def getPolyCoeff(self, traj=None):
         if traj is None:
