@@ -188,7 +188,10 @@ int uavqp_solve_batch_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segm
 /* Same with HOST pointers: H2D copy, solve, D2H copy, synchronous.  total_segments = sum_b M_b.
  * The coefficients of a trajectory flagged UAVQP_INVALID_INPUT come back as zeros (the device entry leaves them
  * untouched; the host entries clear their staging buffer first -- both host entries behave the same); a
- * UAVQP_NON_FINITE trajectory carries the non-finite values it overflowed to. */
+ * UAVQP_NON_FINITE trajectory carries the non-finite values it overflowed to.
+ * Argument checks shared by every *_host entry (one staging routine, csrc/uavqp_stage.h): ragged offsets start at 0 and never decrease;
+ * a trajectory longer than a positive max_segments is flagged UAVQP_INVALID_INPUT, not refused; a batch whose waypoint rows
+ * (total_segments + n_traj) do not fit an int is UAVQP_ERR_INVALID_ARG; optional outputs may be NULL; n_traj == 0 is a no-op. */
 int uavqp_solve_batch_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments,
                            const int32_t* seg_offsets, const double* waypoints, const double* times,
                            const double* bc, double* coeff_out, int32_t* status_out);

@@ -39,7 +39,7 @@ namespace uavqp {
 // Round 6: the LDS of the VERIFYING pass is its own knob.  Measured on config 3 + K = 2 (docs/measurement_log.md R6.1): 80 / 53 / 40 / 32 / 26 KiB per wave
 // = 2 / 3 / 4 / 5 / 6 waves per CU: 426 / 405 / 364 / 373 / 397 us -- the kernel is bound by the dependent issue of a single wave per SIMD, and at 40 KiB
 // every SIMD has one; but the sweep records that no longer fit go through the HBM workspace: + 0.9 GB of counter traffic (2.05 -> 2.98 GB per step) for
-// - 0.08 ms (2.17 -> 2.09 ms).  Default: everything on chip (80); -DUAVQP_ROWS2_VER_LDS_KB=40 buys the time with the bytes.
+// - 0.08 ms (2.17 -> 2.09 ms).  Default: 40 KiB plus the register knots below (which keep those records on chip); 80 is the A/B setting.
 #ifndef UAVQP_ROWS2_VER_LDS_KB
 #define UAVQP_ROWS2_VER_LDS_KB 40
 #endif

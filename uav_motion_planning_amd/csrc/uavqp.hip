@@ -545,6 +545,8 @@ static int ensure_mapped(uavqp_ctx* ctx, size_t need) {
     return UAVQP_OK;
 }
 
+#include "uavqp_stage.h"
+
 extern "C" int uavqp_solve_batch_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments,
                                       const int32_t* seg_offsets, const double* waypoints, const double* times,
                                       const double* bc, double* coeff_out, int32_t* status_out) {
@@ -552,84 +554,28 @@ extern "C" int uavqp_solve_batch_host(uavqp_ctx* ctx, int r, int n_traj, int uni
     if (n_traj == 0) return UAVQP_OK;
     if (!waypoints || !times || !bc || !coeff_out) return UAVQP_ERR_INVALID_ARG;
     if (uniform_segments == 0 && !seg_offsets) return UAVQP_ERR_INVALID_ARG;
-    long long total_seg = 0;
-    int Mmax = uniform_segments;
-    if (uniform_segments > 0) {
-        total_seg = (long long)uniform_segments * n_traj;
-    } else {
-        if (seg_offsets[0] != 0) return UAVQP_ERR_INVALID_ARG;
-        for (int b = 0; b < n_traj; ++b) {
-            const int M = seg_offsets[b + 1] - seg_offsets[b];
-            if (M < 0) return UAVQP_ERR_INVALID_ARG;
-            if (M > Mmax) Mmax = M;
-        }
-        total_seg = seg_offsets[n_traj];
-        if (max_segments > 0 && max_segments < Mmax) Mmax = max_segments;  // larger ones are flagged invalid
-        if (Mmax < 1) Mmax = 1;
-    }
+    BatchShape sh;
+    int rc = batch_shape(n_traj, uniform_segments, max_segments, seg_offsets, &sh);
+    if (rc != UAVQP_OK) return rc;
     UAVQP_HIP(hipSetDevice(ctx->device));
-    const size_t b_off = uniform_segments > 0 ? 0 : align256(sizeof(int32_t) * (size_t)(n_traj + 1));
-    const size_t b_wp = align256(sizeof(double) * 3 * (size_t)(total_seg + n_traj));
-    const size_t b_t = align256(sizeof(double) * (size_t)total_seg);
-    const size_t b_bc = align256(sizeof(double) * (size_t)n_traj * 2 * (r - 1) * 3);
-    const size_t b_out = align256(sizeof(double) * 3 * 2 * r * (size_t)total_seg);
-    const size_t b_st = align256(sizeof(int32_t) * (size_t)n_traj);
+    const size_t n = (size_t)n_traj, tot = (size_t)sh.total_seg;
+    Stage st;
+    const int i_off = uniform_segments > 0 ? -1 : st.in(seg_offsets, sizeof(int32_t) * (n + 1));
+    const int i_wp = st.in(waypoints, sizeof(double) * 3 * (tot + n));
+    const int i_t = st.in(times, sizeof(double) * tot);
+    const int i_bc = st.in(bc, sizeof(double) * n * 2 * (r - 1) * 3);
+    const int i_out = st.out(coeff_out, sizeof(double) * 3 * 2 * r * tot, true);
+    const int i_st = st.out(status_out, sizeof(int32_t) * n);
     // Small batches (a planner's single trajectory, a handful of candidates) are a latency path: the whole batch lives in the
     // pinned page that is mapped into the device, the kernels read and write it over the host link, and the call is the
-    // launch(es) plus one stream synchronisation instead of 3-4 H2D copies, a memset and 2 D2H copies (measured, one 7-segment
-    // trajectory: 72 -> 3x us per call).
-    const size_t b_all = b_off + b_wp + b_t + b_bc + b_out + b_st;
-    if (b_all <= 256 * 1024) {
-        int rcm = ensure_mapped(ctx, b_all + MAPPED_HEAD);
-        if (rcm != UAVQP_OK) return rcm;
-        char* hb = (char*)ctx->h_axis + MAPPED_HEAD;   // (the page's first 256 bytes hold the completion word: a FIXED slot no payload ever aliases)
-        char* db = (char*)ctx->d_axis + MAPPED_HEAD;
-        if (uniform_segments == 0) std::memcpy(hb, seg_offsets, sizeof(int32_t) * (size_t)(n_traj + 1));
-        std::memcpy(hb + b_off, waypoints, sizeof(double) * 3 * (size_t)(total_seg + n_traj));
-        std::memcpy(hb + b_off + b_wp, times, sizeof(double) * (size_t)total_seg);
-        std::memcpy(hb + b_off + b_wp + b_t, bc, sizeof(double) * (size_t)n_traj * 2 * (r - 1) * 3);
-        std::memset(hb + b_off + b_wp + b_t + b_bc, 0, sizeof(double) * 3 * 2 * r * (size_t)total_seg);   // failed trajectories come back as zeros
-        std::memset(hb + b_off + b_wp + b_t + b_bc + b_out, 0, sizeof(int32_t) * (size_t)n_traj);
-        rcm = uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, Mmax, uniform_segments > 0 ? nullptr : (const int32_t*)db,
-                                       (const double*)(db + b_off), (const double*)(db + b_off + b_wp), (const double*)(db + b_off + b_wp + b_t),
-                                       (double*)(db + b_off + b_wp + b_t + b_bc), (int32_t*)(db + b_off + b_wp + b_t + b_bc + b_out));
-        if (rcm != UAVQP_OK) return rcm;
-        {   // (no stream synchronisation: see uavqp_solve_axis_host)
-            const unsigned int seq = ++ctx->pipe_seq;
-            volatile unsigned long long* h_word = (volatile unsigned long long*)ctx->h_axis;
-            *h_word = 0ull;
-            std::atomic_thread_fence(std::memory_order_release);
-            hipLaunchKernelGGL(uavqp::host_word_kernel, dim3(1), dim3(1), 0, ctx->stream, (const int32_t*)nullptr, (volatile unsigned long long*)ctx->d_axis, seq);
-            rcm = await_host_word(ctx->stream, h_word, seq, nullptr, "uavqp_solve_batch_host");
-            if (rcm != UAVQP_OK) return rcm;
-        }
-        std::memcpy(coeff_out, hb + b_off + b_wp + b_t + b_bc, sizeof(double) * 3 * 2 * r * (size_t)total_seg);
-        if (status_out) std::memcpy(status_out, hb + b_off + b_wp + b_t + b_bc + b_out, sizeof(int32_t) * (size_t)n_traj);
-        return UAVQP_OK;
-    }
-    int rc = ensure_stage(ctx, b_all);
+    // launch(es) plus one polled word instead of 3-4 H2D copies, a memset, 2 D2H copies and a stream synchronisation (measured, one
+    // 7-segment trajectory: 72 -> 3x us per call).
+    rc = stage_begin(ctx, st, st.total <= 256 * 1024);
     if (rc != UAVQP_OK) return rc;
-    char* base = (char*)ctx->d_stage;
-    int32_t* d_off = uniform_segments > 0 ? nullptr : (int32_t*)base;
-    double* d_wp = (double*)(base + b_off);
-    double* d_t = (double*)(base + b_off + b_wp);
-    double* d_bc = (double*)(base + b_off + b_wp + b_t);
-    double* d_out = (double*)(base + b_off + b_wp + b_t + b_bc);
-    int32_t* d_st = (int32_t*)(base + b_off + b_wp + b_t + b_bc + b_out);
-    hipStream_t s = ctx->stream;
-    if (d_off) UAVQP_HIP(hipMemcpyAsync(d_off, seg_offsets, sizeof(int32_t) * (size_t)(n_traj + 1), hipMemcpyHostToDevice, s));
-    UAVQP_HIP(hipMemcpyAsync(d_wp, waypoints, sizeof(double) * 3 * (size_t)(total_seg + n_traj), hipMemcpyHostToDevice, s));
-    if (total_seg > 0) UAVQP_HIP(hipMemcpyAsync(d_t, times, sizeof(double) * (size_t)total_seg, hipMemcpyHostToDevice, s));
-    UAVQP_HIP(hipMemcpyAsync(d_bc, bc, sizeof(double) * (size_t)n_traj * 2 * (r - 1) * 3, hipMemcpyHostToDevice, s));
-    // the kernels leave failed trajectories unwritten and the staging buffer is reused: clear it, so that a failed
-    // trajectory comes back as zeros (never as another batch's coefficients)
-    if (total_seg > 0) UAVQP_HIP(hipMemsetAsync(d_out, 0, sizeof(double) * 3 * 2 * r * (size_t)total_seg, s));
-    rc = uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, Mmax, d_off, d_wp, d_t, d_bc, d_out, d_st);
+    rc = uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, sh.Mmax, st.at<int32_t>(i_off), st.at<double>(i_wp), st.at<double>(i_t),
+                                  st.at<double>(i_bc), st.at<double>(i_out), st.at<int32_t>(i_st));
     if (rc != UAVQP_OK) return rc;
-    if (total_seg > 0) UAVQP_HIP(hipMemcpyAsync(coeff_out, d_out, sizeof(double) * 3 * 2 * r * (size_t)total_seg, hipMemcpyDeviceToHost, s));
-    if (status_out) UAVQP_HIP(hipMemcpyAsync(status_out, d_st, sizeof(int32_t) * (size_t)n_traj, hipMemcpyDeviceToHost, s));
-    UAVQP_HIP(hipStreamSynchronize(s));
-    return UAVQP_OK;
+    return stage_end(ctx, st, "uavqp_solve_batch_host");
 }
 
 extern "C" int uavqp_solve_axis_host(uavqp_ctx* ctx, int r, int n_seg, const double* pos_1d, const double* bound_vel,
@@ -675,16 +621,8 @@ extern "C" int uavqp_solve_axis_host(uavqp_ctx* ctx, int r, int n_seg, const dou
     int rc = uavqp_solve_batch_device(ctx, r, 1, n_seg, n_seg, nullptr, (const double*)(db + o_wp), (const double*)(db + o_t),
                                       (const double*)(db + o_bc), (double*)(db + o_out), (int32_t*)(db + o_st));
     if (rc != UAVQP_OK) return rc;
-    // (no stream synchronisation: a one-thread kernel behind the solve stamps a word of the page, the host polls it)
-    {
-        const unsigned int seq = ++ctx->pipe_seq;
-        volatile unsigned long long* h_word = (volatile unsigned long long*)ctx->h_axis;
-        *h_word = 0ull;
-        std::atomic_thread_fence(std::memory_order_release);
-        hipLaunchKernelGGL(uavqp::host_word_kernel, dim3(1), dim3(1), 0, ctx->stream, (const int32_t*)nullptr, (volatile unsigned long long*)ctx->d_axis, seq);
-        rc = await_host_word(ctx->stream, h_word, seq, nullptr, "uavqp_solve_axis_host");
-        if (rc != UAVQP_OK) return rc;
-    }
+    rc = await_mapped_page(ctx, "uavqp_solve_axis_host");   // (no stream synchronisation)
+    if (rc != UAVQP_OK) return rc;
     const int32_t status = *st;
     if (status == UAVQP_SOLVED) std::memcpy(coef_1d, hb + o_out, sizeof(double) * (size_t)nc * n_seg);   // x axis = the first M rows
     if (status_out) *status_out = status;
@@ -1366,55 +1304,25 @@ extern "C" int uavqp_solve_corridor_batch_host(uavqp_ctx* ctx, int r, int n_traj
     if (n_traj == 0) return UAVQP_OK;
     if (!waypoints || !times || !bc || !corr_lo || !corr_hi || !coeff_out) return UAVQP_ERR_INVALID_ARG;
     if (uniform_segments == 0 && !seg_offsets) return UAVQP_ERR_INVALID_ARG;
-    long long total_seg = 0;
-    int Mmax = uniform_segments;
-    if (uniform_segments > 0) total_seg = (long long)uniform_segments * n_traj;
-    else {
-        if (seg_offsets[0] != 0) return UAVQP_ERR_INVALID_ARG;
-        for (int b = 0; b < n_traj; ++b) {
-            const int M = seg_offsets[b + 1] - seg_offsets[b];
-            if (M < 0) return UAVQP_ERR_INVALID_ARG;
-            if (M > Mmax) Mmax = M;
-        }
-        total_seg = seg_offsets[n_traj];
-        if (max_segments > 0 && max_segments < Mmax) Mmax = max_segments;
-        if (Mmax < 1) Mmax = 1;
-    }
+    BatchShape sh;
+    int rc = batch_shape(n_traj, uniform_segments, max_segments, seg_offsets, &sh);
+    if (rc != UAVQP_OK) return rc;
     UAVQP_HIP(hipSetDevice(ctx->device));
-    const size_t n_wp = 3 * (size_t)(total_seg + n_traj);
-    const size_t b_off = uniform_segments > 0 ? 0 : align256(sizeof(int32_t) * (size_t)(n_traj + 1));
-    const size_t b_wp = align256(sizeof(double) * n_wp);
-    const size_t b_t = align256(sizeof(double) * (size_t)total_seg);
-    const size_t b_bc = align256(sizeof(double) * (size_t)n_traj * 2 * (r - 1) * 3);
-    const size_t b_out = align256(sizeof(double) * 3 * 2 * r * (size_t)total_seg);
-    const size_t b_st = align256(sizeof(int32_t) * (size_t)n_traj);
-    int rc = ensure_stage(ctx, b_off + 3 * b_wp + b_t + b_bc + b_out + 2 * b_st);
+    const size_t n = (size_t)n_traj, tot = (size_t)sh.total_seg, b_wp = sizeof(double) * 3 * (tot + n);
+    Stage st;
+    const int i_off = uniform_segments > 0 ? -1 : st.in(seg_offsets, sizeof(int32_t) * (n + 1));
+    const int i_wp = st.in(waypoints, b_wp), i_lo = st.in(corr_lo, b_wp), i_hi = st.in(corr_hi, b_wp);
+    const int i_t = st.in(times, sizeof(double) * tot);
+    const int i_bc = st.in(bc, sizeof(double) * n * 2 * (r - 1) * 3);
+    const int i_out = st.out(coeff_out, sizeof(double) * 3 * 2 * r * tot, true);
+    const int i_st = st.out(status_out, sizeof(int32_t) * n), i_it = st.out(iters_out, sizeof(int32_t) * n);
+    rc = stage_begin(ctx, st);
     if (rc != UAVQP_OK) return rc;
-    char* p = (char*)ctx->d_stage;
-    int32_t* d_off = uniform_segments > 0 ? nullptr : (int32_t*)p; p += b_off;
-    double* d_wp = (double*)p; p += b_wp;
-    double* d_lo = (double*)p; p += b_wp;
-    double* d_hi = (double*)p; p += b_wp;
-    double* d_t = (double*)p; p += b_t;
-    double* d_bc = (double*)p; p += b_bc;
-    double* d_out = (double*)p; p += b_out;
-    int32_t* d_st = (int32_t*)p; p += b_st;
-    int32_t* d_it = (int32_t*)p;
-    hipStream_t s = ctx->stream;
-    if (d_off) UAVQP_HIP(hipMemcpyAsync(d_off, seg_offsets, sizeof(int32_t) * (size_t)(n_traj + 1), hipMemcpyHostToDevice, s));
-    UAVQP_HIP(hipMemcpyAsync(d_wp, waypoints, sizeof(double) * n_wp, hipMemcpyHostToDevice, s));
-    UAVQP_HIP(hipMemcpyAsync(d_lo, corr_lo, sizeof(double) * n_wp, hipMemcpyHostToDevice, s));
-    UAVQP_HIP(hipMemcpyAsync(d_hi, corr_hi, sizeof(double) * n_wp, hipMemcpyHostToDevice, s));
-    if (total_seg > 0) UAVQP_HIP(hipMemcpyAsync(d_t, times, sizeof(double) * (size_t)total_seg, hipMemcpyHostToDevice, s));
-    UAVQP_HIP(hipMemcpyAsync(d_bc, bc, sizeof(double) * (size_t)n_traj * 2 * (r - 1) * 3, hipMemcpyHostToDevice, s));
-    UAVQP_HIP(hipMemsetAsync(d_out, 0, sizeof(double) * 3 * 2 * r * (size_t)total_seg, s));
-    rc = corridor_warm_impl(ctx, r, n_traj, uniform_segments, Mmax, d_off, d_wp, d_t, d_bc, d_lo, d_hi, d_out, d_st, d_it, nullptr, 0, total_seg);
+    rc = corridor_warm_impl(ctx, r, n_traj, uniform_segments, sh.Mmax, st.at<int32_t>(i_off), st.at<double>(i_wp), st.at<double>(i_t),
+                            st.at<double>(i_bc), st.at<double>(i_lo), st.at<double>(i_hi), st.at<double>(i_out), st.at<int32_t>(i_st),
+                            st.at<int32_t>(i_it), nullptr, 0, sh.total_seg);
     if (rc != UAVQP_OK) return rc;
-    if (total_seg > 0) UAVQP_HIP(hipMemcpyAsync(coeff_out, d_out, sizeof(double) * 3 * 2 * r * (size_t)total_seg, hipMemcpyDeviceToHost, s));
-    if (status_out) UAVQP_HIP(hipMemcpyAsync(status_out, d_st, sizeof(int32_t) * (size_t)n_traj, hipMemcpyDeviceToHost, s));
-    if (iters_out) UAVQP_HIP(hipMemcpyAsync(iters_out, d_it, sizeof(int32_t) * (size_t)n_traj, hipMemcpyDeviceToHost, s));
-    UAVQP_HIP(hipStreamSynchronize(s));
-    return UAVQP_OK;
+    return stage_end(ctx, st, "uavqp_solve_corridor_batch_host");
 }
 
 extern "C" int uavqp_solve_rows_batch_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments,
@@ -1428,70 +1336,30 @@ extern "C" int uavqp_solve_rows_batch_host(uavqp_ctx* ctx, int r, int n_traj, in
     if (!waypoints || !times || !bc || !coeff_out || !row_tau || !row_deriv || !row_lo || !row_hi) return UAVQP_ERR_INVALID_ARG;
     if ((corr_lo == nullptr) != (corr_hi == nullptr)) return UAVQP_ERR_INVALID_ARG;
     if (uniform_segments == 0 && !seg_offsets) return UAVQP_ERR_INVALID_ARG;
-    long long total_seg = 0;
-    int Mmax = uniform_segments;
-    if (uniform_segments > 0) total_seg = (long long)uniform_segments * n_traj;
-    else {
-        if (seg_offsets[0] != 0) return UAVQP_ERR_INVALID_ARG;
-        for (int b = 0; b < n_traj; ++b) {
-            const int M = seg_offsets[b + 1] - seg_offsets[b];
-            if (M < 0) return UAVQP_ERR_INVALID_ARG;
-            if (M > Mmax) Mmax = M;
-        }
-        total_seg = seg_offsets[n_traj];
-        if (max_segments > 0 && max_segments < Mmax) Mmax = max_segments;
-        if (Mmax < 1) Mmax = 1;
-    }
+    BatchShape sh;
+    int rc = batch_shape(n_traj, uniform_segments, max_segments, seg_offsets, &sh);
+    if (rc != UAVQP_OK) return rc;
     UAVQP_HIP(hipSetDevice(ctx->device));
     const int K = rows_per_segment;
-    const size_t n_wp = 3 * (size_t)(total_seg + n_traj), n_row = (size_t)total_seg * K;
-    const size_t b_off = uniform_segments > 0 ? 0 : align256(sizeof(int32_t) * (size_t)(n_traj + 1));
-    const size_t b_wp = align256(sizeof(double) * n_wp);
-    const size_t b_t = align256(sizeof(double) * (size_t)total_seg);
-    const size_t b_bc = align256(sizeof(double) * (size_t)n_traj * 2 * (r - 1) * 3);
-    const size_t b_rt = align256(sizeof(double) * n_row), b_rd = align256(sizeof(int32_t) * n_row), b_rb = align256(sizeof(double) * 3 * n_row);
-    const size_t b_out = align256(sizeof(double) * 3 * 2 * r * (size_t)total_seg);
-    const size_t b_st = align256(sizeof(int32_t) * (size_t)n_traj);
-    int rc = ensure_stage(ctx, b_off + 3 * b_wp + b_t + b_bc + b_rt + b_rd + 2 * b_rb + b_out + 2 * b_st);
+    const size_t n = (size_t)n_traj, tot = (size_t)sh.total_seg, b_wp = sizeof(double) * 3 * (tot + n), n_row = tot * K;
+    Stage st;
+    const int i_off = uniform_segments > 0 ? -1 : st.in(seg_offsets, sizeof(int32_t) * (n + 1));
+    const int i_wp = st.in(waypoints, b_wp);
+    const int i_lo = corr_lo ? st.in(corr_lo, b_wp) : -1, i_hi = corr_lo ? st.in(corr_hi, b_wp) : -1;   // (no knot boxes: waypoint equalities)
+    const int i_t = st.in(times, sizeof(double) * tot);
+    const int i_bc = st.in(bc, sizeof(double) * n * 2 * (r - 1) * 3);
+    const int i_rt = st.in(row_tau, sizeof(double) * n_row), i_rd = st.in(row_deriv, sizeof(int32_t) * n_row);
+    const int i_rl = st.in(row_lo, sizeof(double) * 3 * n_row), i_rh = st.in(row_hi, sizeof(double) * 3 * n_row);
+    const int i_out = st.out(coeff_out, sizeof(double) * 3 * 2 * r * tot, true);
+    const int i_st = st.out(status_out, sizeof(int32_t) * n), i_it = st.out(iters_out, sizeof(int32_t) * n);
+    rc = stage_begin(ctx, st);
     if (rc != UAVQP_OK) return rc;
-    char* p = (char*)ctx->d_stage;
-    int32_t* d_off = uniform_segments > 0 ? nullptr : (int32_t*)p; p += b_off;
-    double* d_wp = (double*)p; p += b_wp;
-    double* d_lo = (double*)p; p += b_wp;
-    double* d_hi = (double*)p; p += b_wp;
-    double* d_t = (double*)p; p += b_t;
-    double* d_bc = (double*)p; p += b_bc;
-    double* d_rt = (double*)p; p += b_rt;
-    int32_t* d_rd = (int32_t*)p; p += b_rd;
-    double* d_rl = (double*)p; p += b_rb;
-    double* d_rh = (double*)p; p += b_rb;
-    double* d_out = (double*)p; p += b_out;
-    int32_t* d_st = (int32_t*)p; p += b_st;
-    int32_t* d_it = (int32_t*)p;
-    hipStream_t s = ctx->stream;
-    if (d_off) UAVQP_HIP(hipMemcpyAsync(d_off, seg_offsets, sizeof(int32_t) * (size_t)(n_traj + 1), hipMemcpyHostToDevice, s));
-    UAVQP_HIP(hipMemcpyAsync(d_wp, waypoints, sizeof(double) * n_wp, hipMemcpyHostToDevice, s));
-    if (corr_lo) {
-        UAVQP_HIP(hipMemcpyAsync(d_lo, corr_lo, sizeof(double) * n_wp, hipMemcpyHostToDevice, s));
-        UAVQP_HIP(hipMemcpyAsync(d_hi, corr_hi, sizeof(double) * n_wp, hipMemcpyHostToDevice, s));
-    }
-    if (total_seg > 0) {
-        UAVQP_HIP(hipMemcpyAsync(d_t, times, sizeof(double) * (size_t)total_seg, hipMemcpyHostToDevice, s));
-        UAVQP_HIP(hipMemcpyAsync(d_rt, row_tau, sizeof(double) * n_row, hipMemcpyHostToDevice, s));
-        UAVQP_HIP(hipMemcpyAsync(d_rd, row_deriv, sizeof(int32_t) * n_row, hipMemcpyHostToDevice, s));
-        UAVQP_HIP(hipMemcpyAsync(d_rl, row_lo, sizeof(double) * 3 * n_row, hipMemcpyHostToDevice, s));
-        UAVQP_HIP(hipMemcpyAsync(d_rh, row_hi, sizeof(double) * 3 * n_row, hipMemcpyHostToDevice, s));
-    }
-    UAVQP_HIP(hipMemcpyAsync(d_bc, bc, sizeof(double) * (size_t)n_traj * 2 * (r - 1) * 3, hipMemcpyHostToDevice, s));
-    UAVQP_HIP(hipMemsetAsync(d_out, 0, sizeof(double) * 3 * 2 * r * (size_t)total_seg, s));   // failed trajectories come back as zeros
-    rc = rows_batch_impl(ctx, r, n_traj, uniform_segments, Mmax, d_off, d_wp, d_t, d_bc, corr_lo ? d_lo : nullptr,
-                         corr_lo ? d_hi : nullptr, K, d_rt, d_rd, d_rl, d_rh, d_out, d_st, d_it, nullptr, total_seg);
+    rc = rows_batch_impl(ctx, r, n_traj, uniform_segments, sh.Mmax, st.at<int32_t>(i_off), st.at<double>(i_wp), st.at<double>(i_t),
+                         st.at<double>(i_bc), st.at<double>(i_lo), st.at<double>(i_hi), K, st.at<double>(i_rt), st.at<int32_t>(i_rd),
+                         st.at<double>(i_rl), st.at<double>(i_rh), st.at<double>(i_out), st.at<int32_t>(i_st), st.at<int32_t>(i_it), nullptr,
+                         sh.total_seg);
     if (rc != UAVQP_OK) return rc;
-    if (total_seg > 0) UAVQP_HIP(hipMemcpyAsync(coeff_out, d_out, sizeof(double) * 3 * 2 * r * (size_t)total_seg, hipMemcpyDeviceToHost, s));
-    if (status_out) UAVQP_HIP(hipMemcpyAsync(status_out, d_st, sizeof(int32_t) * (size_t)n_traj, hipMemcpyDeviceToHost, s));
-    if (iters_out) UAVQP_HIP(hipMemcpyAsync(iters_out, d_it, sizeof(int32_t) * (size_t)n_traj, hipMemcpyDeviceToHost, s));
-    UAVQP_HIP(hipStreamSynchronize(s));
-    return UAVQP_OK;
+    return stage_end(ctx, st, "uavqp_solve_rows_batch_host");
 }
 
 static int time_reallocate_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,

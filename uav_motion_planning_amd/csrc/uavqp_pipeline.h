@@ -973,75 +973,31 @@ static int corridor_pipeline_host_impl(uavqp_ctx* ctx, int r, int n_traj, int un
     if (result) *result = uavqp_pipeline_result{};
     if (n_traj == 0) return UAVQP_OK;
     if (!waypoints || !times || !bc || !coeff_out || (n_obs > 0 && !obstacles) || (uniform_segments == 0 && !seg_offsets)) return UAVQP_ERR_INVALID_ARG;
-    long long total_seg = 0;
-    int Mmax = uniform_segments;
-    if (uniform_segments > 0) total_seg = (long long)uniform_segments * n_traj;
-    else {
-        if (seg_offsets[0] != 0) return UAVQP_ERR_INVALID_ARG;
-        for (int b = 0; b < n_traj; ++b) {
-            const int M = seg_offsets[b + 1] - seg_offsets[b];
-            if (M < 0) return UAVQP_ERR_INVALID_ARG;
-            if (M > Mmax) Mmax = M;
-        }
-        total_seg = seg_offsets[n_traj];
-        if (max_segments > 0 && max_segments < Mmax) Mmax = max_segments;
-        if (Mmax < 1) Mmax = 1;
-    }
-    if (total_seg > 0x7fffffffLL - n_traj) return UAVQP_ERR_INVALID_ARG;
+    BatchShape sh;
+    int rc = batch_shape(n_traj, uniform_segments, max_segments, seg_offsets, &sh);
+    if (rc != UAVQP_OK) return rc;
     UAVQP_HIP(hipSetDevice(ctx->device));
-    const size_t n_wp = 3 * (size_t)(total_seg + n_traj);
-    const size_t b_off = uniform_segments > 0 ? 0 : align256(sizeof(int32_t) * (size_t)(n_traj + 1));
-    const size_t b_wp = align256(sizeof(double) * n_wp);
-    const size_t b_t = align256(sizeof(double) * (size_t)total_seg);
-    const size_t b_bc = align256(sizeof(double) * (size_t)n_traj * 2 * (r - 1) * 3);
-    const size_t b_obs = align256(sizeof(double) * 3 * (size_t)(n_obs > 0 ? n_obs : 1));
-    const size_t b_out = align256(sizeof(double) * 3 * 2 * r * (size_t)total_seg);
-    const size_t b_st = align256(sizeof(int32_t) * (size_t)n_traj);
-    const size_t b_rt = rows_mode ? align256(sizeof(double) * 2 * (size_t)total_seg) : 0, b_rd = rows_mode ? align256(sizeof(int32_t) * 2 * (size_t)total_seg) : 0;
-    const size_t b_rb = rows_mode ? align256(sizeof(double) * 6 * (size_t)total_seg) : 0;
-    int rc = ensure_stage(ctx, b_off + 3 * b_wp + b_t + b_bc + b_obs + b_out + 2 * b_st + b_rt + b_rd + 2 * b_rb);
+    const size_t n = (size_t)n_traj, tot = (size_t)sh.total_seg, b_wp = sizeof(double) * 3 * (tot + n);
+    Stage st;
+    const int i_off = uniform_segments > 0 ? -1 : st.in(seg_offsets, sizeof(int32_t) * (n + 1));
+    const int i_wp = st.in(waypoints, b_wp);
+    const int i_lo = st.out(corr_lo, b_wp), i_hi = st.out(corr_hi, b_wp);   // (the boxes: scratch when the caller does not want them back)
+    const int i_t = st.inout(times, sizeof(double) * tot);                  // stretched by the re-allocation
+    const int i_bc = st.in(bc, sizeof(double) * n * 2 * (r - 1) * 3);
+    const int i_obs = st.in(n_obs > 0 ? obstacles : nullptr, sizeof(double) * 3 * (size_t)(n_obs > 0 ? n_obs : 1));
+    const int i_out = st.out(coeff_out, sizeof(double) * 3 * 2 * r * tot, true);
+    const int i_st = st.out(status_out, sizeof(int32_t) * n);
+    const int i_fh = st.out(params && params->check_samples > 0 ? first_hit : nullptr, sizeof(int32_t) * n);   // (written by the check only)
+    const int i_rt = rows_mode ? st.out(row_tau, sizeof(double) * 2 * tot) : -1, i_rd = rows_mode ? st.out(row_deriv, sizeof(int32_t) * 2 * tot) : -1;
+    const int i_rl = rows_mode ? st.out(row_lo, sizeof(double) * 6 * tot) : -1, i_rh = rows_mode ? st.out(row_hi, sizeof(double) * 6 * tot) : -1;
+    rc = stage_begin(ctx, st);
     if (rc != UAVQP_OK) return rc;
-    char* p = (char*)ctx->d_stage;
-    int32_t* d_off = uniform_segments > 0 ? nullptr : (int32_t*)p; p += b_off;
-    double* d_wp = (double*)p; p += b_wp;
-    double* d_lo = (double*)p; p += b_wp;
-    double* d_hi = (double*)p; p += b_wp;
-    double* d_t = (double*)p; p += b_t;
-    double* d_bc = (double*)p; p += b_bc;
-    double* d_obs = (double*)p; p += b_obs;
-    double* d_out = (double*)p; p += b_out;
-    int32_t* d_st = (int32_t*)p; p += b_st;
-    int32_t* d_fh = (int32_t*)p; p += b_st;
-    double* d_rt = rows_mode ? (double*)p : nullptr; p += b_rt;
-    int32_t* d_rd = rows_mode ? (int32_t*)p : nullptr; p += b_rd;
-    double* d_rl = rows_mode ? (double*)p : nullptr; p += b_rb;
-    double* d_rh = rows_mode ? (double*)p : nullptr;
-    hipStream_t s = ctx->stream;
-    if (d_off) UAVQP_HIP(hipMemcpyAsync(d_off, seg_offsets, sizeof(int32_t) * (size_t)(n_traj + 1), hipMemcpyHostToDevice, s));
-    UAVQP_HIP(hipMemcpyAsync(d_wp, waypoints, sizeof(double) * n_wp, hipMemcpyHostToDevice, s));
-    if (total_seg > 0) UAVQP_HIP(hipMemcpyAsync(d_t, times, sizeof(double) * (size_t)total_seg, hipMemcpyHostToDevice, s));
-    UAVQP_HIP(hipMemcpyAsync(d_bc, bc, sizeof(double) * (size_t)n_traj * 2 * (r - 1) * 3, hipMemcpyHostToDevice, s));
-    if (n_obs > 0) UAVQP_HIP(hipMemcpyAsync(d_obs, obstacles, sizeof(double) * 3 * (size_t)n_obs, hipMemcpyHostToDevice, s));
-    UAVQP_HIP(hipMemsetAsync(d_out, 0, sizeof(double) * 3 * 2 * r * (size_t)total_seg, s));   // an invalid trajectory comes back as zeros
-    rc = corridor_pipeline_impl(ctx, r, n_traj, uniform_segments, Mmax, (int)total_seg, d_off, d_wp, d_t, d_bc, d_obs, n_obs, nullptr, params,
-                                d_out, d_st, d_lo, d_hi, d_fh, d_rt, d_rd, d_rl, d_rh, result);
+    rc = corridor_pipeline_impl(ctx, r, n_traj, uniform_segments, sh.Mmax, (int)sh.total_seg, st.at<int32_t>(i_off), st.at<double>(i_wp),
+                                st.at<double>(i_t), st.at<double>(i_bc), st.at<double>(i_obs), n_obs, nullptr, params, st.at<double>(i_out),
+                                st.at<int32_t>(i_st), st.at<double>(i_lo), st.at<double>(i_hi), st.at<int32_t>(i_fh), st.at<double>(i_rt),
+                                st.at<int32_t>(i_rd), st.at<double>(i_rl), st.at<double>(i_rh), result);
     if (rc != UAVQP_OK) return rc;
-    if (rows_mode && total_seg > 0) {
-        UAVQP_HIP(hipMemcpyAsync(row_tau, d_rt, sizeof(double) * 2 * (size_t)total_seg, hipMemcpyDeviceToHost, s));
-        UAVQP_HIP(hipMemcpyAsync(row_deriv, d_rd, sizeof(int32_t) * 2 * (size_t)total_seg, hipMemcpyDeviceToHost, s));
-        UAVQP_HIP(hipMemcpyAsync(row_lo, d_rl, sizeof(double) * 6 * (size_t)total_seg, hipMemcpyDeviceToHost, s));
-        UAVQP_HIP(hipMemcpyAsync(row_hi, d_rh, sizeof(double) * 6 * (size_t)total_seg, hipMemcpyDeviceToHost, s));
-    }
-    if (total_seg > 0) {
-        UAVQP_HIP(hipMemcpyAsync(coeff_out, d_out, sizeof(double) * 3 * 2 * r * (size_t)total_seg, hipMemcpyDeviceToHost, s));
-        UAVQP_HIP(hipMemcpyAsync(times, d_t, sizeof(double) * (size_t)total_seg, hipMemcpyDeviceToHost, s));   // stretched by the re-allocation
-    }
-    if (status_out) UAVQP_HIP(hipMemcpyAsync(status_out, d_st, sizeof(int32_t) * (size_t)n_traj, hipMemcpyDeviceToHost, s));
-    if (corr_lo) UAVQP_HIP(hipMemcpyAsync(corr_lo, d_lo, sizeof(double) * n_wp, hipMemcpyDeviceToHost, s));
-    if (corr_hi) UAVQP_HIP(hipMemcpyAsync(corr_hi, d_hi, sizeof(double) * n_wp, hipMemcpyDeviceToHost, s));
-    if (first_hit && params && params->check_samples > 0) UAVQP_HIP(hipMemcpyAsync(first_hit, d_fh, sizeof(int32_t) * (size_t)n_traj, hipMemcpyDeviceToHost, s));
-    UAVQP_HIP(hipStreamSynchronize(s));
-    return UAVQP_OK;
+    return stage_end(ctx, st, "uavqp_corridor_pipeline_host");
 }
 
 extern "C" int uavqp_corridor_pipeline_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments,

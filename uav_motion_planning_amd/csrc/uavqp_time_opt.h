@@ -151,59 +151,24 @@ extern "C" int uavqp_time_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int u
     if (n_traj == 0) return UAVQP_OK;
     if (!waypoints || !times || !bc || !coeff_out || !objective_out) return UAVQP_ERR_INVALID_ARG;
     if (uniform_segments == 0 && !seg_offsets) return UAVQP_ERR_INVALID_ARG;
-    long long total_seg = 0;
-    int Mmax = uniform_segments;
-    if (uniform_segments > 0) {
-        total_seg = (long long)uniform_segments * n_traj;
-    } else {
-        if (seg_offsets[0] != 0) return UAVQP_ERR_INVALID_ARG;
-        for (int b = 0; b < n_traj; ++b) {
-            const int M = seg_offsets[b + 1] - seg_offsets[b];
-            if (M < 0) return UAVQP_ERR_INVALID_ARG;
-            if (M > Mmax) Mmax = M;
-        }
-        total_seg = seg_offsets[n_traj];
-        if (max_segments > 0 && max_segments < Mmax) Mmax = max_segments;  // larger ones are flagged invalid
-        if (Mmax < 1) Mmax = 1;
-    }
-    if (total_seg > 0x7fffffffll) return UAVQP_ERR_INVALID_ARG;
+    BatchShape sh;
+    int rc = batch_shape(n_traj, uniform_segments, max_segments, seg_offsets, &sh);
+    if (rc != UAVQP_OK) return rc;
     UAVQP_HIP(hipSetDevice(ctx->device));
-    const size_t n = (size_t)n_traj;
-    const size_t b_off = uniform_segments > 0 ? 0 : align256(sizeof(int32_t) * (n + 1));
-    const size_t b_wp = align256(sizeof(double) * 3 * (size_t)(total_seg + n_traj));
-    const size_t b_t = align256(sizeof(double) * (size_t)total_seg);
-    const size_t b_bc = align256(sizeof(double) * n * 2 * (r - 1) * 3);
-    const size_t b_out = align256(sizeof(double) * 3 * 2 * r * (size_t)total_seg);
-    const size_t b_st = align256(sizeof(int32_t) * n);
-    const size_t b_obj = align256(sizeof(double) * 2 * n);
-    const size_t b_acc = align256(sizeof(int32_t) * n);
-    int rc = ensure_stage(ctx, b_off + b_wp + b_t + b_bc + b_out + b_st + b_obj + b_acc);
+    const size_t n = (size_t)n_traj, tot = (size_t)sh.total_seg;
+    Stage st;
+    const int i_off = uniform_segments > 0 ? -1 : st.in(seg_offsets, sizeof(int32_t) * (n + 1));
+    const int i_wp = st.in(waypoints, sizeof(double) * 3 * (tot + n));
+    const int i_t = st.inout(times, sizeof(double) * tot);
+    const int i_bc = st.in(bc, sizeof(double) * n * 2 * (r - 1) * 3);
+    const int i_out = st.out(coeff_out, sizeof(double) * 3 * 2 * r * tot, true);
+    const int i_st = st.out(status_out, sizeof(int32_t) * n);
+    const int i_obj = st.out(objective_out, sizeof(double) * 2 * n), i_acc = st.out(accepted_out, sizeof(int32_t) * n);
+    rc = stage_begin(ctx, st);
     if (rc != UAVQP_OK) return rc;
-    char* base = (char*)ctx->d_stage;
-    int32_t* d_off = uniform_segments > 0 ? nullptr : (int32_t*)base;
-    double* d_wp = (double*)(base + b_off);
-    double* d_t = (double*)(base + b_off + b_wp);
-    double* d_bc = (double*)(base + b_off + b_wp + b_t);
-    double* d_out = (double*)(base + b_off + b_wp + b_t + b_bc);
-    int32_t* d_st = (int32_t*)(base + b_off + b_wp + b_t + b_bc + b_out);
-    double* d_obj = (double*)(base + b_off + b_wp + b_t + b_bc + b_out + b_st);
-    int32_t* d_acc = (int32_t*)(base + b_off + b_wp + b_t + b_bc + b_out + b_st + b_obj);
-    hipStream_t s = ctx->stream;
-    if (d_off) UAVQP_HIP(hipMemcpyAsync(d_off, seg_offsets, sizeof(int32_t) * (n + 1), hipMemcpyHostToDevice, s));
-    UAVQP_HIP(hipMemcpyAsync(d_wp, waypoints, sizeof(double) * 3 * (size_t)(total_seg + n_traj), hipMemcpyHostToDevice, s));
-    if (total_seg > 0) UAVQP_HIP(hipMemcpyAsync(d_t, times, sizeof(double) * (size_t)total_seg, hipMemcpyHostToDevice, s));
-    UAVQP_HIP(hipMemcpyAsync(d_bc, bc, sizeof(double) * n * 2 * (r - 1) * 3, hipMemcpyHostToDevice, s));
-    // failed trajectories come back as zeros (the kernels leave them unwritten and the staging buffer is reused), like the other host entries
-    if (total_seg > 0) UAVQP_HIP(hipMemsetAsync(d_out, 0, sizeof(double) * 3 * 2 * r * (size_t)total_seg, s));
-    rc = uavqp_time_optimize_device(ctx, r, n_traj, uniform_segments, Mmax, (int)total_seg, d_off, d_wp, d_t, d_bc, params, d_out, d_st, d_obj, d_acc);
+    rc = uavqp_time_optimize_device(ctx, r, n_traj, uniform_segments, sh.Mmax, (int)sh.total_seg, st.at<int32_t>(i_off), st.at<double>(i_wp),
+                                    st.at<double>(i_t), st.at<double>(i_bc), params, st.at<double>(i_out), st.at<int32_t>(i_st),
+                                    st.at<double>(i_obj), st.at<int32_t>(i_acc));
     if (rc != UAVQP_OK) return rc;
-    if (total_seg > 0) {
-        UAVQP_HIP(hipMemcpyAsync(coeff_out, d_out, sizeof(double) * 3 * 2 * r * (size_t)total_seg, hipMemcpyDeviceToHost, s));
-        UAVQP_HIP(hipMemcpyAsync(times, d_t, sizeof(double) * (size_t)total_seg, hipMemcpyDeviceToHost, s));
-    }
-    if (status_out) UAVQP_HIP(hipMemcpyAsync(status_out, d_st, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-    UAVQP_HIP(hipMemcpyAsync(objective_out, d_obj, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, s));
-    if (accepted_out) UAVQP_HIP(hipMemcpyAsync(accepted_out, d_acc, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-    UAVQP_HIP(hipStreamSynchronize(s));
-    return UAVQP_OK;
+    return stage_end(ctx, st, "uavqp_time_optimize_host");
 }

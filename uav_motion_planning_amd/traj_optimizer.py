@@ -18,12 +18,22 @@ from . import _lib
 
 
 def _ptr(x):
-    """Raw address of a numpy array / torch tensor / None."""
-    if x is None:
-        return None
+    """Raw address of a numpy array / torch tensor; None and a raw integer address pass through."""
     if isinstance(x, np.ndarray):
         return x.ctypes.data
+    if x is None or isinstance(x, int):
+        return x
     return x.data_ptr()  # torch tensor
+
+
+def _batch_shape(seg_offsets, times, uniform_segments):
+    """(seg_offsets as int32 or None, n_traj, total segments, longest trajectory) of a host batch."""
+    if uniform_segments > 0:
+        n_traj = times.size // uniform_segments
+        return None, n_traj, n_traj * uniform_segments, uniform_segments
+    so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+    n_traj = so.size - 1
+    return so, n_traj, (int(so[-1]) if n_traj > 0 else 0), (int(np.max(np.diff(so))) if n_traj > 0 else 1)
 
 
 class Context:
@@ -79,35 +89,27 @@ class Context:
 
     def eval_batch_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, n_samples, t0, dt, what, out):
         """Batched PolyTraj::evaluatePos/Vel/Acc on the grid t0 + s*dt (device buffers, asynchronous)."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)
-        rc = _lib.lib().uavqp_eval_batch_device(self._h, r, n_traj, uniform_segments, p(seg_offsets), p(times), p(coeff),
-                                                n_samples, float(t0), float(dt), int(what), p(out))
+        rc = _lib.lib().uavqp_eval_batch_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff),
+                                                n_samples, float(t0), float(dt), int(what), _ptr(out))
         _lib.check(rc, "uavqp_eval_batch_device")
 
     def traj_length_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, dt=0.01, length=None, mean_vel=None, n_samples=None):
         """Batched PolyTraj::getTraj + getLength + getMeanVel (poly_traj.hpp:175-207; dt = the reference's 0.01 s): device buffers."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)
-        rc = _lib.lib().uavqp_traj_length_device(self._h, r, n_traj, uniform_segments, p(seg_offsets), p(times), p(coeff), float(dt),
-                                                 p(length), p(mean_vel), p(n_samples))
+        rc = _lib.lib().uavqp_traj_length_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff), float(dt),
+                                                 _ptr(length), _ptr(mean_vel), _ptr(n_samples))
         _lib.check(rc, "uavqp_traj_length_device")
 
     def time_reallocate_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, v_max, a_max,
                                samples_per_seg=16, max_stretch=1.5, changed=None):
         """One stretch-only time re-allocation step (device buffers, `times` updated in place)."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)
-        rc = _lib.lib().uavqp_time_reallocate_device(self._h, r, n_traj, uniform_segments, p(seg_offsets), p(times), p(coeff),
-                                                     float(v_max), float(a_max), int(samples_per_seg), float(max_stretch), p(changed))
+        rc = _lib.lib().uavqp_time_reallocate_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff),
+                                                     float(v_max), float(a_max), int(samples_per_seg), float(max_stretch), _ptr(changed))
         _lib.check(rc, "uavqp_time_reallocate_device")
 
     def cost_time_gradient_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, cost=None, grad=None):
         """uavqp_cost_time_gradient_device: cost [n_traj] = c' P c (integral of the squared r-th derivative, 3 axes) and grad [sum M] =
         d cost / d T_i at the minimiser of the equality-constrained solve (device buffers; either output may be None).  Asynchronous."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)
-        rc = _lib.lib().uavqp_cost_time_gradient_device(self._h, r, n_traj, uniform_segments, p(seg_offsets), p(times), p(coeff), p(cost), p(grad))
+        rc = _lib.lib().uavqp_cost_time_gradient_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff), _ptr(cost), _ptr(grad))
         _lib.check(rc, "uavqp_cost_time_gradient_device")
 
     @staticmethod
@@ -125,12 +127,10 @@ class Context:
         """uavqp_time_optimize_device on device buffers: `times` holds the start and receives the optimised durations, coeff_out the
         solve at them, objective_out [n_traj][2] f = cost + time_weight * sum T at the start and at the result.
         params: fields of uavqp_time_opt_params that differ from uavqp_default_time_opt_params.  Asynchronous."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)
         pp = self._time_opt_params(params)
-        rc = _lib.lib().uavqp_time_optimize_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), p(seg_offsets),
-                                                   p(waypoints), p(times), p(bc), ctypes.byref(pp), p(coeff_out), p(status_out),
-                                                   p(objective_out), p(accepted_out))
+        rc = _lib.lib().uavqp_time_optimize_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), _ptr(seg_offsets),
+                                                   _ptr(waypoints), _ptr(times), _ptr(bc), ctypes.byref(pp), _ptr(coeff_out), _ptr(status_out),
+                                                   _ptr(objective_out), _ptr(accepted_out))
         _lib.check(rc, "uavqp_time_optimize_device")
 
     def time_optimize_host(self, r, seg_offsets, waypoints, times, bc, uniform_segments=0, **params):
@@ -138,16 +138,7 @@ class Context:
         waypoints = np.ascontiguousarray(waypoints, dtype=np.float64)
         times = np.array(times, dtype=np.float64).ravel()   # a copy: the call updates it in place
         bc = np.ascontiguousarray(bc, dtype=np.float64)
-        if uniform_segments > 0:
-            n_traj = times.size // uniform_segments
-            so = None
-            total = n_traj * uniform_segments
-            mmax = uniform_segments
-        else:
-            so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-            n_traj = so.size - 1
-            total = int(so[-1]) if n_traj > 0 else 0
-            mmax = int(np.max(np.diff(so))) if n_traj > 0 else 1
+        so, n_traj, total, mmax = _batch_shape(seg_offsets, times, uniform_segments)
         assert times.size == total
         assert waypoints.size == 3 * (total + n_traj), "waypoints must hold sum(M_b + 1) xyz rows"
         assert bc.size == n_traj * 2 * (r - 1) * 3
@@ -164,11 +155,9 @@ class Context:
     def ellipsoid_check_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, n_samples, t0, dt,
                                obstacles, n_obs, robot_r, robot_h, first_hit, flags=None):
         """Batched KinoAstar::isCollisionFree over the samples of solved trajectories (device buffers)."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)
-        rc = _lib.lib().uavqp_ellipsoid_check_device(self._h, r, n_traj, uniform_segments, p(seg_offsets), p(times), p(coeff),
-                                                     n_samples, float(t0), float(dt), p(obstacles), int(n_obs),
-                                                     float(robot_r), float(robot_h), p(first_hit), p(flags))
+        rc = _lib.lib().uavqp_ellipsoid_check_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff),
+                                                     n_samples, float(t0), float(dt), _ptr(obstacles), int(n_obs),
+                                                     float(robot_r), float(robot_h), _ptr(first_hit), _ptr(flags))
         _lib.check(rc, "uavqp_ellipsoid_check_device")
 
     def solve_corridor_device(self, r, n_traj, uniform_segments, max_segments, seg_offsets, waypoints, times, bc, corr_lo, corr_hi,
@@ -176,41 +165,35 @@ class Context:
         """Corridor-constrained solve on device buffers; active_set ([n_traj,3,2] int64/uint64 device tensor) carries the
         working set between the re-solves of an outer loop (warm_start=True reads it; warm_start=2 also starts the free positions from
         the polynomials found in coeff_out -- include/uavqp.h)."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)
-        rc = _lib.lib().uavqp_solve_corridor_warm_device(self._h, r, n_traj, uniform_segments, max_segments, p(seg_offsets), p(waypoints),
-                                                         p(times), p(bc), p(corr_lo), p(corr_hi), p(coeff_out), p(status_out),
-                                                         p(iters_out), p(active_set), int(warm_start))
+        rc = _lib.lib().uavqp_solve_corridor_warm_device(self._h, r, n_traj, uniform_segments, max_segments, _ptr(seg_offsets), _ptr(waypoints),
+                                                         _ptr(times), _ptr(bc), _ptr(corr_lo), _ptr(corr_hi), _ptr(coeff_out), _ptr(status_out),
+                                                         _ptr(iters_out), _ptr(active_set), int(warm_start))
         _lib.check(rc, "uavqp_solve_corridor_warm_device")
 
     def solve_rows_device(self, r, n_traj, uniform_segments, max_segments, seg_offsets, waypoints, times, bc, corr_lo, corr_hi,
                           rows_per_segment, row_tau, row_deriv, row_lo, row_hi, coeff_out, status_out, iters_out=None, active_out=None):
         """Knot boxes (or None: waypoint equalities) + up to rows_per_segment general rows lo <= p_i^(d)(tau T_i) <= hi per segment and
         axis; exact dual active-set solve on device buffers (uavqp_solve_rows_batch_device)."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)
-        rc = _lib.lib().uavqp_solve_rows_batch_device(self._h, r, n_traj, uniform_segments, max_segments, p(seg_offsets), p(waypoints),
-                                                      p(times), p(bc), p(corr_lo), p(corr_hi), int(rows_per_segment), p(row_tau),
-                                                      p(row_deriv), p(row_lo), p(row_hi), p(coeff_out), p(status_out), p(iters_out),
-                                                      p(active_out))
+        rc = _lib.lib().uavqp_solve_rows_batch_device(self._h, r, n_traj, uniform_segments, max_segments, _ptr(seg_offsets), _ptr(waypoints),
+                                                      _ptr(times), _ptr(bc), _ptr(corr_lo), _ptr(corr_hi), int(rows_per_segment), _ptr(row_tau),
+                                                      _ptr(row_deriv), _ptr(row_lo), _ptr(row_hi), _ptr(coeff_out), _ptr(status_out), _ptr(iters_out),
+                                                      _ptr(active_out))
         _lib.check(rc, "uavqp_solve_rows_batch_device")
 
     def corridor_from_cloud_device(self, r, n_traj, uniform_segments, seg_offsets, n_rows, waypoints, times, coeff,
                                    obstacles, n_obs, robot_r, robot_h, h_max, corr_lo, corr_hi, clearance=None):
         """Corridor boxes of every waypoint row from an obstacle cloud, robot ellipsoid of kino_astar.cpp:721-758
         (device buffers; coeff/times None = hover attitude)."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)
-        rc = _lib.lib().uavqp_corridor_from_cloud_device(self._h, r, n_traj, uniform_segments, p(seg_offsets), int(n_rows),
-                                                         p(waypoints), p(times), p(coeff), p(obstacles), int(n_obs),
-                                                         float(robot_r), float(robot_h), float(h_max), p(corr_lo), p(corr_hi),
-                                                         p(clearance))
+        rc = _lib.lib().uavqp_corridor_from_cloud_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), int(n_rows),
+                                                         _ptr(waypoints), _ptr(times), _ptr(coeff), _ptr(obstacles), int(n_obs),
+                                                         float(robot_r), float(robot_h), float(h_max), _ptr(corr_lo), _ptr(corr_hi),
+                                                         _ptr(clearance))
         _lib.check(rc, "uavqp_corridor_from_cloud_device")
 
     def obstacle_grid_build(self, obstacles, n_obs, cell_size):
         """Uniform grid over a device point cloud; returns an opaque handle (free it with obstacle_grid_destroy)."""
         h = ctypes.c_void_p()
-        rc = _lib.lib().uavqp_obstacle_grid_build_device(self._h, obstacles if isinstance(obstacles, int) or obstacles is None else _ptr(obstacles),
+        rc = _lib.lib().uavqp_obstacle_grid_build_device(self._h, _ptr(obstacles),
                                                          int(n_obs), float(cell_size), ctypes.byref(h))
         _lib.check(rc, "uavqp_obstacle_grid_build_device")
         return h
@@ -221,11 +204,9 @@ class Context:
     def ellipsoid_check_grid_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, n_samples, t0, dt,
                                     grid, robot_r, robot_h, first_hit, flags=None):
         """ellipsoid_check_device with the candidates taken from an obstacle grid (identical flags, no exhaustive scan)."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)
-        rc = _lib.lib().uavqp_ellipsoid_check_grid_device(self._h, r, n_traj, uniform_segments, p(seg_offsets), p(times), p(coeff),
+        rc = _lib.lib().uavqp_ellipsoid_check_grid_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff),
                                                           n_samples, float(t0), float(dt), grid, float(robot_r), float(robot_h),
-                                                          p(first_hit), p(flags))
+                                                          _ptr(first_hit), _ptr(flags))
         _lib.check(rc, "uavqp_ellipsoid_check_grid_device")
 
     @staticmethod
@@ -243,13 +224,11 @@ class Context:
         """uavqp_corridor_pipeline_device: BASELINE config 5 as one C-ABI call on device buffers (times is stretched in place).
         params: fields of uavqp_pipeline_params that differ from uavqp_default_pipeline_params.  Returns the uavqp_pipeline_result
         fields as a dict (repair_rows is 0: the box repair places no rows).  Synchronous."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)
         pp = self._pipeline_params(params)
         res = _lib.PipelineResult()
-        rc = _lib.lib().uavqp_corridor_pipeline_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), p(seg_offsets),
-                                                       p(waypoints), p(times), p(bc), p(obstacles), int(n_obs), grid, ctypes.byref(pp),
-                                                       p(coeff_out), p(status_out), p(corr_lo), p(corr_hi), p(first_hit), ctypes.byref(res))
+        rc = _lib.lib().uavqp_corridor_pipeline_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), _ptr(seg_offsets),
+                                                       _ptr(waypoints), _ptr(times), _ptr(bc), _ptr(obstacles), int(n_obs), grid, ctypes.byref(pp),
+                                                       _ptr(coeff_out), _ptr(status_out), _ptr(corr_lo), _ptr(corr_hi), _ptr(first_hit), ctypes.byref(res))
         _lib.check(rc, "uavqp_corridor_pipeline_device")
         return {k: getattr(res, k) for k, _ in _lib.PipelineResult._fields_}
 
@@ -259,14 +238,12 @@ class Context:
         """uavqp_corridor_pipeline_rows_device: corridor_pipeline_device with the rows repair (between-knot hits become position rows,
         knot boxes stay).  row_tau / row_deriv [total_segments, 2], row_lo / row_hi [total_segments, 2, 3] device buffers: set to unused
         by the call, on return the rows of the final solve.  Returns the uavqp_pipeline_result fields as a dict.  Synchronous."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)
         pp = self._pipeline_params(params)
         res = _lib.PipelineResult()
-        rc = _lib.lib().uavqp_corridor_pipeline_rows_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), p(seg_offsets),
-                                                            p(waypoints), p(times), p(bc), p(obstacles), int(n_obs), grid, ctypes.byref(pp),
-                                                            p(coeff_out), p(status_out), p(corr_lo), p(corr_hi), p(first_hit), p(row_tau),
-                                                            p(row_deriv), p(row_lo), p(row_hi), ctypes.byref(res))
+        rc = _lib.lib().uavqp_corridor_pipeline_rows_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), _ptr(seg_offsets),
+                                                            _ptr(waypoints), _ptr(times), _ptr(bc), _ptr(obstacles), int(n_obs), grid, ctypes.byref(pp),
+                                                            _ptr(coeff_out), _ptr(status_out), _ptr(corr_lo), _ptr(corr_hi), _ptr(first_hit), _ptr(row_tau),
+                                                            _ptr(row_deriv), _ptr(row_lo), _ptr(row_hi), ctypes.byref(res))
         _lib.check(rc, "uavqp_corridor_pipeline_rows_device")
         return {k: getattr(res, k) for k, _ in _lib.PipelineResult._fields_}
 
@@ -275,12 +252,10 @@ class Context:
         """uavqp_repair_rows_from_hits_device: position rows around pushed-out anchors for the colliding runs of a check's per-sample
         flags ([n_traj, n_samples] uint8).  Row arrays IN / OUT in the rows_per_segment = 2 layout; new_rows [n_traj] int32 OUT.
         Device buffers, asynchronous."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)
-        rc = _lib.lib().uavqp_repair_rows_from_hits_device(self._h, r, n_traj, uniform_segments, p(seg_offsets), p(waypoints), p(times),
-                                                           p(coeff), int(n_samples), float(t0), float(dt), p(flags), p(obstacles), int(n_obs),
-                                                           float(robot_r), float(robot_h), float(h_max), p(row_tau), p(row_deriv), p(row_lo),
-                                                           p(row_hi), p(new_rows))
+        rc = _lib.lib().uavqp_repair_rows_from_hits_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(waypoints), _ptr(times),
+                                                           _ptr(coeff), int(n_samples), float(t0), float(dt), _ptr(flags), _ptr(obstacles), int(n_obs),
+                                                           float(robot_r), float(robot_h), float(h_max), _ptr(row_tau), _ptr(row_deriv), _ptr(row_lo),
+                                                           _ptr(row_hi), _ptr(new_rows))
         _lib.check(rc, "uavqp_repair_rows_from_hits_device")
 
     # ---- multi-GPU: the ctx owns an RCCL communicator (include/uavqp.h, "Multi-GPU") ----
@@ -336,10 +311,8 @@ class Context:
     def solve_batch_device(self, r, n_traj, uniform_segments, max_segments, seg_offsets, waypoints, times, bc,
                            coeff_out, status_out=None):
         """All array arguments are device buffers (torch CUDA tensors or raw integer addresses). Asynchronous."""
-        def p(x):
-            return x if isinstance(x, int) or x is None else _ptr(x)
-        rc = _lib.lib().uavqp_solve_batch_device(self._h, r, n_traj, uniform_segments, max_segments, p(seg_offsets),
-                                                 p(waypoints), p(times), p(bc), p(coeff_out), p(status_out))
+        rc = _lib.lib().uavqp_solve_batch_device(self._h, r, n_traj, uniform_segments, max_segments, _ptr(seg_offsets),
+                                                 _ptr(waypoints), _ptr(times), _ptr(bc), _ptr(coeff_out), _ptr(status_out))
         _lib.check(rc, "uavqp_solve_batch_device")
 
     def solve_batch_host(self, r, seg_offsets, waypoints, times, bc, uniform_segments=0):
@@ -347,16 +320,7 @@ class Context:
         waypoints = np.ascontiguousarray(waypoints, dtype=np.float64)
         times = np.ascontiguousarray(times, dtype=np.float64)
         bc = np.ascontiguousarray(bc, dtype=np.float64)
-        if uniform_segments > 0:
-            n_traj = times.size // uniform_segments
-            so = None
-            total = n_traj * uniform_segments
-            mmax = uniform_segments
-        else:
-            so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-            n_traj = so.size - 1
-            total = int(so[-1]) if n_traj > 0 else 0
-            mmax = int(np.max(np.diff(so))) if n_traj > 0 else 1
+        so, n_traj, total, mmax = _batch_shape(seg_offsets, times, uniform_segments)
         assert waypoints.size == 3 * (total + n_traj), "waypoints must hold sum(M_b + 1) xyz rows"
         assert bc.size == n_traj * 2 * (r - 1) * 3
         coeff = np.zeros(3 * 2 * r * total, dtype=np.float64)
@@ -373,14 +337,7 @@ class Context:
         bc = np.ascontiguousarray(bc, dtype=np.float64)
         lo = np.ascontiguousarray(corr_lo, dtype=np.float64)
         hi = np.ascontiguousarray(corr_hi, dtype=np.float64)
-        if uniform_segments > 0:
-            n_traj = times.size // uniform_segments
-            so, total, mmax = None, n_traj * uniform_segments, uniform_segments
-        else:
-            so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-            n_traj = so.size - 1
-            total = int(so[-1]) if n_traj > 0 else 0
-            mmax = int(np.max(np.diff(so))) if n_traj > 0 else 1
+        so, n_traj, total, mmax = _batch_shape(seg_offsets, times, uniform_segments)
         assert waypoints.size == 3 * (total + n_traj) == lo.size == hi.size
         coeff = np.zeros(3 * 2 * r * total, dtype=np.float64)
         status = np.zeros(n_traj, dtype=np.int32)
@@ -404,14 +361,7 @@ class Context:
         drv = np.ascontiguousarray(row_deriv, dtype=np.int32)
         rlo = np.ascontiguousarray(row_lo, dtype=np.float64)
         rhi = np.ascontiguousarray(row_hi, dtype=np.float64)
-        if uniform_segments > 0:
-            n_traj = times.size // uniform_segments
-            so, total, mmax = None, n_traj * uniform_segments, uniform_segments
-        else:
-            so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
-            n_traj = so.size - 1
-            total = int(so[-1]) if n_traj > 0 else 0
-            mmax = int(np.max(np.diff(so))) if n_traj > 0 else 1
+        so, n_traj, total, mmax = _batch_shape(seg_offsets, times, uniform_segments)
         K = int(rows_per_segment)
         assert waypoints.size == 3 * (total + n_traj) and tau.size == total * K == drv.size and rlo.size == 3 * total * K == rhi.size
         coeff = np.zeros(3 * 2 * r * total, dtype=np.float64)
