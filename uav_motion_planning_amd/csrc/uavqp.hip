@@ -136,49 +136,6 @@ static int await_host_word(hipStream_t s, volatile unsigned long long* w, unsign
     return UAVQP_OK;
 }
 
-struct uavqp_ctx {
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    int variant = 0;
-    int tile_override = 0;  // fixed tile shape of the specialised kernel (variants 4 / 8 / 16 / 32)
-    uavqp_settings settings{};
-    int num_cus = 256;
-    double* ws = nullptr;
-    size_t ws_bytes = 0;
-    uavqp::Comm comm;         // RCCL communicator of the multi-GPU entry points (uavqp_comm_create)
-    void* rows_warm2 = nullptr;      // rows part of the starting set of the general-rows solve + the "box phase needed" flags (qp_rows_dual.h)
-    size_t rows_warm2_bytes = 0;
-    void* dbg_queue = nullptr;  // (debug builds) where the last corridor solve kept its work counter
-    int dual_trips_extra = 0;   // added to the trip budget 4 n + 16 of the dual preludes (UAVQP_DUAL_TRIPS_EXTRA, may be negative: tools/ experiments)
-    int wave_prelude = 2;       // re-solves with G in the cache: 2 = corridor_dual_wave2_kernel (two trajectories per wave), 1 = corridor_dual_wave_kernel (one),
-                                // 0 = the batch kernels (UAVQP_WAVE_PRELUDE=0|1|2, UAVQP_NO_WAVE_PRELUDE: A/B runs)
-    void* dbg_dual = nullptr;   // (UAVQP_DUAL_DEBUG builds) dump area of corridor_dual_kernel
-    void* dbg_guess = nullptr;  // (UAVQP_DUAL_DEBUG builds) the starting sets of the last cold corridor solve
-    int32_t* perm = nullptr;  // ragged dealing permutation (window_sort_kernel); behind it the packed {b, s0, M, 0} records
-    size_t perm_count = 0;
-    uint64_t* rows_warm = nullptr;   // [n_traj][3][2] working set of the box-only phase of uavqp_solve_rows_batch_device
-    size_t rows_warm_count = 0;
-    double* dummy = nullptr;
-    int deal_tickets = 1;            // rows_dual_kernel deals its trajectories by ticket (UAVQP_DEAL_TICKETS=0: round-robin as in rounds 4-5, A/B runs)
-    // staging buffers of the host-pointer entry points
-    void* d_stage = nullptr;
-    size_t stage_bytes = 0;
-    // pinned, device-mapped page of the single-axis entry point (uavqp_solve_axis_host): the kernel reads the inputs of the one
-    // trajectory from it and writes coefficients and status into it -- no copy calls on that path
-    void* h_axis = nullptr;
-    void* d_axis = nullptr;
-    size_t axis_bytes = 0;
-    // corridor pipeline (uavqp_pipeline.h): device scratch (counters, flags, working sets) and the pinned page its counters are read through
-    void* d_pipe = nullptr;
-    size_t pipe_bytes = 0;
-    void* h_pipe = nullptr;
-    // duration optimiser (uavqp_time_opt.h): trial durations, stored gradient and the per-trajectory state of the descent
-    void* d_topt = nullptr;
-    size_t topt_bytes = 0;
-    unsigned int pipe_seq = 0;   // sequence number of the last pipeline round enqueued (uavqp_pipeline.h: tags the count a round reports to the host)
-};
-
 #define UAVQP_HIP(expr)                                                                          \
     do {                                                                                         \
         hipError_t e_ = (expr);                                                                  \
@@ -187,6 +144,44 @@ struct uavqp_ctx {
             return UAVQP_ERR_HIP;                                                                \
         }                                                                                        \
     } while (0)
+
+#include "uavqp_ws.h"
+
+struct uavqp_ctx {
+    int device = 0;
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;
+    int variant = 0;
+    int tile_override = 0;  // fixed tile shape of the specialised kernel (variants 4 / 8 / 16 / 32)
+    uavqp_settings settings{};
+    int num_cus = 256;
+    DevBuf ws;                // scratch of the solvers and the cloud scans: every entry lays it out anew
+    uavqp::Comm comm;         // RCCL communicator of the multi-GPU entry points (uavqp_comm_create)
+    DevBuf rows_warm2;        // rows part of the starting set of the general-rows solve + the "box phase needed" flags (qp_rows_dual.h)
+    void* dbg_queue = nullptr;  // (debug builds) where the last corridor solve kept its work counter
+    int dual_trips_extra = 0;   // added to the trip budget 4 n + 16 of the dual preludes (UAVQP_DUAL_TRIPS_EXTRA, may be negative: tools/ experiments)
+    int wave_prelude = 2;       // re-solves with G in the cache: 2 = corridor_dual_wave2_kernel (two trajectories per wave), 1 = corridor_dual_wave_kernel (one),
+                                // 0 = the batch kernels (UAVQP_WAVE_PRELUDE=0|1|2, UAVQP_NO_WAVE_PRELUDE: A/B runs)
+    void* dbg_dual = nullptr;   // (UAVQP_DUAL_DEBUG builds) dump area of corridor_dual_kernel
+    void* dbg_guess = nullptr;  // (UAVQP_DUAL_DEBUG builds) the starting sets of the last cold corridor solve
+    DevBuf perm;              // ragged dealing permutation (window_sort_kernel); behind it the packed {b, s0, M, 0} records
+    DevBuf rows_warm;         // [n_traj][3][2] working set of the box-only phase of uavqp_solve_rows_batch_device
+    double* dummy = nullptr;
+    int deal_tickets = 1;            // rows_dual_kernel deals its trajectories by ticket (UAVQP_DEAL_TICKETS=0: round-robin as in rounds 4-5, A/B runs)
+    // staging buffers of the host-pointer entry points
+    DevBuf stage;
+    // pinned, device-mapped page of the single-axis entry point (uavqp_solve_axis_host): the kernel reads the inputs of the one
+    // trajectory from it and writes coefficients and status into it -- no copy calls on that path
+    void* h_axis = nullptr;
+    void* d_axis = nullptr;
+    size_t axis_bytes = 0;
+    // corridor pipeline (uavqp_pipeline.h): device scratch (counters, flags, working sets) and the pinned page its counters are read through
+    DevBuf pipe;
+    void* h_pipe = nullptr;
+    // duration optimiser (uavqp_time_opt.h): trial durations, stored gradient and the per-trajectory state of the descent
+    DevBuf topt;
+    unsigned int pipe_seq = 0;   // sequence number of the last pipeline round enqueued (uavqp_pipeline.h: tags the count a round reports to the host)
+};
 
 #ifndef UAVQP_SRC_HASH
 #define UAVQP_SRC_HASH "unknown"
@@ -322,16 +317,10 @@ extern "C" int uavqp_destroy(uavqp_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->comm.comm) (void)uavqp_comm_destroy(ctx);
-    if (ctx->ws) (void)hipFree(ctx->ws);
-    if (ctx->perm) (void)hipFree(ctx->perm);
+    for (DevBuf* b : {&ctx->ws, &ctx->perm, &ctx->rows_warm, &ctx->rows_warm2, &ctx->stage, &ctx->pipe, &ctx->topt}) dev_free(*b);
     if (ctx->dummy) (void)hipFree(ctx->dummy);
     if (ctx->h_axis) (void)hipHostFree(ctx->h_axis);
-    if (ctx->rows_warm) (void)hipFree(ctx->rows_warm);
-    if (ctx->rows_warm2) (void)hipFree(ctx->rows_warm2);
-    if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-    if (ctx->d_pipe) (void)hipFree(ctx->d_pipe);
     if (ctx->h_pipe) (void)hipHostFree(ctx->h_pipe);
-    if (ctx->d_topt) (void)hipFree(ctx->d_topt);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return UAVQP_OK;
@@ -366,19 +355,6 @@ extern "C" int uavqp_set_variant(uavqp_ctx* ctx, int variant) {
     const int rc = apply_variant(ctx, variant);
     if (rc == UAVQP_OK) ctx->settings.kernel_variant = variant;
     return rc;
-}
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static int ensure_ws(uavqp_ctx* ctx, size_t bytes) {
-    if (bytes <= ctx->ws_bytes) return UAVQP_OK;
-    UAVQP_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->ws) UAVQP_HIP(hipFree(ctx->ws));
-    ctx->ws = nullptr;
-    ctx->ws_bytes = 0;
-    UAVQP_HIP(hipMalloc((void**)&ctx->ws, bytes));
-    ctx->ws_bytes = bytes;
-    return UAVQP_OK;
 }
 
 extern "C" int uavqp_solve_batch_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments,
@@ -470,9 +446,9 @@ extern "C" int uavqp_solve_batch_device(uavqp_ctx* ctx, int r, int n_traj, int u
     if (lsort) grid = (grid + 15) / 16 * 16;
     const int F = (r - 1) * (r - 1) + nax * (r - 1);
     const size_t ws_bytes = sizeof(double) * (size_t)(Mmax > 1 ? Mmax - 1 : 1) * F * (size_t)grid * block;
-    int rc = ensure_ws(ctx, ws_bytes);
+    int rc = dev_grow(ctx->stream, ctx->ws, ws_bytes);
     if (rc != UAVQP_OK) return rc;
-    a.ws = ctx->ws;
+    a.ws = (double*)ctx->ws.p;
     a.perm = nullptr;
     a.perm4 = nullptr;
     // round 6: the pair kernel's waves rank their window themselves (qp_generic2.h) -- no window_sort_kernel launch in front of the solve, no
@@ -480,22 +456,18 @@ extern "C" int uavqp_solve_batch_device(uavqp_ctx* ctx, int r, int n_traj, int u
     a.fused_sort = (lsort && pair && Mmax <= 63 && ctx->settings.ragged_window_sort != 2) ? 1 : 0;
     if (lsort && !a.fused_sort) {
         // dealing permutation: one counting sort per window of 16 waves' trajectories (see window_sort_kernel)
-        if ((size_t)n_traj > ctx->perm_count) {
-            UAVQP_HIP(hipStreamSynchronize(ctx->stream));
-            if (ctx->perm) UAVQP_HIP(hipFree(ctx->perm));
-            ctx->perm = nullptr;
-            ctx->perm_count = 0;
-            // [n_traj] int32 + (16-byte aligned) [n_traj] int4
-            UAVQP_HIP(hipMalloc((void**)&ctx->perm, align256(sizeof(int32_t) * (size_t)n_traj) + sizeof(int4) * (size_t)n_traj));
-            ctx->perm_count = (size_t)n_traj;
-        }
-        int4* perm4 = pair ? (int4*)((char*)ctx->perm + align256(sizeof(int32_t) * ctx->perm_count)) : nullptr;
+        // [n_traj] int32 + (16-byte aligned) [n_traj] int4
+        const size_t b_perm = align256(sizeof(int32_t) * (size_t)n_traj);
+        rc = dev_grow(ctx->stream, ctx->perm, b_perm + sizeof(int4) * (size_t)n_traj);
+        if (rc != UAVQP_OK) return rc;
+        int32_t* const perm = (int32_t*)ctx->perm.p;
+        int4* perm4 = pair ? (int4*)((char*)ctx->perm.p + b_perm) : nullptr;
         const int win = 16 * ipw;
         const int n_win = (n_traj + win - 1) / win;
-        if (pair) hipLaunchKernelGGL((uavqp::window_sort_kernel<512>), dim3(n_win), dim3(256), 0, ctx->stream, d_seg_offsets, n_traj, ctx->perm, perm4);
-        else if (nax == 3) hipLaunchKernelGGL((uavqp::window_sort_kernel<1024>), dim3(n_win), dim3(256), 0, ctx->stream, d_seg_offsets, n_traj, ctx->perm, perm4);
-        else hipLaunchKernelGGL((uavqp::window_sort_kernel<336>), dim3(n_win), dim3(256), 0, ctx->stream, d_seg_offsets, n_traj, ctx->perm, perm4);
-        a.perm = ctx->perm;
+        if (pair) hipLaunchKernelGGL((uavqp::window_sort_kernel<512>), dim3(n_win), dim3(256), 0, ctx->stream, d_seg_offsets, n_traj, perm, perm4);
+        else if (nax == 3) hipLaunchKernelGGL((uavqp::window_sort_kernel<1024>), dim3(n_win), dim3(256), 0, ctx->stream, d_seg_offsets, n_traj, perm, perm4);
+        else hipLaunchKernelGGL((uavqp::window_sort_kernel<336>), dim3(n_win), dim3(256), 0, ctx->stream, d_seg_offsets, n_traj, perm, perm4);
+        a.perm = perm;
         a.perm4 = perm4;
     }
 #define UAVQP_GENERIC(RR)                                                                                                   \
@@ -517,18 +489,6 @@ extern "C" int uavqp_solve_batch_device(uavqp_ctx* ctx, int r, int n_traj, int u
     UAVQP_HIP(hipGetLastError());
     return UAVQP_OK;
 }
-
-static int ensure_stage(uavqp_ctx* ctx, size_t bytes) {
-    if (bytes <= ctx->stage_bytes) return UAVQP_OK;
-    UAVQP_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->d_stage) UAVQP_HIP(hipFree(ctx->d_stage));
-    ctx->d_stage = nullptr;
-    ctx->stage_bytes = 0;
-    UAVQP_HIP(hipMalloc(&ctx->d_stage, bytes));
-    ctx->stage_bytes = bytes;
-    return UAVQP_OK;
-}
-
 
 // the pinned, device-mapped staging page of the latency paths (single-axis entry point, small host batches)
 static constexpr size_t MAPPED_HEAD = 256;   // head of the mapped page: the completion word of the polled host entries
@@ -570,7 +530,7 @@ extern "C" int uavqp_solve_batch_host(uavqp_ctx* ctx, int r, int n_traj, int uni
     // pinned page that is mapped into the device, the kernels read and write it over the host link, and the call is the
     // launch(es) plus one polled word instead of 3-4 H2D copies, a memset, 2 D2H copies and a stream synchronisation (measured, one
     // 7-segment trajectory: 72 -> 3x us per call).
-    rc = stage_begin(ctx, st, st.total <= 256 * 1024);
+    rc = stage_begin(ctx, st, st.lay.total <= 256 * 1024);
     if (rc != UAVQP_OK) return rc;
     rc = uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, sh.Mmax, st.at<int32_t>(i_off), st.at<double>(i_wp), st.at<double>(i_t),
                                   st.at<double>(i_bc), st.at<double>(i_out), st.at<int32_t>(i_st));
@@ -706,13 +666,17 @@ extern "C" int uavqp_traj_length_device(uavqp_ctx* ctx, int r, int n_traj, int u
     return UAVQP_OK;
 }
 
-// Dealing order of a ragged batch (longest trajectory first; seg_hist / seg_scan / seg_scatter_kernel): order [n_traj] at `storage`,
-// histogram and cursors in its last 2048 bytes (storage = align256(4 n_traj) + 2048 bytes).  The order depends on the segment counts
-// only: a caller that re-solves the same batch (the config-5 pipeline) makes it once and passes it to corridor_warm_impl.
-static size_t length_order_bytes(int n_traj) { return align256(sizeof(int32_t) * (size_t)n_traj) + 2048; }
-static int make_length_order(uavqp_ctx* ctx, const int32_t* d_seg_offsets, int n_traj, char* storage, const int32_t** d_order_out) {
-    int32_t* d_order = (int32_t*)storage;
-    int* d_hist = (int*)(storage + length_order_bytes(n_traj) - 2048);
+// Dealing order of a ragged batch (longest trajectory first; seg_hist / seg_scan / seg_scatter_kernel): order [n_traj], then the histogram
+// and the cursors (256 ints each) -- align256(4 n_traj) + 2048 bytes, declared on the caller's layout by length_order_slots (absent:
+// nothing is reserved).  The order depends on the segment counts only: a caller that re-solves the same batch (the config-5 pipeline)
+// makes it once and passes it to corridor_warm_impl.
+struct LengthOrder { int order, hist; };
+static LengthOrder length_order_slots(Carve& c, int n_traj, bool present) {
+    return LengthOrder{c.add(sizeof(int32_t) * (size_t)n_traj, present), c.add(2048, present)};
+}
+static int make_length_order(uavqp_ctx* ctx, const int32_t* d_seg_offsets, int n_traj, const Carve& c, LengthOrder lo, const int32_t** d_order_out) {
+    int32_t* d_order = c.at<int32_t>(lo.order);
+    int* d_hist = c.at<int>(lo.hist);
     int* d_cursor = d_hist + 256;
     UAVQP_HIP(hipMemsetAsync(d_hist, 0, 256 * sizeof(int), ctx->stream));
     int sg = (n_traj + 255) / 256;
@@ -721,6 +685,21 @@ static int make_length_order(uavqp_ctx* ctx, const int32_t* d_seg_offsets, int n
     hipLaunchKernelGGL(uavqp::seg_scan_kernel, dim3(1), dim3(256), 0, ctx->stream, d_hist, d_cursor);
     hipLaunchKernelGGL(uavqp::seg_scatter_kernel, dim3(sg), dim3(256), 0, ctx->stream, d_seg_offsets, n_traj, d_cursor, d_order);
     *d_order_out = d_order;
+    return UAVQP_OK;
+}
+
+// Waypoint rows of a batch, sum(M_b) + n_traj.  Ragged with total_segments < 0 (unknown): the last CSR offset is only known on the
+// device; a 4-byte read-back (synchronous on the ctx stream).
+static int batch_rows(uavqp_ctx* ctx, int n_traj, int uniform_segments, long long total_segments, const int32_t* d_seg_offsets, long long* rows) {
+    if (uniform_segments > 0) *rows = (long long)n_traj * (uniform_segments + 1);
+    else if (total_segments >= 0) *rows = total_segments + n_traj;
+    else {
+        int32_t last = 0;
+        UAVQP_HIP(hipMemcpyAsync(&last, d_seg_offsets + n_traj, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        UAVQP_HIP(hipStreamSynchronize(ctx->stream));
+        if (last < 0) return UAVQP_ERR_INVALID_ARG;
+        *rows = (long long)last + n_traj;
+    }
     return UAVQP_OK;
 }
 
@@ -775,51 +754,42 @@ static int corridor_warm_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_seg
     const int own_max = (Mmax + 1) / 2;        // own knots of the longer half, meeting knot included
     const int ws_knots = own_max > NT ? own_max - NT : 0;
     long long rows = 0;                        // waypoint rows of the batch
-    if (uniform_segments > 0) rows = (long long)n_traj * (uniform_segments + 1);
-    else if (total_segments >= 0) rows = total_segments + n_traj;
-    else {
-        // sum(M_b) + n_traj: the last CSR offset is only known on the device; a 4-byte read-back (synchronous on the ctx stream)
-        int32_t last = 0;
-        UAVQP_HIP(hipMemcpyAsync(&last, d_seg_offsets + n_traj, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        UAVQP_HIP(hipStreamSynchronize(ctx->stream));
-        if (last < 0) return UAVQP_ERR_INVALID_ARG;
-        rows = (long long)last + n_traj;
-    }
-    const size_t b_xsol = align256(sizeof(double) * 3 * (size_t)r * (size_t)rows);
-    const size_t b_queue = 256;
-    const size_t b_desc = align256(sizeof(unsigned long long) * 3 * (size_t)n_traj);
+    int rc = batch_rows(ctx, n_traj, uniform_segments, total_segments, d_seg_offsets, &rows);
+    if (rc != UAVQP_OK) return rc;
     // (a caller that hands over a compacted dealing order -- the rows solve's box phase, the pipeline -- has decided the order: no window sort nobody reads)
     const bool deal_by_length = uniform_segments == 0 && n_traj >= 64 && ctx->settings.ragged_window_sort && !d_order_ready && !(d_compact_ready && d_n_active_ready);
-    const size_t b_order = deal_by_length ? length_order_bytes(n_traj) : 0;   // order + histogram + cursors
-    const size_t b_state = sizeof(double) * (size_t)ws_knots * F * (size_t)grid * 64;
     const bool guess = gmode != 0;     // cold start from a starting set (closed form: prep kernel; dual method: corridor_dual_kernel)
-    const size_t b_guess = guess ? align256(sizeof(unsigned long long) * 6 * (size_t)n_traj) : 0;
     const bool masked = d_only_i32 || d_only_u8;
+    Carve c;
+    const int i_xsol = c.add(sizeof(double) * 3 * (size_t)r * (size_t)rows);   // (reserved, never touched while fused_emit = 1: DESIGN.md section 1)
+    const int i_queue = c.add(256);            // the work counter; debug builds: the stamps at + 64 (UAVQP_CORRIDOR_TIMING)
+    const int i_desc = c.add(sizeof(unsigned long long) * 3 * (size_t)n_traj);
+    const LengthOrder i_order = length_order_slots(c, n_traj, deal_by_length);
+    const int i_state = c.add(sizeof(double) * (size_t)ws_knots * F * (size_t)grid * 64, ws_knots > 0);
+    const int i_guess = c.add(sizeof(unsigned long long) * 6 * (size_t)n_traj, guess);
     // compacted dealing order + its length -- reserved whether this solve is masked or not (4 bytes per trajectory): the first masked solve of a
     // pipeline call must not grow the workspace, i.e. stop the stream and re-allocate, in the middle of the loop
-    const size_t b_compact = align256(sizeof(int32_t) * (size_t)n_traj) + 256;
+    const int i_compact = c.add(sizeof(int32_t) * (size_t)n_traj), i_n_active = c.add(256);
     // one lane per trajectory (qp_corridor_lane.h): batches of at most 16 segments per trajectory, G not cached across solves
 #ifdef UAVQP_EXPERIMENTS
     const bool lane_prelude = dual && !(d_gcache && gcache_mode != 0) && Mmax - 1 <= uavqp::LANE_NV && ctx->settings.corridor_prelude_lanes == 1;
     long long lgrid = ((long long)n_traj + 63) / 64;
     if (lgrid > (long long)ctx->num_cus * 4) lgrid = (long long)ctx->num_cus * 4;     // (one wave per SIMD: the register file, not the 27 KB of LDS per wave, sets it)
-    const size_t b_lane = lane_prelude ? align256(sizeof(double) * (size_t)uavqp::lane_scratch_doubles(r) * (size_t)lgrid) : 0;
-#else
-    const size_t b_lane = 0;
+    const int i_lane = c.add(sizeof(double) * (size_t)uavqp::lane_scratch_doubles(r) * (size_t)lgrid, lane_prelude);
 #endif
-    int rc = ensure_ws(ctx, b_xsol + b_queue + b_desc + b_order + b_state + b_guess + b_compact + b_lane);
+    rc = carve_on(ctx->stream, ctx->ws, c);
     if (rc != UAVQP_OK) return rc;
-    a.guess = guess ? (unsigned long long*)((char*)ctx->ws + b_xsol + b_queue + b_desc + b_order + b_state) : nullptr;
+    a.guess = c.at<unsigned long long>(i_guess);
     a.coeff = d_coeff_out;
-    a.xsol = ctx->ws;
-    a.queue = (unsigned int*)((char*)ctx->ws + b_xsol);
+    a.xsol = c.at<double>(i_xsol);
+    a.queue = c.at<unsigned int>(i_queue);
     ctx->dbg_queue = a.queue;
-    a.desc = (unsigned long long*)((char*)ctx->ws + b_xsol + b_queue);
-    a.ws = ws_knots > 0 ? (double*)((char*)ctx->ws + b_xsol + b_queue + b_desc + b_order) : nullptr;
+    a.desc = c.at<unsigned long long>(i_desc);
+    a.ws = c.at<double>(i_state);
     a.ws_knots = ws_knots;
     a.order = d_order_ready;
     if (deal_by_length) {
-        rc = make_length_order(ctx, d_seg_offsets, n_traj, (char*)ctx->ws + b_xsol + b_queue + b_desc, &a.order);
+        rc = make_length_order(ctx, d_seg_offsets, n_traj, c, i_order, &a.order);
         if (rc != UAVQP_OK) return rc;
     }
     a.n_active = nullptr;
@@ -829,8 +799,8 @@ static int corridor_warm_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_seg
         a.order = d_compact_ready;
         a.n_active = d_n_active_ready;
     } else if (masked) {
-        int32_t* d_compact = (int32_t*)((char*)ctx->ws + b_xsol + b_queue + b_desc + b_order + b_state + b_guess);
-        int* d_n_active = (int*)((char*)d_compact + align256(sizeof(int32_t) * (size_t)n_traj));
+        int32_t* d_compact = c.at<int32_t>(i_compact);
+        int* d_n_active = c.at<int>(i_n_active);
         hipLaunchKernelGGL(uavqp::compact_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, a.order, n_traj, d_only_i32, d_only_u8, d_compact, d_n_active);
         a.order = d_compact;
         a.n_active = d_n_active;
@@ -874,7 +844,7 @@ static int corridor_warm_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_seg
         }
 #ifdef UAVQP_EXPERIMENTS
     } else if (lane_prelude) {
-        double* const d_lane = (double*)((char*)ctx->ws + b_xsol + b_queue + b_desc + b_order + b_state + b_guess + b_compact);
+        double* const d_lane = c.at<double>(i_lane);
         if (r == 3) hipLaunchKernelGGL((uavqp::corridor_dual_lane_kernel<3>), dim3((unsigned)lgrid), dim3(64), 0, ctx->stream, a, d_lane, ctx->dual_trips_extra);
         else hipLaunchKernelGGL((uavqp::corridor_dual_lane_kernel<4>), dim3((unsigned)lgrid), dim3(64), 0, ctx->stream, a, d_lane, ctx->dual_trips_extra);
 #endif
@@ -951,7 +921,7 @@ extern "C" int uavqp_debug_corridor_dual(uavqp_ctx* ctx, double* out_64x2048, un
 #ifdef UAVQP_CORRIDOR_TIMING
 // debug build only (tools/corridor_sections.py): cycles wave 0 of the last corridor solve spent per section
 extern "C" int uavqp_debug_corridor_stamps(uavqp_ctx* ctx, long long* out7) {
-    if (!ctx || !out7 || !ctx->ws) return UAVQP_ERR_INVALID_ARG;
+    if (!ctx || !out7 || !ctx->ws.p) return UAVQP_ERR_INVALID_ARG;
     UAVQP_HIP(hipStreamSynchronize(ctx->stream));
     UAVQP_HIP(hipMemcpy(out7, (char*)ctx->dbg_queue + 64, 7 * sizeof(long long), hipMemcpyDeviceToHost));
     return UAVQP_OK;
@@ -1016,16 +986,9 @@ static int rows_batch_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_segmen
     if (uniform_segments == 0 && (!d_seg_offsets || max_segments < 1)) return UAVQP_ERR_INVALID_ARG;
     UAVQP_HIP(hipSetDevice(ctx->device));
     const int Mmax = uniform_segments > 0 ? uniform_segments : max_segments;
-    long long rows = 0;
-    if (uniform_segments > 0) rows = (long long)n_traj * (uniform_segments + 1);
-    else if (total_segments >= 0) rows = total_segments + n_traj;
-    else {   // read once here, handed on to the box phase below
-        int32_t last = 0;
-        UAVQP_HIP(hipMemcpyAsync(&last, d_seg_offsets + n_traj, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        UAVQP_HIP(hipStreamSynchronize(ctx->stream));
-        if (last < 0) return UAVQP_ERR_INVALID_ARG;
-        rows = (long long)last + n_traj;
-    }
+    long long rows = 0;   // (an unknown total is read back once here, handed on to the box phase below)
+    int rc = batch_rows(ctx, n_traj, uniform_segments, total_segments, d_seg_offsets, &rows);
+    if (rc != UAVQP_OK) return rc;
     // Phase 1 (only with knot boxes): the box-only problem on the fast corridor kernel; its working set is where the dual method
     // starts, so that its iterations go into the rows and the few boxes they move instead of re-discovering every active box one
     // constraint per block solve (BASELINE config 3 with K = 2 rows: 34 -> 25 iterations mean, 36 -> 30 ms; uavqp_settings.warm_start = 0
@@ -1040,15 +1003,10 @@ static int rows_batch_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_segmen
     const bool prelude = ctx->settings.corridor_initial_guess == 2 && ctx->settings.warm_start != 0 && pair_kernel &&
                          Mmax >= 2 && (Mmax - 1) + K_ * Mmax <= 48;
     if (warm || prelude) {
-        if ((size_t)n_traj * 6 > ctx->rows_warm_count) {
-            UAVQP_HIP(hipStreamSynchronize(ctx->stream));
-            if (ctx->rows_warm) UAVQP_HIP(hipFree(ctx->rows_warm));
-            ctx->rows_warm = nullptr;
-            ctx->rows_warm_count = 0;
-            UAVQP_HIP(hipMalloc((void**)&ctx->rows_warm, sizeof(uint64_t) * (size_t)n_traj * 6));
-            ctx->rows_warm_count = (size_t)n_traj * 6;
-        }
+        rc = dev_grow(ctx->stream, ctx->rows_warm, sizeof(uint64_t) * (size_t)n_traj * 6);
+        if (rc != UAVQP_OK) return rc;
     }
+    unsigned long long* const d_warm_box = (warm || prelude) ? (unsigned long long*)ctx->rows_warm.p : nullptr;
     const long long total_seg = rows - n_traj;
     const long long pairs = 3LL * n_traj;
     unsigned long long* d_warm_rows = nullptr;
@@ -1058,8 +1016,7 @@ static int rows_batch_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_segmen
     unsigned int* d_queue = nullptr;
     unsigned long long* d_desc = nullptr;
     int32_t* d_status_box = nullptr;
-    double* d_kd = nullptr;
-    size_t b_kd = 0;
+    double *d_kdF = nullptr, *d_kdB = nullptr;
     long long kd_plane = 0;
     uavqp::RowsArgs a;
     a.n_traj = n_traj; a.uniform = uniform_segments; a.max_segments = Mmax;
@@ -1075,37 +1032,31 @@ static int rows_batch_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_segmen
         // re-uses ctx->ws), and rows_prep_kernel is the step's FIRST kernel: validation + permanent masks as before, and with them the row
         // functionals (was rows_gfun_kernel: a second pass over the same rows), the initial status / iteration counts (was fill_i32_kernel + a
         // memset) and the clearing of what the prelude only writes for the trajectories it takes (was two memsets).
-        const size_t b_wr = prelude ? align256(sizeof(uint64_t) * (size_t)n_traj * 3 * 2 * K_) : 0, b_np = prelude ? align256((size_t)n_traj) : 0;
-        const size_t b_ctr = 512;                                                                  // [0, 256): the prelude's counters; [256, 512): the pair kernel's queue
-        const size_t b_gf = align256(sizeof(double) * (size_t)total_seg * K_ * 2 * r);             // row functionals: made once, used by the prelude AND the rows kernel
+        Carve c;
+        const int i_wr = c.add(sizeof(uint64_t) * (size_t)n_traj * 3 * 2 * K_, prelude), i_np = c.add((size_t)n_traj, prelude);
+        const int i_ctr = c.add(512);   // [0, 256): the prelude's counters (its ticket: word 16); [256, 512): the pair kernel's queue
+        const int i_gf = c.add(sizeof(double) * (size_t)total_seg * K_ * 2 * r);                   // row functionals: made once, used by the prelude AND the rows kernel
         // chain records (rows_chain_kernel): two halves, knot-major planes of n_traj (padded to whole waves) rows each, knots 1 .. Mmax - 1 <= 31
         const int kd_planes = Mmax - 1 < 1 ? 1 : (Mmax - 1 > 31 ? 31 : Mmax - 1);
         kd_plane = ((long long)n_traj + 63) / 64 * 64 * uavqp::rows_chain_half_mem(r);
-        b_kd = prelude ? 2 * align256(sizeof(double) * (size_t)kd_planes * (size_t)kd_plane) : 0;
-        const size_t b_desc = align256(sizeof(unsigned long long) * (size_t)pairs * (2 + 2 * K));
-        const size_t b_sb = warm ? align256(sizeof(int32_t) * (size_t)n_traj) : 0;                 // the box phase's statuses (not the step's)
-        const size_t need = b_wr + b_np + b_ctr + b_gf + b_kd + b_desc + b_sb;
-        if (need > ctx->rows_warm2_bytes) {
-            UAVQP_HIP(hipStreamSynchronize(ctx->stream));
-            if (ctx->rows_warm2) UAVQP_HIP(hipFree(ctx->rows_warm2));
-            ctx->rows_warm2 = nullptr;
-            ctx->rows_warm2_bytes = 0;
-            UAVQP_HIP(hipMalloc((void**)&ctx->rows_warm2, need));
-            ctx->rows_warm2_bytes = need;
-        }
-        char* p = (char*)ctx->rows_warm2;
-        d_warm_rows = prelude ? (unsigned long long*)p : nullptr; p += b_wr;
-        d_need_phase1 = prelude ? (unsigned char*)p : nullptr; p += b_np;
-        d_n_phase1 = (unsigned int*)p; d_queue = (unsigned int*)(p + 256); p += b_ctr;
-        d_gfun_pre = (double*)p; p += b_gf;
-        d_kd = (double*)p; p += b_kd;
-        d_desc = (unsigned long long*)p; p += b_desc;
-        d_status_box = warm ? (int32_t*)p : nullptr;
+        const size_t b_kd_half = sizeof(double) * (size_t)kd_planes * (size_t)kd_plane;
+        const int i_kdF = c.add(b_kd_half, prelude), i_kdB = c.add(b_kd_half, prelude);
+        const int i_desc = c.add(sizeof(unsigned long long) * (size_t)pairs * (2 + 2 * K));
+        const int i_sb = c.add(sizeof(int32_t) * (size_t)n_traj, warm);                            // the box phase's statuses (not the step's)
+        rc = carve_on(ctx->stream, ctx->rows_warm2, c);
+        if (rc != UAVQP_OK) return rc;
+        d_warm_rows = c.at<unsigned long long>(i_wr);
+        d_need_phase1 = c.at<unsigned char>(i_np);
+        d_n_phase1 = c.at<unsigned int>(i_ctr); d_queue = (unsigned int*)((char*)d_n_phase1 + 256);
+        d_gfun_pre = c.at<double>(i_gf);
+        d_kdF = c.at<double>(i_kdF); d_kdB = c.at<double>(i_kdB);
+        d_desc = c.at<unsigned long long>(i_desc);
+        d_status_box = c.at<int32_t>(i_sb);
         a.queue = d_queue;
         ctx->dbg_queue = a.queue;
         aa.r = a;
         aa.desc = d_desc; aa.gfun = d_gfun_pre; aa.prep_gfun = 1;
-        aa.init_warm_box = (warm || prelude) ? (unsigned long long*)ctx->rows_warm : nullptr;
+        aa.init_warm_box = d_warm_box;
         aa.init_warm_rows = d_warm_rows;
         aa.init_counters = d_n_phase1;                      // 128 words: the prelude's counters and the queue behind them
         // rows_prep_kernel: four waves per block; two trajectories per wave when none has more than 31 segments (a half-wave's lanes), else one
@@ -1126,14 +1077,14 @@ static int rows_batch_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_segmen
         da.r.seg_offsets = d_seg_offsets; da.r.waypoints = d_waypoints; da.r.times = d_times; da.r.bc = d_bc;
         da.r.corr_lo = d_corr_lo; da.r.corr_hi = d_corr_hi; da.r.row_tau = d_row_tau; da.r.row_deriv = d_row_deriv; da.r.row_lo = d_row_lo; da.r.row_hi = d_row_hi;
         da.order = nullptr;
-        da.warm_box = (unsigned long long*)ctx->rows_warm; da.warm_rows = d_warm_rows; da.need_phase1 = d_need_phase1; da.gfun = d_gfun_pre;
-        da.kdF = d_kd; da.kdB = (const double*)((const char*)d_kd + b_kd / 2); da.kd_plane = kd_plane; da.n_phase1 = d_n_phase1;
+        da.warm_box = d_warm_box; da.warm_rows = d_warm_rows; da.need_phase1 = d_need_phase1; da.gfun = d_gfun_pre;
+        da.kdF = d_kdF; da.kdB = d_kdB; da.kd_plane = kd_plane; da.n_phase1 = d_n_phase1;
         da.ticket = (d_n_phase1 && ctx->deal_tickets) ? d_n_phase1 + 16 : nullptr;      // (the prelude's counter block: zeroed by rows_prep_kernel, the step's first kernel)
         {   // the chain of every trajectory once, one lane each (the prelude's waves would each repeat it in 64 lanes)
             long long cg = ((long long)n_traj + 63) / 64;
             if (cg > (long long)ctx->num_cus * 16) cg = (long long)ctx->num_cus * 16;
-            if (r == 3) hipLaunchKernelGGL((uavqp::rows_chain_kernel<3>), dim3((unsigned)cg), dim3(64), 0, ctx->stream, da.r, d_kd, (double*)((char*)d_kd + b_kd / 2), kd_plane);
-            else hipLaunchKernelGGL((uavqp::rows_chain_kernel<4>), dim3((unsigned)cg), dim3(64), 0, ctx->stream, da.r, d_kd, (double*)((char*)d_kd + b_kd / 2), kd_plane);
+            if (r == 3) hipLaunchKernelGGL((uavqp::rows_chain_kernel<3>), dim3((unsigned)cg), dim3(64), 0, ctx->stream, da.r, d_kdF, d_kdB, kd_plane);
+            else hipLaunchKernelGGL((uavqp::rows_chain_kernel<4>), dim3((unsigned)cg), dim3(64), 0, ctx->stream, da.r, d_kdF, d_kdB, kd_plane);
         }
 #ifdef UAVQP_DUAL_DEBUG
         {
@@ -1157,7 +1108,7 @@ static int rows_batch_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_segmen
         // knot box to start from: the three launches that compacted and solved that list -- empty as a rule -- are gone; need_phase1 is still written,
         // nobody reads it.)  The box phase's statuses are its own: the step's statuses started in rows_prep_kernel.
         const int rc1 = corridor_warm_impl(ctx, r, n_traj, uniform_segments, max_segments, d_seg_offsets, d_waypoints, d_times,
-                                           d_bc, d_corr_lo, d_corr_hi, d_coeff_out, pair_kernel ? d_status_box : d_status_out, nullptr, ctx->rows_warm, 0, rows - n_traj);
+                                           d_bc, d_corr_lo, d_corr_hi, d_coeff_out, pair_kernel ? d_status_box : d_status_out, nullptr, (uint64_t*)d_warm_box, 0, rows - n_traj);
         if (rc1 != UAVQP_OK) return rc1;
     }
 #ifdef UAVQP_DUAL_DEBUG
@@ -1165,14 +1116,13 @@ static int rows_batch_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_segmen
         static unsigned long long* s_box = nullptr;
         static size_t s_box_n = 0;
         if (s_box_n < (size_t)n_traj * 6) { if (s_box) (void)hipFree(s_box); UAVQP_HIP(hipMalloc((void**)&s_box, sizeof(uint64_t) * (size_t)n_traj * 6)); s_box_n = (size_t)n_traj * 6; }
-        UAVQP_HIP(hipMemcpyAsync(s_box, ctx->rows_warm, sizeof(uint64_t) * (size_t)n_traj * 6, hipMemcpyDeviceToDevice, ctx->stream));
+        UAVQP_HIP(hipMemcpyAsync(s_box, d_warm_box, sizeof(uint64_t) * (size_t)n_traj * 6, hipMemcpyDeviceToDevice, ctx->stream));
         ctx->dbg_guess = s_box;
         ctx->dbg_dual = g_rows_dbg;
     }
 #endif
-    a.warm = (warm || prelude) ? (const unsigned long long*)ctx->rows_warm : nullptr;
+    a.warm = d_warm_box;
     a.warm_rows = prelude ? (const unsigned long long*)d_warm_rows : nullptr;
-    int rc;
     if (pair_kernel) {
         // two lanes per problem, sweep state in LDS (qp_rows2.h): 80 KiB per single-wave workgroup = two waves per CU
         const int Fp = Bk * (Bk + 1) / 2 + Bk, NCN = 1 + K;
@@ -1187,31 +1137,23 @@ static int rows_batch_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_segmen
         if (grid > max_grid) grid = max_grid;
         if (grid_v > max_grid_v) grid_v = max_grid_v;
         const bool deal_by_length = uniform_segments == 0 && n_traj >= 64 && ctx->settings.ragged_window_sort;
-        const size_t b_order = deal_by_length ? align256(sizeof(int32_t) * (size_t)n_traj) + 2048 : 0;
         const size_t b_state_g = sizeof(double) * (size_t)ws_knots * Fp * (size_t)grid * 64, b_state_v = prelude ? sizeof(double) * (size_t)ws_knots_v * Fp * (size_t)grid_v * 64 : 0;
-        const size_t b_state = align256(b_state_g > b_state_v ? b_state_g : b_state_v);
-        const size_t b_lam = align256(sizeof(double) * (size_t)kown * 2 * NCN * (size_t)grid * 64);
-        const size_t b_redo = align256(sizeof(unsigned int) * (size_t)pairs);
-        rc = ensure_ws(ctx, 256 + b_order + b_state + b_lam + b_redo);
+        Carve c;
+        (void)c.add(256);   // unused head: no kernel is handed these bytes (the pair kernel's queue is in rows_warm2); kept: the same bytes are asked for
+        const LengthOrder i_order = length_order_slots(c, n_traj, deal_by_length);
+        const int i_state = c.add(b_state_g > b_state_v ? b_state_g : b_state_v);
+        const int i_lam = c.add(sizeof(double) * (size_t)kown * 2 * NCN * (size_t)grid * 64);
+        const int i_redo = c.add(sizeof(unsigned int) * (size_t)pairs);
+        rc = carve_on(ctx->stream, ctx->ws, c);
         if (rc != UAVQP_OK) return rc;
-        char* p = (char*)ctx->ws + 256;
         aa.order = nullptr;
         if (deal_by_length) {
-            int32_t* d_order = (int32_t*)p;
-            int* d_hist = (int*)(p + b_order - 2048);
-            int* d_cursor = d_hist + 256;
-            UAVQP_HIP(hipMemsetAsync(d_hist, 0, 256 * sizeof(int), ctx->stream));
-            int sg = (n_traj + 255) / 256;
-            if (sg > ctx->num_cus * 4) sg = ctx->num_cus * 4;
-            hipLaunchKernelGGL(uavqp::seg_hist_kernel, dim3(sg), dim3(256), 0, ctx->stream, d_seg_offsets, n_traj, d_hist);
-            hipLaunchKernelGGL(uavqp::seg_scan_kernel, dim3(1), dim3(256), 0, ctx->stream, d_hist, d_cursor);
-            hipLaunchKernelGGL(uavqp::seg_scatter_kernel, dim3(sg), dim3(256), 0, ctx->stream, d_seg_offsets, n_traj, d_cursor, d_order);
-            aa.order = d_order;
+            rc = make_length_order(ctx, d_seg_offsets, n_traj, c, i_order, &aa.order);
+            if (rc != UAVQP_OK) return rc;
         }
-        p += b_order;
-        a.ws = (double*)p; p += b_state;
-        aa.lam = (double*)p; p += b_lam;
-        aa.redo = (unsigned int*)p;
+        a.ws = c.at<double>(i_state);
+        aa.lam = c.at<double>(i_lam);
+        aa.redo = c.at<unsigned int>(i_redo);
         aa.ws_knots = ws_knots;
         aa.lam_knots = kown;
         aa.coeff = d_coeff_out;                                 // the pair kernels write the polynomials themselves: no xsol, no emission launch
@@ -1243,15 +1185,16 @@ static int rows_batch_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_segmen
         else UAVQP_ROWS2(4, 2);
 #undef UAVQP_ROWS2
     } else {
-        const size_t b_xsol = align256(sizeof(double) * 3 * (size_t)r * (size_t)rows);
         const int F = Bk * (Bk + 1) / 2 + Bk + 2 * (1 + K);   // must match rows_solve_kernel's state layout
         long long grid = (3LL * n_traj + 63) / 64;
         const long long max_grid = (long long)ctx->num_cus * 4;
         if (grid > max_grid) grid = max_grid;
-        const size_t b_state = sizeof(double) * (size_t)Mmax * F * (size_t)grid * 64;
-        rc = ensure_ws(ctx, b_xsol + 256 + b_state);
+        Carve c;
+        const int i_xsol = c.add(sizeof(double) * 3 * (size_t)r * (size_t)rows), i_queue = c.add(256);
+        const int i_state = c.add(sizeof(double) * (size_t)Mmax * F * (size_t)grid * 64);
+        rc = carve_on(ctx->stream, ctx->ws, c);
         if (rc != UAVQP_OK) return rc;
-        a.xsol = ctx->ws; a.queue = (unsigned int*)((char*)ctx->ws + b_xsol); a.ws = (double*)((char*)ctx->ws + b_xsol + 256);
+        a.xsol = c.at<double>(i_xsol); a.queue = c.at<unsigned int>(i_queue); a.ws = c.at<double>(i_state);
         UAVQP_HIP(hipMemsetAsync(a.queue, 0, 256, ctx->stream));
         hipLaunchKernelGGL(uavqp::fill_i32_kernel, dim3((n_traj + 255) / 256), dim3(256), 0, ctx->stream, d_status_out, n_traj, (int32_t)UAVQP_SOLVED);
         if (d_iters_out) UAVQP_HIP(hipMemsetAsync(d_iters_out, 0, sizeof(int32_t) * (size_t)n_traj, ctx->stream));
@@ -1265,7 +1208,7 @@ static int rows_batch_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform_segmen
         // Hermite solution -> coefficients (the corridor solver's emission kernel; it reads the same fields) -- the one-lane cross-check kernel only
         uavqp::CorridorArgs e{};
         e.n_traj = n_traj; e.uniform = uniform_segments; e.max_segments = Mmax; e.seg_offsets = d_seg_offsets; e.waypoints = d_waypoints;
-        e.times = d_times; e.bc = d_bc; e.coeff = d_coeff_out; e.status = d_status_out; e.xsol = ctx->ws;
+        e.times = d_times; e.bc = d_bc; e.coeff = d_coeff_out; e.status = d_status_out; e.xsol = a.xsol;
         const long long chunks = 3LL * (rows - n_traj);
         long long egrid = (chunks + 255) / 256;
         if (egrid > (long long)ctx->num_cus * 16) egrid = (long long)ctx->num_cus * 16;
@@ -1612,25 +1555,20 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
         // clearance so far does not bound what farther points could change are re-sorted by the radius it implies and scan exactly that -- identical boxes.
         const double rmax = robot_r > robot_h ? robot_r : robot_h, rmin = robot_r > robot_h ? robot_h : robot_r;
         a.reach = rmax * (1.0 + 3.0 * h_max / rmin) * (1.0 + 1e-9) + 1e-9;
-        const size_t b_cg = 256, b_h = align256(sizeof(int32_t) * (uavqp::CLOUD2D_MAX_CELLS + 2));
-        const size_t b_h2 = align256(sizeof(int32_t) * ((size_t)uavqp::CLOUD2D_BUCKETS * uavqp::CLOUD2D_MAX_CELLS + 2));
-        const size_t b_pts = align256(sizeof(double) * 3 * (size_t)n_obs), b_perm = align256(sizeof(int32_t) * (size_t)n_rows), b_m = align256(sizeof(double) * (size_t)n_rows);
-        const int rc = ensure_ws(ctx, b_cg + 4 * b_h + 2 * b_h2 + b_pts + 4 * b_perm + b_m);
+        const size_t b_h = sizeof(int32_t) * (uavqp::CLOUD2D_MAX_CELLS + 2), b_h2 = align256(sizeof(int32_t) * ((size_t)uavqp::CLOUD2D_BUCKETS * uavqp::CLOUD2D_MAX_CELLS + 2));
+        const size_t b_perm = sizeof(int32_t) * (size_t)n_rows;
+        Carve c;
+        const int i_cg = c.add(256), i_pstart = c.add(b_h), i_pcur = c.add(b_h), i_rstart = c.add(b_h), i_rcur = c.add(b_h);
+        const int i_hist2 = c.add(b_h2), i_cur2 = c.add(b_h2), i_pts = c.add(sizeof(double) * 3 * (size_t)n_obs);
+        const int i_perm = c.add(b_perm), i_rbin = c.add(b_perm), i_rkey = c.add(b_perm), i_perm2 = c.add(b_perm), i_rm = c.add(sizeof(double) * (size_t)n_rows);
+        const int rc = carve_on(ctx->stream, ctx->ws, c);
         if (rc != UAVQP_OK) return rc;
-        char* p = (char*)ctx->ws;
-        uavqp::Cloud2D* d_cg = (uavqp::Cloud2D*)p; p += b_cg;
-        int32_t* d_pstart = (int32_t*)p; p += b_h;
-        int32_t* d_pcur = (int32_t*)p; p += b_h;
-        int32_t* d_rstart = (int32_t*)p; p += b_h;
-        int32_t* d_rcur = (int32_t*)p; p += b_h;
-        int32_t* d_hist2 = (int32_t*)p; p += b_h2;
-        int32_t* d_cur2 = (int32_t*)p; p += b_h2;
-        double* d_pts = (double*)p; p += b_pts;
-        int32_t* d_perm = (int32_t*)p; p += b_perm;
-        int32_t* d_rbin = (int32_t*)p; p += b_perm;
-        int32_t* d_rkey = (int32_t*)p; p += b_perm;
-        int32_t* d_perm2 = (int32_t*)p; p += b_perm;
-        double* d_rm = (double*)p;
+        uavqp::Cloud2D* d_cg = c.at<uavqp::Cloud2D>(i_cg);
+        int32_t *d_pstart = c.at<int32_t>(i_pstart), *d_pcur = c.at<int32_t>(i_pcur), *d_rstart = c.at<int32_t>(i_rstart), *d_rcur = c.at<int32_t>(i_rcur);
+        int32_t *d_hist2 = c.at<int32_t>(i_hist2), *d_cur2 = c.at<int32_t>(i_cur2);
+        double* d_pts = c.at<double>(i_pts);
+        int32_t *d_perm = c.at<int32_t>(i_perm), *d_rbin = c.at<int32_t>(i_rbin), *d_rkey = c.at<int32_t>(i_rkey), *d_perm2 = c.at<int32_t>(i_perm2);
+        double* d_rm = c.at<double>(i_rm);
         long long sgrid = ((long long)n_obs + n_rows + 511) / 512;
         if (sgrid > (long long)ctx->num_cus * 2) sgrid = (long long)ctx->num_cus * 2;
         UAVQP_HIP(hipMemsetAsync(d_hist2, 0, b_h2, ctx->stream));
@@ -1657,19 +1595,17 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
         // as the clearance found bounds what farther points could still change (cloud_grid2d.h) -- identical boxes, a fraction of the pairs.
         const double rmax = robot_r > robot_h ? robot_r : robot_h, rmin = robot_r > robot_h ? robot_h : robot_r;
         a.reach = rmax * (1.0 + 3.0 * h_max / rmin) * (1.0 + 1e-9) + 1e-9;
-        const size_t b_cg = 256, b_h = align256(sizeof(int32_t) * (uavqp::CLOUD2D_MAX_CELLS + 1));
-        const size_t b_pts = align256(sizeof(double) * 3 * (size_t)n_obs), b_perm = align256(sizeof(int32_t) * (size_t)n_rows);
-        const int rc = ensure_ws(ctx, b_cg + 4 * b_h + b_pts + b_perm);
+        const size_t b_h = sizeof(int32_t) * (uavqp::CLOUD2D_MAX_CELLS + 1);
+        Carve c;
+        const int i_cg = c.add(256), i_pstart = c.add(b_h), i_pcur = c.add(b_h), i_rstart = c.add(b_h), i_rcur = c.add(b_h);
+        const int i_pts = c.add(sizeof(double) * 3 * (size_t)n_obs), i_perm = c.add(sizeof(int32_t) * (size_t)n_rows);
+        const int rc = carve_on(ctx->stream, ctx->ws, c);
         if (rc != UAVQP_OK) return rc;
-        char* p = (char*)ctx->ws;
-        uavqp::Cloud2D* d_cg = (uavqp::Cloud2D*)p;
-        unsigned int* d_phase = (unsigned int*)(p + 128); p += b_cg;
-        int32_t* d_pstart = (int32_t*)p; p += b_h;
-        int32_t* d_pcur = (int32_t*)p; p += b_h;
-        int32_t* d_rstart = (int32_t*)p; p += b_h;
-        int32_t* d_rcur = (int32_t*)p; p += b_h;
-        double* d_pts = (double*)p; p += b_pts;
-        int32_t* d_perm = (int32_t*)p;
+        uavqp::Cloud2D* d_cg = c.at<uavqp::Cloud2D>(i_cg);
+        unsigned int* d_phase = (unsigned int*)((char*)d_cg + 128);   // (probe builds: blocks per ring, in the grid record's slot)
+        int32_t *d_pstart = c.at<int32_t>(i_pstart), *d_pcur = c.at<int32_t>(i_pcur), *d_rstart = c.at<int32_t>(i_rstart), *d_rcur = c.at<int32_t>(i_rcur);
+        double* d_pts = c.at<double>(i_pts);
+        int32_t* d_perm = c.at<int32_t>(i_perm);
         long long sgrid = ((long long)n_obs + n_rows + 511) / 512;
         if (sgrid > (long long)ctx->num_cus * 2) sgrid = (long long)ctx->num_cus * 2;
 #ifdef UAVQP_CLOUD_STATS
@@ -1699,19 +1635,16 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
     if (windowed) {
         const double rmax = robot_r > robot_h ? robot_r : robot_h, rmin = robot_r > robot_h ? robot_h : robot_r;
         a.reach = rmax * (1.0 + 3.0 * h_max / rmin) * (1.0 + 1e-9) + 1e-9;
-        const size_t b_cs = 256, b_ph = align256(sizeof(int32_t) * (uavqp::CLOUD_PT_BINS + 1)), b_rh = align256(sizeof(int32_t) * (uavqp::CLOUD_ROW_BINS + 2));
-        const size_t b_pts = align256(sizeof(double) * 3 * (size_t)n_obs), b_perm = align256(sizeof(int32_t) * (size_t)n_rows);
-        const int rc = ensure_ws(ctx, b_cs + 2 * b_ph + 2 * b_rh + b_pts + 2 * b_perm);
+        const size_t b_ph = sizeof(int32_t) * (uavqp::CLOUD_PT_BINS + 1), b_rh = sizeof(int32_t) * (uavqp::CLOUD_ROW_BINS + 2), b_perm = sizeof(int32_t) * (size_t)n_rows;
+        Carve c;
+        const int i_cs = c.add(256), i_pstart = c.add(b_ph), i_pcur = c.add(b_ph), i_rstart = c.add(b_rh), i_rcur = c.add(b_rh);
+        const int i_pts = c.add(sizeof(double) * 3 * (size_t)n_obs), i_perm = c.add(b_perm), i_rbin = c.add(b_perm);
+        const int rc = carve_on(ctx->stream, ctx->ws, c);
         if (rc != UAVQP_OK) return rc;
-        char* p = (char*)ctx->ws;
-        uavqp::CloudSort* d_cs = (uavqp::CloudSort*)p; p += b_cs;
-        int32_t* d_pstart = (int32_t*)p; p += b_ph;
-        int32_t* d_pcur = (int32_t*)p; p += b_ph;
-        int32_t* d_rstart = (int32_t*)p; p += b_rh;
-        int32_t* d_rcur = (int32_t*)p; p += b_rh;
-        double* d_pts = (double*)p; p += b_pts;
-        int32_t* d_perm = (int32_t*)p; p += b_perm;
-        int32_t* d_rbin = (int32_t*)p;
+        uavqp::CloudSort* d_cs = c.at<uavqp::CloudSort>(i_cs);
+        int32_t *d_pstart = c.at<int32_t>(i_pstart), *d_pcur = c.at<int32_t>(i_pcur), *d_rstart = c.at<int32_t>(i_rstart), *d_rcur = c.at<int32_t>(i_rcur);
+        double* d_pts = c.at<double>(i_pts);
+        int32_t *d_perm = c.at<int32_t>(i_perm), *d_rbin = c.at<int32_t>(i_rbin);
         long long sgrid = ((long long)n_obs + n_rows + 511) / 512;   // every block: one contiguous slice of the keys, bins counted in LDS
         if (sgrid > (long long)ctx->num_cus * 2) sgrid = (long long)ctx->num_cus * 2;
         hipLaunchKernelGGL(uavqp::cloud_sort_setup_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_obstacles, n_obs, a.reach, d_cs, d_pstart, d_rstart);

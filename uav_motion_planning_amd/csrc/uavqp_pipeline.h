@@ -492,20 +492,13 @@ __global__ __launch_bounds__(256) void pipe_rows_count_kernel(long long n_slots,
 
 }  // namespace uavqp
 
-static int ensure_pipe_ws(uavqp_ctx* ctx, size_t bytes) {
-    // counter block [0] + the ring of per-round words [at 256 bytes]; host-coherent: the device writes a round's word while the stream runs on
-    if (!ctx->h_pipe) {
-        UAVQP_HIP(hipHostMalloc(&ctx->h_pipe, 1024, hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(ctx->h_pipe, 0, 1024);
-    }
-    if (bytes <= ctx->pipe_bytes) return UAVQP_OK;
-    UAVQP_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->d_pipe) UAVQP_HIP(hipFree(ctx->d_pipe));
-    ctx->d_pipe = nullptr;
-    ctx->pipe_bytes = 0;
-    UAVQP_HIP(hipMalloc(&ctx->d_pipe, bytes));
-    ctx->pipe_bytes = bytes;
-    return UAVQP_OK;
+// the pinned page the pipeline's counters are read through: counter block [0] + the ring of per-round words [at 256 bytes];
+// host-coherent: the device writes a round's word while the stream runs on
+static int ensure_h_pipe(uavqp_ctx* ctx) {
+    if (ctx->h_pipe) return UAVQP_OK;
+    UAVQP_HIP(hipHostMalloc(&ctx->h_pipe, 1024, hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(ctx->h_pipe, 0, 1024);
+    return dev_grow(ctx->stream, ctx->pipe, 256);   // (as ever: a ctx's first call asks for the counter block alone, then for the layout below)
 }
 
 extern "C" void uavqp_default_pipeline_params(uavqp_pipeline_params* p) {
@@ -595,7 +588,8 @@ static int corridor_pipeline_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform
     // every workspace below is sized from the caller's total_segments: it is checked against the last CSR offset on the device
     // before anything that depends on it is launched.  The word travels through the host-coherent page (await_word below) while the
     // kernels that only look at seg_offsets[0..n] -- the dealing order, the counter reset -- already run.
-    if (!ctx->h_pipe) { const int rc0 = ensure_pipe_ws(ctx, 256); if (rc0 != UAVQP_OK) return rc0; }
+    int rc = ensure_h_pipe(ctx);
+    if (rc != UAVQP_OK) return rc;
     volatile unsigned long long* const h_words = (volatile unsigned long long*)((char*)ctx->h_pipe + 256);   // [0..3] round counts, [4] this check
     unsigned long long* d_words = nullptr;
     UAVQP_HIP(hipHostGetDevicePointer((void**)&d_words, (void*)h_words, 0));
@@ -607,70 +601,51 @@ static int corridor_pipeline_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform
     const int n_rows = total_segments + n_traj;
     const bool checking = P.check_samples > 0;
 
-    // scratch: [counters 64 B][iters n][changed n][first_hit n][active n x 6 x 8][roomy n][flag n][dealing order of the corridor solves]
-    const size_t o_it = 256, o_ch = o_it + align256(sizeof(int32_t) * (size_t)n), o_fh = o_ch + align256(sizeof(int32_t) * (size_t)n);
-    const size_t o_as = o_fh + align256(sizeof(int32_t) * (size_t)n), o_rm = o_as + align256(sizeof(uint64_t) * 6 * (size_t)n);
-    const size_t o_fl = o_rm + align256((size_t)n), o_or = o_fl + align256((size_t)n);
     const bool deal_by_length = uni == 0 && n >= 64 && ctx->settings.ragged_window_sort;
     // G of the dual prelude across the rounds (the re-allocation multiplies all durations of a trajectory by one factor: G only rescales)
     const bool g_across = ctx->settings.corridor_initial_guess == 2 && mx - 1 <= 24 && mx >= 2;
-    const size_t o_cp = o_or + (deal_by_length ? length_order_bytes(n) : 0);          // compacted dealing order of the next re-solve + its count
     const int cblocks = (n + uavqp::COMPACT_BLOCK - 1) / uavqp::COMPACT_BLOCK;           // workgroups of a compaction (more than one: two launches)
     if (cblocks > 1024) { g_last_error = "uavqp_corridor_pipeline_device: more than 16 777 216 trajectories in one call"; return UAVQP_ERR_INVALID_ARG; }
-    // (two lists: round k compacts round k - 1's into the other one; then their two counts and the per-workgroup counts of a large compaction)
-    const size_t o_sc = o_cp + 2 * align256(sizeof(int32_t) * (size_t)n) + 256 + align256(sizeof(int) * (size_t)cblocks);
-    const size_t o_gc = o_sc + (g_across ? align256(sizeof(double) * (size_t)n) : 0);
-    const size_t o_rw = o_gc + (g_across ? align256(sizeof(double) * (size_t)n * uavqp::corridor_gcache_stride) : 0);
+    const size_t nt_ = (size_t)n, ts_ = (size_t)total_segments, b_i32n = sizeof(int32_t) * nt_, b_wp = sizeof(double) * 3 * (ts_ + nt_);
+    Carve c;
+    const int i_cnt = c.add(256), i_it = c.add(b_i32n), i_ch = c.add(b_i32n), i_fh = c.add(b_i32n), i_as = c.add(sizeof(uint64_t) * 6 * nt_);
+    const int i_rm = c.add(nt_), i_fl = c.add(nt_);
+    const LengthOrder i_or = length_order_slots(c, n, deal_by_length);      // dealing order of the corridor solves
+    // compacted dealing order of the next re-solve (two lists: round k compacts round k - 1's into the other one), then their two counts
+    // (words 0 and 32 of one slot) and the per-workgroup counts of a large compaction
+    const int i_cp[2] = {c.add(b_i32n), c.add(b_i32n)}, i_na = c.add(256), i_cblk = c.add(sizeof(int) * (size_t)cblocks);
+    const int i_sc = c.add(sizeof(double) * nt_, g_across), i_gc = c.add(sizeof(double) * nt_ * uavqp::corridor_gcache_stride, g_across);
     // rows repair: per-sample flags of the check, new rows per trajectory, slots placed this round, the sub-batch (list, CSR offsets,
     // inputs, rows, outputs) -- sized for the whole batch
-    const size_t ns_ = (size_t)(checking ? P.check_samples : 0), nt_ = (size_t)n, ts_ = (size_t)total_segments, tr_ = ts_ + nt_;
-    const size_t rw_sz[] = {align256(nt_ * ns_), align256(sizeof(int32_t) * nt_), align256(ts_), 2 * align256(sizeof(int32_t) * (nt_ + 1)),
-                            3 * align256(sizeof(double) * 3 * tr_), align256(sizeof(double) * ts_), align256(sizeof(double) * nt_ * 2 * (r - 1) * 3),
-                            align256(sizeof(double) * 2 * ts_), align256(sizeof(int32_t) * 2 * ts_), 2 * align256(sizeof(double) * 6 * ts_),
-                            align256(sizeof(double) * 3 * 2 * r * ts_), 4 * align256(sizeof(int32_t) * nt_)};
-    size_t rw_total = 0;
-    if (rows_mode)
-        for (size_t x : rw_sz) rw_total += x;
-    const size_t need = o_rw + rw_total;
-    int rc = ensure_pipe_ws(ctx, need);
+    const bool rm = rows_mode;
+    const int i_sflags = c.add(nt_ * (size_t)(checking ? P.check_samples : 0), rm), i_newrows = c.add(b_i32n, rm), i_placed = c.add(ts_, rm);
+    const int i_glist = c.add(sizeof(int32_t) * (nt_ + 1), rm), i_goff = c.add(sizeof(int32_t) * (nt_ + 1), rm);
+    const int i_gwp = c.add(b_wp, rm), i_glo = c.add(b_wp, rm), i_ghi = c.add(b_wp, rm), i_gT = c.add(sizeof(double) * ts_, rm);
+    const int i_gbc = c.add(sizeof(double) * nt_ * 2 * (r - 1) * 3, rm), i_gtau = c.add(sizeof(double) * 2 * ts_, rm), i_gdrv = c.add(sizeof(int32_t) * 2 * ts_, rm);
+    const int i_grlo = c.add(sizeof(double) * 6 * ts_, rm), i_grhi = c.add(sizeof(double) * 6 * ts_, rm), i_gco = c.add(sizeof(double) * 3 * 2 * r * ts_, rm);
+    const int i_gst1 = c.add(b_i32n, rm), i_gst2 = c.add(b_i32n, rm), i_git = c.add(b_i32n, rm), i_gch = c.add(b_i32n, rm);
+    rc = carve_on(ctx->stream, ctx->pipe, c);
     if (rc != UAVQP_OK) return rc;
-    char* base = (char*)ctx->d_pipe;
-    uavqp::PipeCounters* d_cnt = (uavqp::PipeCounters*)base;
-    int32_t* d_iters = (int32_t*)(base + o_it);
-    int32_t* d_changed = (int32_t*)(base + o_ch);
-    int32_t* d_fh = d_first_hit ? d_first_hit : (int32_t*)(base + o_fh);
-    uint64_t* d_active = (uint64_t*)(base + o_as);
-    int32_t* const d_cp2[2] = {(int32_t*)(base + o_cp), (int32_t*)(base + o_cp + align256(sizeof(int32_t) * (size_t)n))};
-    int* const d_na2[2] = {(int*)(base + o_cp + 2 * align256(sizeof(int32_t) * (size_t)n)), (int*)(base + o_cp + 2 * align256(sizeof(int32_t) * (size_t)n)) + 32};
-    int* const d_cblk = (int*)(base + o_cp + 2 * align256(sizeof(int32_t) * (size_t)n) + 256);
+    uavqp::PipeCounters* d_cnt = c.at<uavqp::PipeCounters>(i_cnt);
+    int32_t* d_iters = c.at<int32_t>(i_it);
+    int32_t* d_changed = c.at<int32_t>(i_ch);
+    int32_t* d_fh = d_first_hit ? d_first_hit : c.at<int32_t>(i_fh);
+    uint64_t* d_active = c.at<uint64_t>(i_as);
+    int32_t* const d_cp2[2] = {c.at<int32_t>(i_cp[0]), c.at<int32_t>(i_cp[1])};
+    int* const d_na2[2] = {c.at<int>(i_na), c.at<int>(i_na) + 32};
+    int* const d_cblk = c.at<int>(i_cblk);
     int cur_list = 0;                                                                  // the list the next re-solve takes
-    double* d_scale = g_across ? (double*)(base + o_sc) : nullptr;     // factor by which every trajectory was stretched since its G was stored
-    double* d_gcache = g_across ? (double*)(base + o_gc) : nullptr;
+    double* d_scale = c.at<double>(i_sc);     // factor by which every trajectory was stretched since its G was stored
+    double* d_gcache = c.at<double>(i_gc);
     int solves_done = 0;
-    uint8_t* d_roomy = (uint8_t*)(base + o_rm);
-    uint8_t* d_flag = (uint8_t*)(base + o_fl);
+    uint8_t* d_roomy = c.at<uint8_t>(i_rm);
+    uint8_t* d_flag = c.at<uint8_t>(i_fl);
     uavqp::PipeCounters* h_cnt = (uavqp::PipeCounters*)ctx->h_pipe;
-    char* rp = base + o_rw;
-    auto take = [&](size_t bytes) { char* q = rp; rp += bytes; return q; };
-    uint8_t* d_sflags = rows_mode ? (uint8_t*)take(rw_sz[0]) : nullptr;
-    int32_t* d_newrows = rows_mode ? (int32_t*)take(rw_sz[1]) : nullptr;
-    uint8_t* d_placed = rows_mode ? (uint8_t*)take(rw_sz[2]) : nullptr;
-    int32_t* d_glist = rows_mode ? (int32_t*)take(rw_sz[3] / 2) : nullptr;
-    int32_t* d_goff = rows_mode ? (int32_t*)take(rw_sz[3] / 2) : nullptr;
-    double* d_gwp = rows_mode ? (double*)take(rw_sz[4] / 3) : nullptr;
-    double* d_glo = rows_mode ? (double*)take(rw_sz[4] / 3) : nullptr;
-    double* d_ghi = rows_mode ? (double*)take(rw_sz[4] / 3) : nullptr;
-    double* d_gT = rows_mode ? (double*)take(rw_sz[5]) : nullptr;
-    double* d_gbc = rows_mode ? (double*)take(rw_sz[6]) : nullptr;
-    double* d_gtau = rows_mode ? (double*)take(rw_sz[7]) : nullptr;
-    int32_t* d_gdrv = rows_mode ? (int32_t*)take(rw_sz[8]) : nullptr;
-    double* d_grlo = rows_mode ? (double*)take(rw_sz[9] / 2) : nullptr;
-    double* d_grhi = rows_mode ? (double*)take(rw_sz[9] / 2) : nullptr;
-    double* d_gco = rows_mode ? (double*)take(rw_sz[10]) : nullptr;
-    int32_t* d_gst1 = rows_mode ? (int32_t*)take(rw_sz[11] / 4) : nullptr;
-    int32_t* d_gst2 = rows_mode ? (int32_t*)take(rw_sz[11] / 4) : nullptr;
-    int32_t* d_git = rows_mode ? (int32_t*)take(rw_sz[11] / 4) : nullptr;
-    int32_t* d_gch = rows_mode ? (int32_t*)take(rw_sz[11] / 4) : nullptr;
+    uint8_t *d_sflags = c.at<uint8_t>(i_sflags), *d_placed = c.at<uint8_t>(i_placed);
+    int32_t *d_newrows = c.at<int32_t>(i_newrows), *d_glist = c.at<int32_t>(i_glist), *d_goff = c.at<int32_t>(i_goff);
+    double *d_gwp = c.at<double>(i_gwp), *d_glo = c.at<double>(i_glo), *d_ghi = c.at<double>(i_ghi), *d_gT = c.at<double>(i_gT), *d_gbc = c.at<double>(i_gbc);
+    double *d_gtau = c.at<double>(i_gtau), *d_grlo = c.at<double>(i_grlo), *d_grhi = c.at<double>(i_grhi), *d_gco = c.at<double>(i_gco);
+    int32_t *d_gdrv = c.at<int32_t>(i_gdrv), *d_gst1 = c.at<int32_t>(i_gst1), *d_gst2 = c.at<int32_t>(i_gst2), *d_git = c.at<int32_t>(i_git), *d_gch = c.at<int32_t>(i_gch);
     int cgrid = (n + 255) / 256;
     if (cgrid > ctx->num_cus * 8) cgrid = ctx->num_cus * 8;
 
@@ -683,7 +658,7 @@ static int corridor_pipeline_impl(uavqp_ctx* ctx, int r, int n_traj, int uniform
     // every corridor solve of the call deals the same trajectories: their order by segment count is made once
     const int32_t* d_order = nullptr;
     if (deal_by_length) {
-        rc = make_length_order(ctx, d_seg_offsets, n, base + o_or, &d_order);
+        rc = make_length_order(ctx, d_seg_offsets, n, c, i_or, &d_order);
         if (rc != UAVQP_OK) return rc;
     }
     // Re-solves take only the trajectories whose problem changed since their last solve -- durations stretched by the re-allocation

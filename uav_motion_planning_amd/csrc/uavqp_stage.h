@@ -1,4 +1,4 @@
-// uavqp_stage.h -- what every host-pointer entry point of include/uavqp.h shares (included by uavqp.hip behind ensure_stage /
+// uavqp_stage.h -- what every host-pointer entry point of include/uavqp.h shares (included by uavqp.hip behind uavqp_ws.h and
 // ensure_mapped): the shape of a batch from its CSR offsets, and the layout of the staging buffer.  An entry point declares each of its
 // arrays ONCE (Stage::in / out / inout / scratch), then calls stage_begin, its device implementation and stage_end:
 //     uploads, clears -> device entry -> downloads -> one stream synchronisation, all on the ctx's stream.
@@ -41,27 +41,22 @@ static int await_mapped_page(uavqp_ctx* ctx, const char* who) {
     return await_host_word(ctx->stream, h_word, seq, nullptr, who);
 }
 
-// The sub-buffers of one call, laid out in the order they are declared; each starts on a 256-byte boundary (the specialised kernels are
-// chosen only for 16-byte aligned arrays).  A declaration returns the slot's index for at<T>(); index -1 (an array this call does not
-// have) gives a null pointer.  The pointers are good for this call only: a later call may free the buffer (ensure_stage).
+// The arrays of one call: where each lies is the carver's business (uavqp_ws.h: declaration order, 256-byte boundaries, handle -1 = an
+// array this call does not have = a null pointer); Stage adds what is copied where.  The pointers are good for this call only.
 struct Stage {
-    static constexpr int CAP = 16;
     struct Slot {
         const void* src;   // copied host -> device before the device entry (null: nothing to upload)
         void* dst;         // copied device -> host behind it (null: the caller does not want it, or device-only scratch)
-        size_t bytes, offset;
+        size_t bytes;
         bool clear;
-    } slot[CAP];
-    int n = 0;
-    size_t total = 0;
-    char* base = nullptr;   // device view of the buffer
-    char* page = nullptr;   // mapped route only: host view of the same bytes
+    } slot[Carve::CAP];
+    Carve lay;    // device view of the buffer
+    Carve page;   // mapped route only (else unplaced): host view of the same bytes
 
     int add(const void* src, void* dst, size_t bytes, bool clear) {
-        if (n >= CAP) return n = CAP + 1, -1;   // (stage_begin refuses the call)
-        slot[n] = Slot{src, dst, bytes, total, clear};
-        total += align256(bytes);
-        return n++;
+        const int i = lay.add(bytes);   // (-1: over the capacity, stage_begin refuses the call)
+        if (i >= 0) slot[i] = Slot{src, dst, bytes, clear};
+        return i;
     }
     int in(const void* src, size_t bytes) { return add(src, nullptr, bytes, false); }
     // clear: the kernels leave a failed trajectory unwritten and the buffer is reused -- cleared first, it comes back as zeros, never as
@@ -70,39 +65,43 @@ struct Stage {
     int inout(void* both, size_t bytes) { return add(both, both, bytes, false); }
     int scratch(size_t bytes) { return add(nullptr, nullptr, bytes, false); }
     template <class T>
-    T* at(int i) const { return i < 0 ? nullptr : (T*)(base + slot[i].offset); }
+    T* at(int i) const { return lay.at<T>(i); }
 };
 
 // mapped: the latency route -- the batch lives in the pinned page that is mapped into the device (behind MAPPED_HEAD: the completion
 // word has a FIXED slot no payload ever aliases), an upload is a memcpy into the page and the kernels work over the host link.
 static int stage_begin(uavqp_ctx* ctx, Stage& st, bool mapped = false) {
-    if (st.n > Stage::CAP) { g_last_error = "host entry: more staging slots than Stage::CAP"; return UAVQP_ERR_ALLOC; }
-    const int rc = mapped ? ensure_mapped(ctx, st.total + MAPPED_HEAD) : ensure_stage(ctx, st.total);
+    if (st.lay.overflow()) { g_last_error = "host entry: more staging slots than Carve::CAP"; return UAVQP_ERR_ALLOC; }
+    const int rc = mapped ? ensure_mapped(ctx, st.lay.total + MAPPED_HEAD) : carve_on(ctx->stream, ctx->stage, st.lay);
     if (rc != UAVQP_OK) return rc;
-    st.base = mapped ? (char*)ctx->d_axis + MAPPED_HEAD : (char*)ctx->d_stage;
-    st.page = mapped ? (char*)ctx->h_axis + MAPPED_HEAD : nullptr;
-    for (int i = 0; i < st.n; ++i) {
+    if (mapped) {
+        st.lay.place((char*)ctx->d_axis + MAPPED_HEAD);
+        st.page = st.lay;
+        st.page.place((char*)ctx->h_axis + MAPPED_HEAD);
+    }
+    for (int i = 0; i < st.lay.n; ++i) {
         const Stage::Slot& q = st.slot[i];
         if (q.bytes == 0) continue;
-        if (q.src && mapped) std::memcpy(st.page + q.offset, q.src, q.bytes);
-        else if (q.src) UAVQP_HIP(hipMemcpyAsync(st.base + q.offset, q.src, q.bytes, hipMemcpyHostToDevice, ctx->stream));
-        if (q.clear && mapped) std::memset(st.page + q.offset, 0, q.bytes);
-        else if (q.clear) UAVQP_HIP(hipMemsetAsync(st.base + q.offset, 0, q.bytes, ctx->stream));
+        if (q.src && mapped) std::memcpy(st.page.at<char>(i), q.src, q.bytes);
+        else if (q.src) UAVQP_HIP(hipMemcpyAsync(st.lay.at<char>(i), q.src, q.bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (q.clear && mapped) std::memset(st.page.at<char>(i), 0, q.bytes);
+        else if (q.clear) UAVQP_HIP(hipMemsetAsync(st.lay.at<char>(i), 0, q.bytes, ctx->stream));
     }
     return UAVQP_OK;
 }
 
 static int stage_end(uavqp_ctx* ctx, const Stage& st, const char* who) {
-    if (st.page) {
+    const bool mapped = st.page.base != nullptr;
+    if (mapped) {
         const int rc = await_mapped_page(ctx, who);
         if (rc != UAVQP_OK) return rc;
     }
-    for (int i = 0; i < st.n; ++i) {
+    for (int i = 0; i < st.lay.n; ++i) {
         const Stage::Slot& q = st.slot[i];
         if (!q.dst || q.bytes == 0) continue;
-        if (st.page) std::memcpy(q.dst, st.page + q.offset, q.bytes);
-        else UAVQP_HIP(hipMemcpyAsync(q.dst, st.base + q.offset, q.bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (mapped) std::memcpy(q.dst, st.page.at<char>(i), q.bytes);
+        else UAVQP_HIP(hipMemcpyAsync(q.dst, st.lay.at<char>(i), q.bytes, hipMemcpyDeviceToHost, ctx->stream));
     }
-    if (!st.page) UAVQP_HIP(hipStreamSynchronize(ctx->stream));
+    if (!mapped) UAVQP_HIP(hipStreamSynchronize(ctx->stream));
     return UAVQP_OK;
 }

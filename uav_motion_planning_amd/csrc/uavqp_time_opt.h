@@ -57,17 +57,6 @@ static bool topt_params_valid(const uavqp_time_opt_params* p) {
     return true;
 }
 
-static int ensure_topt_ws(uavqp_ctx* ctx, size_t bytes) {
-    if (bytes <= ctx->topt_bytes) return UAVQP_OK;
-    UAVQP_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->d_topt) UAVQP_HIP(hipFree(ctx->d_topt));
-    ctx->d_topt = nullptr;
-    ctx->topt_bytes = 0;
-    UAVQP_HIP(hipMalloc(&ctx->d_topt, bytes));
-    ctx->topt_bytes = bytes;
-    return UAVQP_OK;
-}
-
 extern "C" int uavqp_time_optimize_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
                                           const int32_t* d_seg_offsets, const double* d_waypoints, double* d_times, const double* d_bc,
                                           const uavqp_time_opt_params* params, double* d_coeff_out, int32_t* d_status_out,
@@ -82,26 +71,19 @@ extern "C" int uavqp_time_optimize_device(uavqp_ctx* ctx, int r, int n_traj, int
     const uavqp_time_opt_params P = *params;
     const size_t n = (size_t)n_traj, tot = (size_t)total_segments;
 
-    // workspace: [trial tot][gbest tot][fbest n][alpha n][need n][active n][status n]
-    const size_t o_tr = 0;
-    const size_t o_gb = o_tr + align256(sizeof(double) * tot);
-    const size_t o_fb = o_gb + align256(sizeof(double) * tot);
-    const size_t o_al = o_fb + align256(sizeof(double) * n);
-    const size_t o_nd = o_al + align256(sizeof(double) * n);
-    const size_t o_ac = o_nd + align256(sizeof(double) * n);
-    const size_t o_st = o_ac + align256(sizeof(int32_t) * n);
-    const size_t need = o_st + align256(sizeof(int32_t) * n);
-    int rc = ensure_topt_ws(ctx, need);
+    Carve c;
+    const int i_tr = c.add(sizeof(double) * tot), i_gb = c.add(sizeof(double) * tot), i_fb = c.add(sizeof(double) * n), i_al = c.add(sizeof(double) * n);
+    const int i_nd = c.add(sizeof(double) * n), i_ac = c.add(sizeof(int32_t) * n), i_st = c.add(sizeof(int32_t) * n);
+    int rc = carve_on(ctx->stream, ctx->topt, c);
     if (rc != UAVQP_OK) return rc;
-    char* base = (char*)ctx->d_topt;
-    int32_t* d_st_loop = (int32_t*)(base + o_st);
+    int32_t* d_st_loop = c.at<int32_t>(i_st);
     int32_t* d_st_final = d_status_out ? d_status_out : d_st_loop;
 
     uavqp::TimeOptArgs a;
     a.n_traj = n_traj; a.uniform = uniform_segments; a.seg_offsets = d_seg_offsets;
-    a.times = d_times; a.trial = (double*)(base + o_tr); a.gbest = (double*)(base + o_gb);
+    a.times = d_times; a.trial = c.at<double>(i_tr); a.gbest = c.at<double>(i_gb);
     a.coeff = d_coeff_out; a.status = P.max_iters > 0 ? d_st_loop : d_st_final;
-    a.fbest = (double*)(base + o_fb); a.alpha = (double*)(base + o_al); a.need = (double*)(base + o_nd); a.active = (int32_t*)(base + o_ac);
+    a.fbest = c.at<double>(i_fb); a.alpha = c.at<double>(i_al); a.need = c.at<double>(i_nd); a.active = c.at<int32_t>(i_ac);
     a.objective = d_objective_out; a.accepted = d_accepted_out;
     a.w = P.time_weight; a.t_min = P.t_min; a.t_max = P.t_max; a.initial_step = P.initial_step; a.armijo = P.armijo_c;
     a.shrink = P.shrink; a.grow = P.grow;
