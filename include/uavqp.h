@@ -367,6 +367,37 @@ int uavqp_time_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segm
                              const double* waypoints, double* times, const double* bc, const uavqp_time_opt_params* params,
                              double* coeff_out, int32_t* status_out, double* objective_out, int32_t* accepted_out);
 
+/* Backward pass of the equality-constrained solve (uavqp_solve_batch_*; no reference counterpart): the vector-Jacobian products of the
+ * minimiser.  Per trajectory and axis c*(T, p, y0, yM) is the unique minimiser the forward solve returns (coeff_out layout
+ * [axis][segment][2r]).  For a given g = dPhi/dc of an arbitrary Phi(c), in the same layout:
+ *   grad_times[seg_offsets[b] + i] = sum over axes, j of g_j dc*_j/dT_i             [sum_b M_b]
+ *   grad_waypoints[k][a]           = sum_j g_j dc*_j/dp_k (axis a)                  waypoint layout, all M_b + 1 knots incl. both ends
+ *   grad_bc[b][s][d][a]            = sum_j g_j dc*_j/dbc                            bc layout [n_traj][2][r-1][3]
+ * Equivalent KKT statement, per axis, with K = [[P, A'], [A, 0]], [c; nu] = K^-1 [0; b], [u; mu] = K^-1 [g; 0]:
+ *   dPhi/dtheta = -u' (dP/dtheta c + dA'/dtheta nu) - mu' (dA/dtheta c) + mu' db/dtheta
+ * (theta = T_i: b does not depend on it; theta = p_k or a boundary derivative: only b does).  This is ONLY the part through c*: the caller
+ * adds the explicit T-dependence of its own loss (e.g. Phi = c' P(T) c has the explicit part c' dP/dT_i c = sum over axes of
+ * (p^(r)(T_i))^2; with it the total is what uavqp_cost_time_gradient_device returns).
+ * Computed in the knot-derivative variables of the forward solve: the adjoint system is the forward's SPD block-tridiagonal matrix
+ * (DESIGN.md section 5.16), factorised once per trajectory with the three axes as right-hand sides; everything else is local to a segment.
+ *   d_coeff        the coefficients uavqp_solve_batch_device wrote for these inputs
+ *   d_status       [n_traj] its status, or NULL.  A trajectory whose status is not UAVQP_SOLVED, or that is invalid (M < 1, M > max_segments,
+ *                  a duration that is not positive and finite) gets ZERO in all three outputs.
+ *   d_grad_*       each may be NULL; all NULL: UAVQP_OK, nothing done.
+ * UAVQP_ERR_INVALID_ARG: r not 3 / 4, a negative count, a NULL input, ragged without offsets or with max_segments < 1, uniform with
+ * total_segments != uniform_segments * n_traj.  One launch, asynchronous on the ctx stream, no read-back (a first call of a given size
+ * grows the ctx workspace).  Every output element is written once, in a fixed order of additions: the same bytes run to run.
+ * Out of scope: corridor and general-rows solves (active sets), using this gradient inside uavqp_time_optimize_*, multi-GPU (shard the
+ * batch as for the solve). */
+int uavqp_solve_backward_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                                const int32_t* d_seg_offsets, const double* d_waypoints, const double* d_times, const double* d_bc,
+                                const double* d_coeff, const int32_t* d_status, const double* d_grad_coeff, double* d_grad_times,
+                                double* d_grad_waypoints, double* d_grad_bc);
+/* The same from HOST pointers (H2D copy, run, D2H copy, synchronous). */
+int uavqp_solve_backward_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                              const double* waypoints, const double* times, const double* bc, const double* coeff, const int32_t* status,
+                              const double* grad_coeff, double* grad_times, double* grad_waypoints, double* grad_bc);
+
 /* Batched evaluation of solved trajectories on a uniform time grid.
  * Replaces, for a whole batch, PolyTraj::evaluatePos / evaluateVel / evaluateAcc
  * (src/planner/traj_utils/include/traj_utils/poly_traj.hpp:74-168) as driven by poly_traj_server's

@@ -50,6 +50,8 @@ SYMBOLS = (
     "uavqp_default_time_opt_params",
     "uavqp_time_optimize_device",
     "uavqp_time_optimize_host",
+    "uavqp_solve_backward_device",
+    "uavqp_solve_backward_host",
     "uavqp_eval_batch_device",
     "uavqp_traj_length_device",
     "uavqp_ellipsoid_check_device",
@@ -172,6 +174,8 @@ def lib():
     L.uavqp_default_time_opt_params.restype = None
     L.uavqp_time_optimize_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, ctypes.POINTER(TimeOptParams), dp, ip, dp, ip]
     L.uavqp_time_optimize_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, ctypes.POINTER(TimeOptParams), dp, ip, dp, ip]
+    L.uavqp_solve_backward_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, dp, ip, dp, dp, dp, dp]
+    L.uavqp_solve_backward_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, dp, ip, dp, dp, dp, dp]
     L.uavqp_eval_batch_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, i32, dp]
     L.uavqp_traj_length_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ctypes.c_double, dp, dp, ip]
     L.uavqp_ellipsoid_check_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, dp, i32,

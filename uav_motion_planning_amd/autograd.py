@@ -1,0 +1,78 @@
+"""The batched equality-constrained solve as a differentiable torch operation.
+
+    coeff = solve_batch(ctx, r, waypoints, times, bc, uniform_segments=8)
+    loss(coeff).backward()          # -> times.grad, waypoints.grad, bc.grad
+
+forward = uavqp_solve_batch_device, backward = uavqp_solve_backward_device (include/uavqp.h), both enqueued on torch's current stream.
+The gradients are the part THROUGH the minimiser; a loss that also depends on `times` explicitly (e.g. through sampling times that scale
+with the durations) gets that part from torch's own graph, as for any other operation.  Inputs: contiguous float64 tensors on the
+ctx's device.  No CPU path: without libuavqp.so or a GPU the call raises.  torch is imported when the operation is first used.
+"""
+from . import _lib
+
+_Function = None
+
+
+def _function():
+    global _Function
+    if _Function is not None:
+        return _Function
+    import torch
+
+    class SolveBatch(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, waypoints, times, bc, ctx, r, seg_offsets, uniform_segments, max_segments, check_status):
+            for name, t in (("waypoints", waypoints), ("times", times), ("bc", bc)):
+                if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+                    raise ValueError(f"solve_batch: {name} must be a contiguous float64 tensor on the GPU")
+            total = times.numel()
+            n_traj = total // uniform_segments if uniform_segments > 0 else seg_offsets.numel() - 1
+            if waypoints.numel() != 3 * (total + n_traj) or bc.numel() != n_traj * 2 * (r - 1) * 3:
+                raise ValueError("solve_batch: waypoints must hold sum(M_b + 1) xyz rows and bc [n_traj][2][r-1][3]")
+            coeff = torch.zeros(3 * 2 * r * total, dtype=torch.float64, device=times.device)
+            status = torch.zeros(n_traj, dtype=torch.int32, device=times.device)
+            ctx.set_stream(torch.cuda.current_stream(times.device).cuda_stream)
+            ctx.solve_batch_device(r, n_traj, uniform_segments, max_segments, seg_offsets, waypoints.detach(), times.detach(), bc.detach(),
+                                   coeff, status)
+            if check_status and not bool((status == _lib.UAVQP_SOLVED).all()):   # (a read-back: only on request)
+                bad = int((status != _lib.UAVQP_SOLVED).sum())
+                raise _lib.UavqpError(f"solve_batch: {bad} of {n_traj} trajectories did not solve")
+            fctx.save_for_backward(waypoints, times, bc, coeff, status)
+            fctx.call = (ctx, r, n_traj, uniform_segments, max_segments, total, seg_offsets)
+            fctx.mark_non_differentiable(status)
+            return coeff, status
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable   # the gradients come from a raw kernel: no second derivative through them
+        def backward(fctx, grad_coeff, _grad_status):
+            waypoints, times, bc, coeff, status = fctx.saved_tensors
+            ctx, r, n_traj, uniform_segments, max_segments, total, seg_offsets = fctx.call
+            need_w, need_t, need_b = fctx.needs_input_grad[:3]
+            g = grad_coeff.contiguous()
+            g_w = torch.empty_like(waypoints) if need_w else None
+            g_t = torch.empty_like(times) if need_t else None
+            g_b = torch.empty_like(bc) if need_b else None
+            ctx.set_stream(torch.cuda.current_stream(times.device).cuda_stream)
+            ctx.solve_backward_device(r, n_traj, uniform_segments, max_segments, total, seg_offsets, waypoints, times, bc, coeff, g,
+                                      grad_times=g_t, grad_waypoints=g_w, grad_bc=g_b, status=status)
+            return g_w, g_t, g_b, None, None, None, None, None, None
+
+    _Function = SolveBatch
+    return _Function
+
+
+def solve_batch(ctx, r, waypoints, times, bc, seg_offsets=None, uniform_segments=0, max_segments=0, check_status=False, return_status=False):
+    """Differentiable uavqp_solve_batch_device.  ctx: a Context on the tensors' device.  waypoints [sum (M_b + 1)][3], times [sum M_b],
+    bc [n_traj][2][r-1][3]; seg_offsets: int32 device tensor [n_traj + 1] (ragged; max_segments = the longest trajectory, read back from
+    the offsets when 0) or None with uniform_segments > 0.  Returns coeff [sum_b 3 * M_b * 2r] (layout [axis][segment][2r] per
+    trajectory), with return_status also the int32 status tensor.  A trajectory that does not solve carries zero gradient;
+    check_status=True raises UavqpError instead (it costs a read-back)."""
+    if uniform_segments <= 0:
+        if seg_offsets is None:
+            raise ValueError("solve_batch: ragged batches need seg_offsets")
+        if max_segments <= 0:
+            max_segments = max(int((seg_offsets[1:] - seg_offsets[:-1]).max()), 1)
+    else:
+        max_segments = uniform_segments
+    coeff, status = _function().apply(waypoints, times, bc, ctx, int(r), seg_offsets, int(uniform_segments), int(max_segments), bool(check_status))
+    return (coeff, status) if return_status else coeff

@@ -174,6 +174,28 @@ class TrajOptimizer {
         return cost;
     }
 
+    // Backward pass of the last solve() (include/uavqp.h uavqp_solve_backward_host; the reference's equality rows only: false when a corridor
+    // or rows are set, or before a solve()).  gradCoeff = d loss / d getPolyCoeff(), same layout.  Out: the gradients of the loss through the
+    // solve with respect to the durations [sum M], the waypoints [sum (M + 1)][3] and the boundary derivatives [n_traj][2][order-1][3].
+    // The explicit dependence of the loss on the durations is the caller's.  A trajectory that did not solve carries zeros.
+    bool backward(const std::vector<double>& gradCoeff, std::vector<double>& gradTimes, std::vector<double>& gradWaypoints,
+                  std::vector<double>& gradBoundary) {
+        if (n_traj_ <= 0 || !ctx_ || !lo_.empty() || rows_k_ > 0) return false;
+        if (coef_.size() != static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_] || gradCoeff.size() != coef_.size() ||
+            status_.size() != static_cast<size_t>(n_traj_) || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_]))
+            return false;
+        gradTimes.assign(T_.size(), 0.0);
+        gradWaypoints.assign(wp_.size(), 0.0);
+        gradBoundary.assign(bc_.size(), 0.0);
+        const int rc = uavqp_solve_backward_host(ctx_, order_, n_traj_, 0, 0, seg_offsets_.data(), wp_.data(), T_.data(), bc_.data(), coef_.data(),
+                                                 status_.data(), gradCoeff.data(), gradTimes.data(), gradWaypoints.data(), gradBoundary.data());
+        if (rc != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            return false;
+        }
+        return true;
+    }
+
     // BASELINE config 5 as one call (include/uavqp.h uavqp_corridor_pipeline_host): plain solve -> corridor boxes from the obstacle cloud
     // (SE(3) robot ellipsoid of KinoAstar::isCollisionFree) -> <= max_rounds x (corridor solve + time re-allocation) -> collision check
     // -> repair.  obstacles [n_obs][3].  On return: getPolyCoeff() = the final polynomials, timeAllocation() = the stretched durations,

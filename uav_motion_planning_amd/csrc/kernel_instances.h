@@ -89,3 +89,7 @@
     UAVQP_INST __global__ void uavqp::time_opt_step_kernel<R_, true>(uavqp::TimeOptArgs);    \
     UAVQP_INST __global__ void uavqp::time_opt_step_kernel<R_, false>(uavqp::TimeOptArgs);
 #define UAVQP_INSTANCES_TIMEOPT UAVQP_TIMEOPT_R(3) UAVQP_TIMEOPT_R(4)
+
+// ---- qp_adjoint.h: backward pass of the equality-constrained solve
+#define UAVQP_ADJOINT_R(R_) UAVQP_INST __global__ void uavqp::solve_backward_kernel<R_>(uavqp::AdjointArgs);
+#define UAVQP_INSTANCES_ADJOINT UAVQP_ADJOINT_R(3) UAVQP_ADJOINT_R(4)

@@ -31,6 +31,7 @@
 #include "qp_rows_dual.h"
 #include "obstacle_grid.h"
 #include "qp_time_opt.h"
+#include "qp_adjoint.h"
 // Measured-slower alternatives kept as bit-identical cross-checks: `make experiments` (-DUAVQP_EXPERIMENTS) only
 #ifdef UAVQP_EXPERIMENTS
 #include "cloud_grid2d.h"
@@ -53,6 +54,7 @@ UAVQP_INSTANCES_ROWS42
 UAVQP_INSTANCES_ROWS_DUAL
 UAVQP_INSTANCES_CLOUD
 UAVQP_INSTANCES_TIMEOPT
+UAVQP_INSTANCES_ADJOINT
 #endif
 
 namespace uavqp {
@@ -1678,6 +1680,11 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
 // Cost, exact time gradient and the duration optimiser
 // ===================================================================================================
 #include "uavqp_time_opt.h"
+
+// ===================================================================================================
+// Backward pass of the equality-constrained solve
+// ===================================================================================================
+#include "uavqp_adjoint.h"
 
 // ===================================================================================================
 // N3: quadrotor_msgs/PolynomialTrajectory packer (host only)

@@ -152,6 +152,37 @@ class Context:
         _lib.check(rc, "uavqp_time_optimize_host")
         return times, coeff, status, objective, accepted
 
+    def solve_backward_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc, coeff,
+                              grad_coeff, grad_times=None, grad_waypoints=None, grad_bc=None, status=None):
+        """uavqp_solve_backward_device on device buffers: for grad_coeff = dPhi/dcoeff (layout of coeff) the vector-Jacobian products
+        through the minimiser of uavqp_solve_batch_device -- grad_times [sum M], grad_waypoints [sum (M + 1)][3], grad_bc
+        [n_traj][2][r-1][3]; each output may be None.  status (the solve's, optional): trajectories that are not SOLVED get zeros.
+        The explicit dependence of the caller's loss on the durations is not included.  Asynchronous."""
+        rc = _lib.lib().uavqp_solve_backward_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), _ptr(seg_offsets),
+                                                    _ptr(waypoints), _ptr(times), _ptr(bc), _ptr(coeff), _ptr(status), _ptr(grad_coeff),
+                                                    _ptr(grad_times), _ptr(grad_waypoints), _ptr(grad_bc))
+        _lib.check(rc, "uavqp_solve_backward_device")
+
+    def solve_backward_host(self, r, seg_offsets, waypoints, times, bc, coeff, grad_coeff, uniform_segments=0, status=None,
+                            want=(True, True, True)):
+        """numpy in / numpy out (synchronous).  Returns (grad_times, grad_waypoints, grad_bc); an entry of `want` that is False gives None."""
+        waypoints = np.ascontiguousarray(waypoints, dtype=np.float64)
+        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
+        bc = np.ascontiguousarray(bc, dtype=np.float64)
+        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
+        grad_coeff = np.ascontiguousarray(grad_coeff, dtype=np.float64).ravel()
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        so, n_traj, total, mmax = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total and waypoints.size == 3 * (total + n_traj), "waypoints must hold sum(M_b + 1) xyz rows"
+        assert bc.size == n_traj * 2 * (r - 1) * 3 and coeff.size == 3 * 2 * r * total == grad_coeff.size
+        g_t = np.zeros(total, dtype=np.float64) if want[0] else None
+        g_w = np.zeros((total + n_traj, 3), dtype=np.float64) if want[1] else None
+        g_b = np.zeros((n_traj, 2, r - 1, 3), dtype=np.float64) if want[2] else None
+        rc = _lib.lib().uavqp_solve_backward_host(self._h, r, n_traj, uniform_segments, max(mmax, 1), _ptr(so), _ptr(waypoints), _ptr(times),
+                                                  _ptr(bc), _ptr(coeff), _ptr(status), _ptr(grad_coeff), _ptr(g_t), _ptr(g_w), _ptr(g_b))
+        _lib.check(rc, "uavqp_solve_backward_host")
+        return g_t, g_w, g_b
+
     def ellipsoid_check_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, n_samples, t0, dt,
                                obstacles, n_obs, robot_r, robot_h, first_hit, flags=None):
         """Batched KinoAstar::isCollisionFree over the samples of solved trajectories (device buffers)."""
@@ -448,6 +479,8 @@ class TrajOptimizer:
     optimizeTime(time_weight, ...)   equality-constrained problems only: minimises cost + time_weight * sum T over the durations
                                      (uavqp_time_optimize_host), stores the optimised allocation (getTimeAllocation) and the
                                      coefficients at it; objective [n_traj][2] (start, result) in .objective
+    backward(grad_coeff)             equality-constrained problems only, after solve(): (grad_times, grad_waypoints, grad_bc) of a loss
+                                     with d loss / d getPolyCoeff() = grad_coeff, through the solve
     getCost()                        [n_traj] control cost c' P c of the stored coefficients at the stored durations
     getPolyCoeff()                   flat float64 array, trajectory b at 3*2r*seg_offsets[b], [axis][seg][2r]
     """
@@ -542,6 +575,17 @@ class TrajOptimizer:
         self._T, self._coef, self.status, self.objective, self.iterations = self._ctx.time_optimize_host(
             self._r, self._so, self._wp, self._T, bc, **params)
         return bool(np.all(self.status == _lib.UAVQP_SOLVED))
+
+    def backward(self, grad_coeff):
+        """After solve() of an equality-constrained problem: (grad_times, grad_waypoints, grad_bc) as numpy for grad_coeff = dPhi/dcoeff in
+        the layout of getPolyCoeff() (uavqp_solve_backward_host).  Trajectories that did not solve carry zeros."""
+        if self._lo is not None or self._rows is not None:
+            raise ValueError("backward: corridor and general-rows problems are out of scope (include/uavqp.h)")
+        if self._ctx is None or self._coef.size != 3 * 2 * self._r * int(self._so[-1]) or self.status.size != self._so.size - 1:
+            raise _lib.UavqpError("backward: no solved coefficients (call solve() first)")
+        n_traj = self._so.size - 1
+        bc = self._bc if self._bc is not None else np.zeros((n_traj, 2, self._r - 1, 3))
+        return self._ctx.solve_backward_host(self._r, self._so, self._wp, self._T, bc, self._coef, grad_coeff, status=self.status)
 
     def getTimeAllocation(self):
         return self._T.copy()
