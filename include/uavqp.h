@@ -299,6 +299,8 @@ int uavqp_solve_rows_batch_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_s
  * (never shrunk).  Scaling is per trajectory, not per segment: stretching one segment next to short ones makes
  * it overshoot more (it inherits their knot acceleration) and diverges; uniform scaling T -> sT lowers speeds
  * ~1/s and accelerations ~1/s^2.
+ * Non-finite input: if ANY sample of a trajectory is NaN or infinite (coefficients or durations that a UAVQP_NON_FINITE solve
+ * hands over), the whole trajectory is left unchanged and d_changed_out[b] = 0, whatever its other segments say.
  * d_times is updated in place; d_changed_out[b] (may be NULL) receives the number of stretched segments of
  * trajectory b, so the caller can stop when it is all zero.  Typical loop: solve, reallocate, solve, ... (<= 5x). */
 int uavqp_time_reallocate_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,

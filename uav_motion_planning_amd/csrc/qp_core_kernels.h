@@ -608,7 +608,7 @@ __global__ __launch_bounds__(256) void ellipsoid_kernel(EllipsoidArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Time re-allocation: one lane per segment; peak |v|, |a| by sampling, stretch-only update of T.
+// Time re-allocation: eight lanes per trajectory; peak |v|, |a| by sampling, stretch-only update of T by one factor per trajectory.
 // ---------------------------------------------------------------------------------------------------
 struct ReallocArgs {
     int n_traj, uniform, samples;
@@ -660,8 +660,10 @@ __global__ __launch_bounds__(64) void realloc_kernel(ReallocArgs a) {
                     vs += v * v;
                     as += ac * ac;
                 }
-                v2 = fmax(v2, vs);
-                a2 = fmax(a2, as);
+                // a NaN sample marks the peak with +Inf (fmax alone would drop it and let the other samples decide): the mark travels
+                // through the maxima and the shuffles below like any peak, and an infinite ratio leaves the whole trajectory alone
+                v2 = fmax(v2, vs == vs ? vs : INFINITY);
+                a2 = fmax(a2, as == as ? as : INFINITY);
             }
         }
 #pragma unroll
