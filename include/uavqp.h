@@ -639,9 +639,23 @@ int uavqp_allgather_status(uavqp_ctx* ctx, const int32_t* d_local, const int64_t
 /* hipGraph capture of a launch-bound inner loop: everything enqueued on the ctx stream between
  * uavqp_capture_begin and uavqp_capture_end (any number of uavqp_solve_batch_device calls with their
  * workspaces already sized by one eager call) becomes one executable graph; uavqp_graph_launch replays
- * it on the ctx stream.  No reference counterpart (the reference has no device queue). */
+ * it on the ctx stream.  No reference counterpart (the reference has no device queue).
+ *
+ * A replay may run captured solves CONCURRENTLY.  uavqp_capture_end knows which bytes every captured uniform-batch
+ * uavqp_solve_batch_device call reads (waypoints, times, bc) and writes (coeff_out, status_out) and orders two of them only
+ * where those ranges overlap (read after write, write after read, write after write); solves on disjoint buffers become
+ * chain graphs on streams of the ctx ("lanes"), forked from and joined to the ctx stream by events (work queued on the ctx stream
+ * behind uavqp_graph_launch waits for all of it): at most UAVQP_CAPTURE_LANES (default 4, 1..8; 1 = keep the captured order) side
+ * by side, and a lane only where there are 16 launches for it (UAVQP_CAPTURE_LANE_NODES) -- a shorter capture replays as captured.
+ * When a replay completes, every buffer holds what the calls would have left in the order they were captured.  One visible
+ * difference: a status store that a LATER captured solve overwrites completely, with nothing in between touching those
+ * entries, is not performed (that is what lets steps that share one status array overlap) -- the array holds the last
+ * writer's codes, as in serial order, but never an earlier solve's codes in the meantime.
+ * Ragged batches, and batches that take a kernel with a ctx workspace, are ordered against everything before and after them.
+ * A capture that contains anything else -- another entry point's launch, a copy, a foreign node -- and a process started
+ * with GPU_MAX_HW_QUEUES below 4 (read, never set) replay exactly the chain that was captured. */
 int uavqp_capture_begin(uavqp_ctx* ctx);
-int uavqp_capture_end(uavqp_ctx* ctx, void** out_graph_exec);
+int uavqp_capture_end(uavqp_ctx* ctx, void** out_graph_exec);   /* the handle is the library's own: only for uavqp_graph_launch / _destroy */
 int uavqp_graph_launch(uavqp_ctx* ctx, void* graph_exec);
 int uavqp_graph_destroy(uavqp_ctx* ctx, void* graph_exec);
 

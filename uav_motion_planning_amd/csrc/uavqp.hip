@@ -148,6 +148,15 @@ static int await_host_word(hipStream_t s, volatile unsigned long long* w, unsign
     } while (0)
 
 #include "uavqp_ws.h"
+#include "uavqp_capture.h"
+
+// one kernel launch of uavqp_solve_batch_device made while the ctx stream was capturing: what uavqp_capture_end rebuilds the graph from
+struct CapturedLaunch {
+    const void* fn = nullptr;
+    dim3 grid, block;
+    unsigned int lds_bytes = 0;
+    BatchArgs args{};  // (a barrier launch is re-added with the parameters of its captured node: not every such kernel takes a BatchArgs)
+};
 
 struct uavqp_ctx {
     int device = 0;
@@ -183,7 +192,41 @@ struct uavqp_ctx {
     // duration optimiser (uavqp_time_opt.h): trial durations, stored gradient and the per-trajectory state of the descent
     DevBuf topt;
     unsigned int pipe_seq = 0;   // sequence number of the last pipeline round enqueued (uavqp_pipeline.h: tags the count a round reports to the host)
+    // between uavqp_capture_begin and uavqp_capture_end: one entry per kernel launch of uavqp_solve_batch_device, in launch order
+    bool capturing = false;
+    // replay (uavqp_graph_launch): lane 0 of a stage runs on the ctx stream, lane l > 0 on lane_stream[l] (non-blocking, made on first use),
+    // forked from the ctx stream by ev_fork and joined to it by ev_join[l]
+    hipStream_t lane_stream[uavqp_capture::LANES_MAX] = {};
+    hipEvent_t ev_fork = nullptr, ev_join[uavqp_capture::LANES_MAX] = {};
+    std::vector<CapturedLaunch> cap_launch;
+    std::vector<uavqp_capture::Record> cap_rec;
 };
+
+// (capture only) remember a launch just made on the ctx stream; `a` null = a launch that cannot be analysed (a barrier)
+static void capture_note(uavqp_ctx* ctx, const void* fn, dim3 grid, dim3 block, size_t lds_bytes, const BatchArgs* a, int r) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusActive) {   // the capture ended behind the library's back
+        ctx->capturing = false;
+        ctx->cap_launch.clear();
+        ctx->cap_rec.clear();
+        return;
+    }
+    CapturedLaunch l;
+    l.fn = fn; l.grid = grid; l.block = block; l.lds_bytes = (unsigned int)lds_bytes;
+    uavqp_capture::Record rec;
+    rec.barrier = a == nullptr;
+    if (a) {
+        l.args = *a;
+        const size_t n = (size_t)a->n_traj, tot = n * (size_t)a->uniform;
+        rec.read[0] = uavqp_capture::range_of(a->waypoints, sizeof(double) * 3 * (tot + n));
+        rec.read[1] = uavqp_capture::range_of(a->times, sizeof(double) * tot);
+        rec.read[2] = uavqp_capture::range_of(a->bc, sizeof(double) * n * 2 * (size_t)(r - 1) * 3);
+        rec.coeff = uavqp_capture::range_of(a->coeff, sizeof(double) * 3 * 2 * (size_t)r * tot);
+        rec.status = uavqp_capture::range_of(a->status, sizeof(int32_t) * n);
+    }
+    ctx->cap_launch.push_back(l);
+    ctx->cap_rec.push_back(rec);
+}
 
 #ifndef UAVQP_SRC_HASH
 #define UAVQP_SRC_HASH "unknown"
@@ -323,6 +366,11 @@ extern "C" int uavqp_destroy(uavqp_ctx* ctx) {
     if (ctx->dummy) (void)hipFree(ctx->dummy);
     if (ctx->h_axis) (void)hipHostFree(ctx->h_axis);
     if (ctx->h_pipe) (void)hipHostFree(ctx->h_pipe);
+    for (hipStream_t& s : ctx->lane_stream)
+        if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+    for (hipEvent_t& e : ctx->ev_join)
+        if (e) (void)hipEventDestroy(e);
+    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return UAVQP_OK;
@@ -407,6 +455,7 @@ extern "C" int uavqp_solve_batch_device(uavqp_ctx* ctx, int r, int n_traj, int u
             int g = n_tiles < max_wg ? n_tiles : max_wg;
             hipLaunchKernelGGL(fn, dim3(g), dim3(64), 0, ctx->stream, a);
             UAVQP_HIP(hipGetLastError());
+            if (ctx->capturing) capture_note(ctx, (const void*)fn, dim3(g), dim3(64), 0, &a, r);   // no workspace of the ctx: the one analysable launch
             return UAVQP_OK;
         }
         if (ctx->variant == 2) {
@@ -469,6 +518,7 @@ extern "C" int uavqp_solve_batch_device(uavqp_ctx* ctx, int r, int n_traj, int u
         if (pair) hipLaunchKernelGGL((uavqp::window_sort_kernel<512>), dim3(n_win), dim3(256), 0, ctx->stream, d_seg_offsets, n_traj, perm, perm4);
         else if (nax == 3) hipLaunchKernelGGL((uavqp::window_sort_kernel<1024>), dim3(n_win), dim3(256), 0, ctx->stream, d_seg_offsets, n_traj, perm, perm4);
         else hipLaunchKernelGGL((uavqp::window_sort_kernel<336>), dim3(n_win), dim3(256), 0, ctx->stream, d_seg_offsets, n_traj, perm, perm4);
+        if (ctx->capturing) capture_note(ctx, nullptr, dim3(n_win), dim3(256), 0, nullptr, r);
         a.perm = perm;
         a.perm4 = perm4;
     }
@@ -489,6 +539,7 @@ extern "C" int uavqp_solve_batch_device(uavqp_ctx* ctx, int r, int n_traj, int u
     else UAVQP_GENERIC(4);
 #undef UAVQP_GENERIC
     UAVQP_HIP(hipGetLastError());
+    if (ctx->capturing) capture_note(ctx, nullptr, dim3(grid), dim3(block), 0, nullptr, r);   // ctx->ws (and ctx->perm): ordered against everything
     return UAVQP_OK;
 }
 
@@ -591,38 +642,176 @@ extern "C" int uavqp_solve_axis_host(uavqp_ctx* ctx, int r, int n_seg, const dou
     return rc;
 }
 
+static void capture_forget(uavqp_ctx* ctx) {
+    ctx->capturing = false;
+    ctx->cap_launch.clear();
+    ctx->cap_rec.clear();
+}
+
 extern "C" int uavqp_capture_begin(uavqp_ctx* ctx) {
     if (!ctx) return UAVQP_ERR_INVALID_ARG;
+    capture_forget(ctx);
     UAVQP_HIP(hipSetDevice(ctx->device));
     UAVQP_HIP(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+    ctx->capturing = true;
     return UAVQP_OK;
+}
+
+// The captured chain in launch order, if a chain of kernel nodes is what was captured (one root, every node at most one dependent).
+static bool captured_chain(hipGraph_t graph, std::vector<hipGraphNode_t>& order) {
+    size_t n = 0, n_root = 0;
+    if (hipGraphGetNodes(graph, nullptr, &n) != hipSuccess || n == 0) return false;
+    if (hipGraphGetRootNodes(graph, nullptr, &n_root) != hipSuccess || n_root != 1) return false;
+    hipGraphNode_t node = nullptr;
+    if (hipGraphGetRootNodes(graph, &node, &n_root) != hipSuccess || n_root != 1) return false;
+    order.clear();
+    while (node) {
+        hipGraphNodeType type;
+        if (order.size() == n || hipGraphNodeGetType(node, &type) != hipSuccess || type != hipGraphNodeTypeKernel) return false;
+        order.push_back(node);
+        size_t n_next = 0;
+        if (hipGraphNodeGetDependentNodes(node, nullptr, &n_next) != hipSuccess || n_next > 1) return false;
+        hipGraphNode_t next = nullptr;
+        if (n_next == 1 && (hipGraphNodeGetDependentNodes(node, &next, &n_next) != hipSuccess || n_next != 1)) return false;
+        node = next;
+    }
+    return order.size() == n;
+}
+
+// What uavqp_capture_end hands out: the stages of a replay, each a set of chain graphs that run side by side (uavqp_capture.h:
+// stage_starts).  A capture that is replayed as captured is one stage of one lane.
+struct CapturedGraph {
+    std::vector<std::vector<hipGraphExec_t>> stage;
+    ~CapturedGraph() {
+        for (auto& lanes : stage)
+            for (hipGraphExec_t e : lanes) (void)hipGraphExecDestroy(e);
+    }
+};
+
+// The same launches as `captured`, ordered by what they touch instead of by when they were enqueued (uavqp_capture.h): independent solves
+// go to different lanes, at most `lanes` of them.  False when the capture is not exactly the recorded launches of
+// uavqp_solve_batch_device, when nothing in it is independent, or when the runtime refuses a step: the caller keeps the captured graph.
+// (Measured: ONE graph with parallel branches replays slower than the captured chain -- the runtime leaves its single-queue fast path --
+//  so every lane of a stage is a chain graph of its own: docs/measurement_log.md.)
+static bool rebuild_captured(uavqp_ctx* ctx, hipGraph_t captured, int lanes, int nodes_per_lane, CapturedGraph& out) {
+    const size_t n = ctx->cap_launch.size();
+    if (lanes <= 1 || n < 2 || n != ctx->cap_rec.size()) return false;
+    std::vector<hipGraphNode_t> order;
+    if (!captured_chain(captured, order) || order.size() != n) return false;
+    std::vector<hipKernelNodeParams> params(n);
+    for (size_t k = 0; k < n; ++k) {
+        const CapturedLaunch& l = ctx->cap_launch[k];
+        hipKernelNodeParams& p = params[k];
+        if (hipGraphKernelNodeGetParams(order[k], &p) != hipSuccess) return false;
+        if ((l.fn && p.func != l.fn) || p.gridDim.x != l.grid.x || p.gridDim.y != l.grid.y || p.gridDim.z != l.grid.z) return false;
+    }
+    const uavqp_capture::Plan plan = uavqp_capture::analyse(ctx->cap_rec, lanes);
+    if (!plan.parallel) return false;
+    std::vector<int> starts = uavqp_capture::stage_starts(plan, lanes);
+    starts.push_back((int)n);
+    bool side_by_side = false;
+    for (size_t s = 0; s + 1 < starts.size(); ++s) {
+        const int first = starts[s], width = uavqp_capture::lanes_that_pay(starts[s + 1] - first, lanes, nodes_per_lane);
+        side_by_side |= width > 1;
+        out.stage.emplace_back();
+        for (int lane = 0; lane < width; ++lane) {   // node k of the stage: lane (k % lanes) % width
+            hipGraph_t graph = nullptr;
+            if (hipGraphCreate(&graph, 0) != hipSuccess) return false;
+            hipGraphNode_t prev = nullptr;
+            bool ok = true;
+            for (int k = first; ok && k < starts[s + 1]; ++k) {
+                if ((k % lanes) % width != lane) continue;
+                const CapturedLaunch& l = ctx->cap_launch[k];
+                BatchArgs a = l.args;
+                if (plan.status_dead[k]) a.status = nullptr;   // a later solve overwrites every one of them before anything reads one
+                void* kernel_params[1] = {&a};
+                hipKernelNodeParams p = params[k];             // a barrier: as captured
+                if (l.fn) {
+                    p = hipKernelNodeParams{};
+                    p.func = const_cast<void*>(l.fn);
+                    p.gridDim = l.grid;
+                    p.blockDim = l.block;
+                    p.sharedMemBytes = l.lds_bytes;
+                    p.kernelParams = kernel_params;
+                }
+                hipGraphNode_t node = nullptr;
+                ok = hipGraphAddKernelNode(&node, graph, prev ? &prev : nullptr, prev ? 1 : 0, &p) == hipSuccess;   // (the arguments are copied into the node)
+                prev = node;
+            }
+            hipGraphExec_t exec = nullptr;
+            ok = ok && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
+            (void)hipGraphDestroy(graph);
+            if (!ok) return false;
+            out.stage.back().push_back(exec);
+        }
+    }
+    if (!side_by_side) return false;
+    // the streams and events the replay forks to and joins through
+    if (!ctx->ev_fork && hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess) return false;
+    for (int lane = 1; lane < lanes; ++lane) {
+        if (!ctx->lane_stream[lane] && hipStreamCreateWithFlags(&ctx->lane_stream[lane], hipStreamNonBlocking) != hipSuccess) return false;
+        if (!ctx->ev_join[lane] && hipEventCreateWithFlags(&ctx->ev_join[lane], hipEventDisableTiming) != hipSuccess) return false;
+    }
+    return true;
 }
 
 extern "C" int uavqp_capture_end(uavqp_ctx* ctx, void** out_graph_exec) {
     if (!ctx || !out_graph_exec) return UAVQP_ERR_INVALID_ARG;
     *out_graph_exec = nullptr;
+    struct Forget {   // the records of this capture are gone on every way out
+        uavqp_ctx* ctx;
+        ~Forget() { capture_forget(ctx); }
+    } forget{ctx};
     hipGraph_t graph = nullptr;
     UAVQP_HIP(hipStreamEndCapture(ctx->stream, &graph));
-    hipGraphExec_t exec = nullptr;
-    hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) {
-        g_last_error = std::string("hipGraphInstantiate: ") + hipGetErrorString(e);
-        return UAVQP_ERR_HIP;
+    // UAVQP_CAPTURE_LANES = 1..8 (A/B runs; 1 = replay the chain as captured).  GPU_MAX_HW_QUEUES is only read: a process given fewer
+    // than 4 hardware queues keeps the chain.  UAVQP_CAPTURE_LANE_NODES: the launches a stage must have per lane (default 16).
+    const uavqp_capture::Knobs knobs = uavqp_capture::knobs_from_environment();
+    const int lanes = ctx->capturing ? knobs.lanes : 1;
+    CapturedGraph* cg = new (std::nothrow) CapturedGraph();
+    if (!cg) { (void)hipGraphDestroy(graph); return UAVQP_ERR_ALLOC; }
+    if (!rebuild_captured(ctx, graph, lanes, knobs.nodes_per_lane, *cg)) {
+        (void)hipGetLastError();
+        delete cg;
+        cg = new (std::nothrow) CapturedGraph();
+        if (!cg) { (void)hipGraphDestroy(graph); return UAVQP_ERR_ALLOC; }
+        hipGraphExec_t exec = nullptr;
+        const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        if (e != hipSuccess) {
+            (void)hipGraphDestroy(graph);
+            delete cg;
+            g_last_error = std::string("hipGraphInstantiate: ") + hipGetErrorString(e);
+            return UAVQP_ERR_HIP;
+        }
+        cg->stage.emplace_back(1, exec);
     }
-    *out_graph_exec = (void*)exec;
+    (void)hipGraphDestroy(graph);
+    *out_graph_exec = (void*)cg;
     return UAVQP_OK;
 }
 
+// Lane 0 of every stage replays on the ctx stream; the other lanes wait for what the ctx stream holds so far (ev_fork) and the ctx stream
+// waits for each of them (ev_join) before the next stage, or whatever the caller enqueues behind the replay, starts.
 extern "C" int uavqp_graph_launch(uavqp_ctx* ctx, void* graph_exec) {
     if (!ctx || !graph_exec) return UAVQP_ERR_INVALID_ARG;
-    UAVQP_HIP(hipGraphLaunch((hipGraphExec_t)graph_exec, ctx->stream));
+    const CapturedGraph* cg = (const CapturedGraph*)graph_exec;
+    for (const std::vector<hipGraphExec_t>& lanes : cg->stage) {
+        const size_t m = lanes.size();
+        if (m > 1) UAVQP_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
+        for (size_t l = 1; l < m; ++l) {
+            UAVQP_HIP(hipStreamWaitEvent(ctx->lane_stream[l], ctx->ev_fork, 0));
+            UAVQP_HIP(hipGraphLaunch(lanes[l], ctx->lane_stream[l]));
+            UAVQP_HIP(hipEventRecord(ctx->ev_join[l], ctx->lane_stream[l]));
+        }
+        UAVQP_HIP(hipGraphLaunch(lanes[0], ctx->stream));
+        for (size_t l = 1; l < m; ++l) UAVQP_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join[l], 0));
+    }
     return UAVQP_OK;
 }
 
 extern "C" int uavqp_graph_destroy(uavqp_ctx* ctx, void* graph_exec) {
     if (!ctx) return UAVQP_ERR_INVALID_ARG;
-    if (graph_exec) UAVQP_HIP(hipGraphExecDestroy((hipGraphExec_t)graph_exec));
+    delete (CapturedGraph*)graph_exec;
     return UAVQP_OK;
 }
 

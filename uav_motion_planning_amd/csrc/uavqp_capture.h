@@ -1,0 +1,163 @@
+// uavqp_capture.h -- which captured solves may run side by side when their graph is replayed: the dependency analysis behind
+// uavqp_capture_end (uavqp.hip).  A stream capture orders every launch behind the one before it; steps of a launch-bound inner loop
+// usually touch disjoint buffers, and about 30 % of each is the GPU idling at that kernel boundary (docs/measurement_log.md 5.1, 6, 7).
+// Host-only: byte ranges and indices, no HIP type -- compiles without the runtime (tests/cpp/test_capture_deps.cpp).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <cstdlib>
+#include <vector>
+
+namespace uavqp_capture {
+
+// bytes [lo, hi) of the address space; lo == hi is "nothing".  Two ranges that touch end to start do not overlap.
+struct Range {
+    uintptr_t lo = 0, hi = 0;
+    bool empty() const { return hi <= lo; }
+    bool overlaps(const Range& o) const { return !empty() && !o.empty() && lo < o.hi && o.lo < hi; }
+    bool covers(const Range& o) const { return !empty() && !o.empty() && lo <= o.lo && o.hi <= hi; }
+};
+static inline Range range_of(const void* p, size_t bytes) {
+    Range g;
+    if (p && bytes) { g.lo = (uintptr_t)p; g.hi = g.lo + bytes; }
+    return g;
+}
+
+// What one captured launch touches.  A launch whose extents the host does not know (ragged batches), or that goes through a workspace
+// of the ctx, is a barrier: it conflicts with everything before and after it.
+struct Record {
+    bool barrier = false;
+    Range read[3];    // waypoints, durations, boundary values
+    Range coeff;      // written
+    Range status;     // written; empty when the caller passed no status array
+};
+
+struct Plan {
+    std::vector<std::vector<int>> preds;   // per node: the nodes it waits for (transitive reduction, descending)
+    std::vector<char> status_dead;         // per node: a later node overwrites every status it would store before anything reads one
+    bool parallel = false;                 // at least two nodes are mutually independent
+};
+
+static constexpr int LANES_DEFAULT = 4;    // what bench.py's `pipelined` sub-record was measured with; HIP's default hardware-queue count
+static constexpr int LANES_MAX = 8;
+static constexpr size_t NODES_MAX = 4096;  // the ancestor sets are n^2 / 8 bytes: larger captures stay the chain they were captured as
+
+// UAVQP_CAPTURE_LANES (1..8, anything else: the default) and GPU_MAX_HW_QUEUES as found in the environment (either may be null).  A process
+// given fewer than 4 hardware queues replays its graphs as captured: parallel branches want a queue each.
+static inline int lanes_from_env(const char* lanes_env, const char* hw_queues_env) {
+    int lanes = LANES_DEFAULT;
+    if (lanes_env && *lanes_env) {
+        const int v = std::atoi(lanes_env);
+        if (v >= 1 && v <= LANES_MAX) lanes = v;
+    }
+    if (hw_queues_env && *hw_queues_env && std::atoi(hw_queues_env) < 4) lanes = 1;
+    return lanes;
+}
+
+static inline bool writes_into(const Record& w, bool w_status_dead, const Range& g) {
+    return w.coeff.overlaps(g) || (!w_status_dead && w.status.overlaps(g));
+}
+static inline bool touches(const Record& x, const Range& g) {   // any read or write of x, its status store included
+    return x.read[0].overlaps(g) || x.read[1].overlaps(g) || x.read[2].overlaps(g) || x.coeff.overlaps(g) || x.status.overlaps(g);
+}
+// must k (later) wait for i (earlier)?  read-after-write, write-after-read, write-after-write; a dead status store is no write
+static inline bool conflict(const Record& i, bool i_dead, const Record& k, bool k_dead) {
+    if (i.barrier || k.barrier) return true;
+    for (int q = 0; q < 3; ++q)
+        if (writes_into(i, i_dead, k.read[q]) || writes_into(k, k_dead, i.read[q])) return true;
+    if (writes_into(i, i_dead, k.coeff)) return true;
+    return !k_dead && writes_into(i, i_dead, k.status);
+}
+
+// The status store of node i is dead when the NEXT node that touches its range at all is a solve whose status range covers it and that
+// touches it in no other way: nothing captured reads a status, so when the graph completes the array holds the last writer's values, as
+// in serial order.  Anything else -- a partial overlap, a read of those bytes, a barrier in between -- keeps the store (and its edge).
+static inline std::vector<char> dead_status_stores(const std::vector<Record>& rec) {
+    const size_t n = rec.size();
+    std::vector<char> dead(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        if (rec[i].barrier || rec[i].status.empty()) continue;
+        const Range& s = rec[i].status;
+        for (size_t k = i + 1; k < n; ++k) {
+            if (rec[k].barrier) break;
+            if (!touches(rec[k], s)) continue;
+            const Record& x = rec[k];
+            dead[i] = x.status.covers(s) && !x.coeff.overlaps(s) && !x.read[0].overlaps(s) && !x.read[1].overlaps(s) && !x.read[2].overlaps(s);
+            break;
+        }
+    }
+    return dead;
+}
+
+// Edges of the rebuilt graph: conflicts + the lane edges k - lanes -> k (at most `lanes` chains run side by side), transitively reduced.
+// Nodes are in capture order, so every edge points forward and node k's ancestors are known once k - 1 .. 0 have been looked at,
+// nearest first: a candidate already among the ancestors is implied by an edge taken before it.
+static inline Plan analyse(const std::vector<Record>& rec, int lanes) {
+    const size_t n = rec.size();
+    Plan plan;
+    plan.preds.assign(n, std::vector<int>());
+    if (n > NODES_MAX) lanes = 1;
+    if (lanes < 1) lanes = 1;
+    plan.status_dead = lanes > 1 ? dead_status_stores(rec) : std::vector<char>(n, 0);
+    if (lanes == 1) {    // the captured chain
+        for (size_t k = 1; k < n; ++k) plan.preds[k].push_back((int)k - 1);
+        return plan;
+    }
+    const size_t words = (n + 63) / 64;
+    std::vector<uint64_t> anc(n * words, 0);    // anc[k]: bit i = node i runs before node k
+    for (size_t k = 0; k < n; ++k) {
+        uint64_t* mine = &anc[k * words];
+        size_t n_anc = 0;
+        for (size_t i = k; i-- > 0;) {
+            if (mine[i / 64] >> (i % 64) & 1) { ++n_anc; continue; }
+            if (i + (size_t)lanes != k && !conflict(rec[i], plan.status_dead[i] != 0, rec[k], plan.status_dead[k] != 0)) continue;
+            plan.preds[k].push_back((int)i);
+            const uint64_t* theirs = &anc[i * words];
+            for (size_t w = 0; w <= i / 64; ++w) mine[w] |= theirs[w];
+            mine[i / 64] |= (uint64_t)1 << (i % 64);
+            ++n_anc;
+        }
+        if (n_anc < k) plan.parallel = true;
+    }
+    return plan;
+}
+
+// How the plan is replayed: node k belongs to lane k % lanes, each lane of a stage is one chain graph on a stream of its own, and a
+// stage ends where the lanes have to meet -- in front of a node that waits for a node of ANOTHER lane of the same stage (a path between
+// two lanes of a stage contains such an edge, so edges the reduction dropped need no look).  Returns the first node of every stage.
+static inline std::vector<int> stage_starts(const Plan& plan, int lanes) {
+    std::vector<int> starts;
+    const int n = (int)plan.preds.size();
+    if (lanes < 1) lanes = 1;
+    for (int k = 0; k < n; ++k) {
+        bool cut = k == 0;
+        for (int i : plan.preds[k])
+            if (!cut && i >= starts.back() && i % lanes != k % lanes) cut = true;
+        if (cut) starts.push_back(k);
+    }
+    return starts;
+}
+
+// How many lanes a stage of `nodes` launches is replayed on.  Every lane beyond the first is one more graph launch and a fork / join
+// through events: 10-16 us of host time per replay, where a solve that no longer waits at a kernel boundary gains about 1.3 us
+// (docs/measurement_log.md: 20 captured steps on 4 lanes replay SLOWER than the chain, 35-step stages gain on 2 lanes and not on 4).
+// A lane pays for itself after about 10 launches; it is used when the stage has 16 for it.  Lane of node k: (k % lanes) % that many --
+// a stage has no conflict between two classes k % lanes, so they may share a lane in any combination.
+// UAVQP_CAPTURE_LANE_NODES (1..4096) overrides the 16: 1 puts every stage on as many lanes as it has launches for (tests, A/B runs).
+static constexpr int NODES_PER_LANE_MIN = 16;
+static inline int lane_nodes_from_env(const char* env) {
+    const int v = env && *env ? std::atoi(env) : 0;
+    return v >= 1 && v <= (int)NODES_MAX ? v : NODES_PER_LANE_MIN;
+}
+static inline int lanes_that_pay(int nodes, int lanes, int nodes_per_lane = NODES_PER_LANE_MIN) {
+    const int by_size = nodes / (nodes_per_lane < 1 ? 1 : nodes_per_lane);
+    return by_size < 1 ? 1 : (by_size < lanes ? by_size : lanes);
+}
+
+// The two knobs as the process environment has them NOW: read when a capture ends (uavqp_capture_end), never on a launch path.
+struct Knobs { int lanes, nodes_per_lane; };
+static inline Knobs knobs_from_environment() {
+    return Knobs{lanes_from_env(std::getenv("UAVQP_CAPTURE_LANES"), std::getenv("GPU_MAX_HW_QUEUES")), lane_nodes_from_env(std::getenv("UAVQP_CAPTURE_LANE_NODES"))};
+}
+
+}  // namespace uavqp_capture
