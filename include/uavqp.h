@@ -410,6 +410,12 @@ int uavqp_solve_backward_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_seg
  *   end, poly_traj.hpp:77-88).
  *   what: bit 0 position, bit 1 velocity, bit 2 acceleration; K = popcount(what) outputs per sample.
  *   d_out [n_traj][n_samples][K][3] float64 (pos, vel, acc order; xyz interleaved = Eigen::Vector3d).
+ * The segment rule in full (shared by the four samplers below; float64, the same subtractions in the same order): idx = 0; while idx < M and
+ * t > T_idx + 1e-4 (the sum rounded once, the comparison strict): t -= T_idx, ++idx; if idx == M: idx = M - 1, t = T_{M-1}.  So a sample exactly on
+ * a knot, or beyond it by no more than the slack, belongs to the EARLIER segment, whose polynomial is then evaluated past its end; t < 0 is
+ * segment 0 extrapolated backwards; every sample past the end is the end point of the last segment (velocity and acceleration there too).
+ * Only the low three bits of `what` count ((what & 7) == 0: UAVQP_ERR_INVALID_ARG).  A zero-segment trajectory gets rows of zeros.  n_samples == 0
+ * or n_traj == 0 writes nothing.  d_out needs no more than the 8-byte alignment of a double.
  * d_coeff / d_times / d_seg_offsets: the arrays of uavqp_solve_batch_device.  Asynchronous on the ctx stream. */
 int uavqp_eval_batch_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
                             const double* d_times, const double* d_coeff, int n_samples, double t0, double dt,
@@ -420,6 +426,10 @@ int uavqp_eval_batch_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segme
  * dt is the constant 0.01 and its t is ACCUMULATED in floating point: the sample count follows that accumulation exactly, so a
  * total time that is a multiple of dt -- the reference's own 1.0 s per segment -- gives the reference's count), length = sum of the
  * chord lengths between consecutive samples, mean velocity = length / total time.
+ * The positions themselves are evaluated at t_s = s * dt (the float64 product, not the accumulated t: the two differ by rounding only)
+ * through the segment rule of uavqp_eval_batch_device.  total time = the durations added in order.  One sample (dt >= total time): length 0.
+ * A zero-segment trajectory has total time 0: no sample, length 0, and mean velocity 0 / 0 = NaN -- the reference's length / total, unguarded.
+ * dt must be positive and finite (else UAVQP_ERR_INVALID_ARG).
  *   d_length / d_mean_vel [n_traj] float64, d_n_samples [n_traj] int32: any of them may be NULL.  Asynchronous on the ctx stream. */
 int uavqp_traj_length_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
                              const double* d_times, const double* d_coeff, double dt, double* d_length, double* d_mean_vel,
@@ -437,7 +447,12 @@ int uavqp_traj_length_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segm
  *   samples: t_s = t0 + s*dt, position and acceleration from the polynomials (segment rule of uavqp_eval_batch_device)
  *   d_obstacles [n_obs][3] float64
  *   d_first_hit [n_traj] int32: index of the first colliding sample, n_samples if the trajectory is collision-free
- *   d_flags     [n_traj][n_samples] uint8 (1 = collides), may be NULL */
+ *   d_flags     [n_traj][n_samples] uint8 (1 = collides), may be NULL (d_first_hit is the same with and without it)
+ * Degenerate attitudes: acc = (0, 0, -9.81) (no thrust: b3 is the zero vector) and acc = (a, 0, -9.81) (b3 parallel to x: b3 x (1,0,0) is the
+ * zero vector) leave axes that cannot be normalised.  The reference's E is then singular, E^-1 (o - p) is not a number and its test
+ * |E^-1 (o - p)| <= 1 is false for every point (the same in oracle/ellipsoid.c, whose division by the zero norm gives NaN axes): such a sample
+ * is reported COLLISION-FREE whatever the cloud holds, by both entry points.  A zero-segment trajectory has nothing to sample: flags 0,
+ * first_hit = n_samples. */
 int uavqp_ellipsoid_check_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
                                  const double* d_times, const double* d_coeff, int n_samples, double t0, double dt,
                                  const double* d_obstacles, int n_obs, double robot_r, double robot_h,
