@@ -344,9 +344,8 @@ int uavqp_cost_time_gradient_device(uavqp_ctx* ctx, int r, int n_traj, int unifo
  *   params           uavqp_default_time_opt_params fills the defaults; UAVQP_ERR_INVALID_ARG for a wrong struct_size, max_iters < 0,
  *                    time_weight <= 0, t_min <= 0, t_min > t_max, initial_step <= 0, armijo_c outside (0, 1), shrink outside (0, 1), grow < 1
  *                    or a non-finite value.  max_iters = 0: the plain solve, both objective columns equal.
- * Out of scope: corridor and general-rows solves (see above), velocity / acceleration limits inside the optimiser (run
- * uavqp_time_reallocate_device afterwards: it stretches the whole trajectory by one factor and keeps the distribution), multi-GPU (shard
- * the batch as for the solve: trajectories are independent). */
+ * Velocity / acceleration limits: uavqp_time_optimize_limits_device below.
+ * Out of scope: corridor and general-rows solves (see above), multi-GPU (shard the batch as for the solve: trajectories are independent). */
 typedef struct uavqp_time_opt_params {
     int32_t struct_size;
     int32_t max_iters;      /* trials per trajectory (default 24) */
@@ -389,8 +388,7 @@ int uavqp_time_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segm
  * UAVQP_ERR_INVALID_ARG: r not 3 / 4, a negative count, a NULL input, ragged without offsets or with max_segments < 1, uniform with
  * total_segments != uniform_segments * n_traj.  One launch, asynchronous on the ctx stream, no read-back (a first call of a given size
  * grows the ctx workspace).  Every output element is written once, in a fixed order of additions: the same bytes run to run.
- * Out of scope: corridor and general-rows solves (active sets), using this gradient inside uavqp_time_optimize_*, multi-GPU (shard the
- * batch as for the solve). */
+ * Out of scope: corridor and general-rows solves (active sets), multi-GPU (shard the batch as for the solve). */
 int uavqp_solve_backward_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
                                 const int32_t* d_seg_offsets, const double* d_waypoints, const double* d_times, const double* d_bc,
                                 const double* d_coeff, const int32_t* d_status, const double* d_grad_coeff, double* d_grad_times,
@@ -399,6 +397,71 @@ int uavqp_solve_backward_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_s
 int uavqp_solve_backward_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
                               const double* waypoints, const double* times, const double* bc, const double* coeff, const int32_t* status,
                               const double* grad_coeff, double* grad_times, double* grad_waypoints, double* grad_bc);
+
+/* Velocity / acceleration limit penalty of solved trajectories with its gradients (no reference counterpart; a soft penalty on sampled
+ * speed and acceleration in the style of GCOPTER / MINCO).  Per trajectory, K = samples_per_seg, tau_s = s / K, trapezoid weights
+ * om_0 = om_K = 1/2, om_s = 1 otherwise, pos(x) = max(0, x):
+ *   Phi = sum_i (T_i / K) sum_{s=0..K} om_s [ weight_v pos(|v_i(tau_s T_i)|^2 / v_max^2 - 1)^3 + weight_a pos(|a_i(tau_s T_i)|^2 / a_max^2 - 1)^3 ]
+ * |.| the 3-axis norm of the segment's own polynomial at segment-local time.  The ratios are dimensionless: Phi has the unit of
+ * time_weight * T, the two weights are comparable with uavqp_time_opt_params.time_weight; the cube makes Phi twice continuously differentiable.
+ *   d_penalty     [n_traj] Phi
+ *   d_grad_coeff  layout of coeff ([axis][segment][2r] per trajectory): dPhi/dc at FIXED durations
+ *   d_grad_times  [sum_b M_b]: the EXPLICIT dPhi/dT_i at FIXED coefficients (the sampling times scale with T_i), with pv, pa the pos() terms:
+ *                 Phi_i / T_i + (T_i / K) sum_s om_s tau_s [3 weight_v pv^2 * 2 v.a / v_max^2 + 3 weight_a pa^2 * 2 a.j / a_max^2]
+ *   d_peak        [n_traj][2]: the largest sampled |v| / v_max and |a| / a_max of the trajectory
+ * Each output may be NULL (all NULL: UAVQP_OK, nothing done).  For coefficients of uavqp_solve_batch_device at d_times, the TOTAL gradient
+ * of Phi in the durations is
+ *       d_grad_times + uavqp_solve_backward_device(g = d_grad_coeff).grad_times.
+ *   d_status      [n_traj] status of the solve, or NULL (every trajectory counts as solved).  A trajectory whose status is not UAVQP_SOLVED,
+ *                 or with M < 1, gets zeros everywhere.
+ * Every output element is written exactly once, zeros included: no memset is needed beforehand.  The additions are in a fixed order: the
+ * same bytes run to run and for any grid.  One launch, asynchronous on the ctx stream, no allocation, no read-back.
+ * UAVQP_ERR_INVALID_ARG: r not 3 / 4, a negative count, a wrong struct_size, samples_per_seg < 1, a limit or weight that is not finite, a
+ * limit <= 0, a weight < 0, NULL times / coeff, ragged without offsets. */
+typedef struct uavqp_limit_params {
+    int32_t struct_size;
+    int32_t samples_per_seg;   /* K: K + 1 sample points per segment (default 8) */
+    double v_max;              /* speed limit, m/s (default 7: uavqp_default_pipeline_params) */
+    double a_max;              /* acceleration limit, m/s^2 (default 10) */
+    double weight_v;           /* >= 0 (default 1e3) */
+    double weight_a;           /* >= 0 (default 1e3) */
+} uavqp_limit_params;
+void uavqp_default_limit_params(uavqp_limit_params* out);   /* callable without a device */
+int uavqp_limit_penalty_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
+                               const double* d_coeff, const int32_t* d_status, const uavqp_limit_params* params, double* d_penalty,
+                               double* d_grad_coeff, double* d_grad_times, double* d_peak);
+/* The same from HOST pointers (H2D copy, run, D2H copy, synchronous). */
+int uavqp_limit_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
+                             const double* coeff, const int32_t* status, const uavqp_limit_params* params, double* penalty,
+                             double* grad_coeff, double* grad_times, double* peak);
+
+/* uavqp_time_optimize_device with the limit penalty inside the objective: per trajectory
+ *       minimise  f(T) = J(T) + time_weight * sum_i T_i + Phi(c*(T), T)     subject to  t_min <= T_i <= t_max.
+ * c*(T) is still the minimiser of J alone (the QP does not see the penalty), so dJ/dT_i = -H_i still holds and
+ *       df/dT_i = -H_i + time_weight + d_grad_times_i + uavqp_solve_backward_device(g = d_grad_coeff).grad_times_i
+ * with the two penalty gradients above.  Method, parameters, Armijo rule, projection, arguments and outputs are those of
+ * uavqp_time_optimize_device, f and its gradient replaced; host sequencing
+ *       clamp, solve, [penalty, backward], step, max_iters x { solve at the trial durations, [penalty, backward], step }, solve
+ * with every decision on the device, nothing read back, the number of launches depending on max_iters alone.  d_objective_out holds f
+ * INCLUDING Phi; d_coeff_out is bit for bit uavqp_solve_batch_device at the durations handed back.  With weight_v = weight_a = 0, or limits
+ * nothing reaches, every output equals that of uavqp_time_optimize_device byte for byte.
+ *   limits       validated as for uavqp_limit_penalty_device
+ *   d_peak_out   [n_traj][2] (may be NULL): sampled |v| / v_max and |a| / a_max at the durations handed back (zeros for a trajectory that is
+ *                not UAVQP_SOLVED)
+ * THE PENALTY IS SOFT: at finite weights the result may exceed the limits.  Expect sampled peaks a few per cent above a limit that binds (a
+ * CPU simulation of this method at weight 1e3 left 3-12 % with limits set to 0.7 x the unconstrained peak).  The hard guarantee remains
+ * uavqp_time_reallocate_device afterwards, which then has far less to stretch.
+ * Out of scope: corridor and general-rows solves, multi-GPU (shard the batch as for the solve). */
+int uavqp_time_optimize_limits_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                                      const int32_t* d_seg_offsets, const double* d_waypoints, double* d_times, const double* d_bc,
+                                      const uavqp_time_opt_params* params, double* d_coeff_out, int32_t* d_status_out,
+                                      double* d_objective_out, int32_t* d_accepted_out, const uavqp_limit_params* limits,
+                                      double* d_peak_out);
+/* The same from HOST pointers (as uavqp_time_optimize_host). */
+int uavqp_time_optimize_limits_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                                    const double* waypoints, double* times, const double* bc, const uavqp_time_opt_params* params,
+                                    double* coeff_out, int32_t* status_out, double* objective_out, int32_t* accepted_out,
+                                    const uavqp_limit_params* limits, double* peak_out);
 
 /* Batched evaluation of solved trajectories on a uniform time grid.
  * Replaces, for a whole batch, PolyTraj::evaluatePos / evaluateVel / evaluateAcc

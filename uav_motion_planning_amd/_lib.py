@@ -52,6 +52,11 @@ SYMBOLS = (
     "uavqp_time_optimize_host",
     "uavqp_solve_backward_device",
     "uavqp_solve_backward_host",
+    "uavqp_default_limit_params",
+    "uavqp_limit_penalty_device",
+    "uavqp_limit_penalty_host",
+    "uavqp_time_optimize_limits_device",
+    "uavqp_time_optimize_limits_host",
     "uavqp_eval_batch_device",
     "uavqp_traj_length_device",
     "uavqp_ellipsoid_check_device",
@@ -118,6 +123,12 @@ class TimeOptParams(ctypes.Structure):
                 ("grow", ctypes.c_double)]
 
 
+class LimitParams(ctypes.Structure):
+    """uavqp_limit_params of include/uavqp.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("samples_per_seg", ctypes.c_int32), ("v_max", ctypes.c_double), ("a_max", ctypes.c_double),
+                ("weight_v", ctypes.c_double), ("weight_a", ctypes.c_double)]
+
+
 def build(force=False):
     """Compile csrc/*.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
     csrc = os.path.join(_PKG, "csrc")
@@ -176,6 +187,14 @@ def lib():
     L.uavqp_time_optimize_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, ctypes.POINTER(TimeOptParams), dp, ip, dp, ip]
     L.uavqp_solve_backward_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, dp, ip, dp, dp, dp, dp]
     L.uavqp_solve_backward_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, dp, ip, dp, dp, dp, dp]
+    L.uavqp_default_limit_params.argtypes = [ctypes.POINTER(LimitParams)]
+    L.uavqp_default_limit_params.restype = None
+    L.uavqp_limit_penalty_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, ctypes.POINTER(LimitParams), dp, dp, dp, dp]
+    L.uavqp_limit_penalty_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, ctypes.POINTER(LimitParams), dp, dp, dp, dp]
+    L.uavqp_time_optimize_limits_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, ctypes.POINTER(TimeOptParams), dp, ip, dp, ip,
+                                                    ctypes.POINTER(LimitParams), dp]
+    L.uavqp_time_optimize_limits_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, ctypes.POINTER(TimeOptParams), dp, ip, dp, ip,
+                                                  ctypes.POINTER(LimitParams), dp]
     L.uavqp_eval_batch_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, i32, dp]
     L.uavqp_traj_length_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ctypes.c_double, dp, dp, ip]
     L.uavqp_ellipsoid_check_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, dp, i32,

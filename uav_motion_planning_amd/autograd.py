@@ -7,6 +7,11 @@ forward = uavqp_solve_batch_device, backward = uavqp_solve_backward_device (incl
 The gradients are the part THROUGH the minimiser; a loss that also depends on `times` explicitly (e.g. through sampling times that scale
 with the durations) gets that part from torch's own graph, as for any other operation.  Inputs: contiguous float64 tensors on the
 ctx's device.  No CPU path: without libuavqp.so or a GPU the call raises.  torch is imported when the operation is first used.
+
+    phi = limit_penalty(ctx, r, coeff, times, uniform_segments=8, v_max=3.0)      # [n_traj]
+    phi.sum().backward()            # coeff.grad, times.grad (the explicit part); through solve_batch: the total gradient
+
+forward = uavqp_limit_penalty_device, which also writes both gradients; backward scales them by the incoming gradient per trajectory.
 """
 from . import _lib
 
@@ -61,6 +66,53 @@ def _function():
     return _Function
 
 
+_Penalty = None
+
+
+def _penalty_function():
+    global _Penalty
+    if _Penalty is not None:
+        return _Penalty
+    import torch
+
+    class LimitPenalty(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, coeff, times, ctx, r, seg_offsets, uniform_segments, status, limits):
+            for name, t in (("coeff", coeff), ("times", times)):
+                if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+                    raise ValueError(f"limit_penalty: {name} must be a contiguous float64 tensor on the GPU")
+            total = times.numel()
+            n_traj = total // uniform_segments if uniform_segments > 0 else seg_offsets.numel() - 1
+            if coeff.numel() != 3 * 2 * r * total:
+                raise ValueError("limit_penalty: coeff must hold 3 * 2r doubles per segment")
+            phi = torch.empty(n_traj, dtype=torch.float64, device=times.device)
+            g_c = torch.empty_like(coeff)
+            g_t = torch.empty_like(times)
+            ctx.set_stream(torch.cuda.current_stream(times.device).cuda_stream)
+            ctx.limit_penalty_device(r, n_traj, uniform_segments, seg_offsets, times.detach(), coeff.detach(), status=status, penalty=phi,
+                                     grad_coeff=g_c, grad_times=g_t, **limits)
+            if uniform_segments > 0:
+                counts = torch.full((n_traj,), uniform_segments, dtype=torch.int64, device=times.device)
+            else:
+                counts = (seg_offsets[1:] - seg_offsets[:-1]).to(torch.int64)
+            fctx.save_for_backward(g_c, g_t, counts)
+            fctx.nc = 3 * 2 * r
+            return phi
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable   # the gradients come from a raw kernel: no second derivative through them
+        def backward(fctx, grad_phi):
+            g_c, g_t, counts = fctx.saved_tensors
+            need_c, need_t = fctx.needs_input_grad[:2]
+            per_seg = torch.repeat_interleave(grad_phi, counts)                 # [sum M]
+            out_c = g_c * torch.repeat_interleave(grad_phi, counts * fctx.nc) if need_c else None
+            out_t = g_t * per_seg if need_t else None
+            return out_c, out_t, None, None, None, None, None, None
+
+    _Penalty = LimitPenalty
+    return _Penalty
+
+
 def solve_batch(ctx, r, waypoints, times, bc, seg_offsets=None, uniform_segments=0, max_segments=0, check_status=False, return_status=False):
     """Differentiable uavqp_solve_batch_device.  ctx: a Context on the tensors' device.  waypoints [sum (M_b + 1)][3], times [sum M_b],
     bc [n_traj][2][r-1][3]; seg_offsets: int32 device tensor [n_traj + 1] (ragged; max_segments = the longest trajectory, read back from
@@ -76,3 +128,14 @@ def solve_batch(ctx, r, waypoints, times, bc, seg_offsets=None, uniform_segments
         max_segments = uniform_segments
     coeff, status = _function().apply(waypoints, times, bc, ctx, int(r), seg_offsets, int(uniform_segments), int(max_segments), bool(check_status))
     return (coeff, status) if return_status else coeff
+
+
+def limit_penalty(ctx, r, coeff, times, seg_offsets=None, uniform_segments=0, status=None, **limits):
+    """Differentiable uavqp_limit_penalty_device: the velocity / acceleration limit penalty [n_traj] of coeff (layout of solve_batch's
+    result) at the durations `times` [sum M_b].  limits: fields of uavqp_limit_params that differ from the defaults (v_max, a_max,
+    weight_v, weight_a, samples_per_seg).  status: optional int32 status tensor of the solve (trajectories that are not SOLVED give zero).
+    The gradient in `times` is the explicit part; with coeff = solve_batch(..., times, ...) torch adds the part through the solve, so
+    limit_penalty(solve_batch(...), times).sum().backward() leaves the total gradient in times.grad."""
+    if uniform_segments <= 0 and seg_offsets is None:
+        raise ValueError("limit_penalty: ragged batches need seg_offsets")
+    return _penalty_function().apply(coeff, times, ctx, int(r), seg_offsets, int(uniform_segments), status, dict(limits))

@@ -148,6 +148,50 @@ class TrajOptimizer {
         for (int32_t s : status_) if (s != UAVQP_SOLVED) return false;
         return true;
     }
+    // The same with the soft velocity / acceleration limit penalty inside the objective (uavqp_time_optimize_limits_host): objective()
+    // includes the penalty, peak() = [n_traj][2] sampled |v| / v_max, |a| / a_max at the result.  The penalty is soft: a peak may end
+    // above 1 (include/uavqp.h); uavqp_time_reallocate_device afterwards is the hard guarantee.
+    bool optimizeTime(const uavqp_limit_params& limits, double time_weight = 0.0, const uavqp_time_opt_params* params = nullptr) {
+        if (n_traj_ <= 0 || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_])) return false;
+        if (!lo_.empty() || rows_k_ > 0) {
+            std::cout << "solver solve failed! (optimizeTime: corridor and general-rows problems are out of scope)" << std::endl;
+            return false;
+        }
+        if (!ensureContext()) return false;
+        if (bc_.empty()) bc_.assign(static_cast<size_t>(n_traj_) * 2 * (order_ - 1) * 3, 0.0);
+        uavqp_time_opt_params pp;
+        if (params) pp = *params; else uavqp_default_time_opt_params(&pp);
+        if (time_weight > 0.0) pp.time_weight = time_weight;
+        coef_.assign(static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_], 0.0);
+        status_.assign(n_traj_, 0);
+        objective_.assign(static_cast<size_t>(2) * n_traj_, 0.0);
+        accepted_.assign(n_traj_, 0);
+        peak_.assign(static_cast<size_t>(2) * n_traj_, 0.0);
+        const int rc = uavqp_time_optimize_limits_host(ctx_, order_, n_traj_, 0, 0, seg_offsets_.data(), wp_.data(), T_.data(), bc_.data(), &pp,
+                                                       coef_.data(), status_.data(), objective_.data(), accepted_.data(), &limits, peak_.data());
+        if (rc != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            return false;
+        }
+        for (int32_t s : status_) if (s != UAVQP_SOLVED) return false;
+        return true;
+    }
+    const std::vector<double>& peak() const { return peak_; }
+    // Limit penalty per trajectory of the stored coefficients at the stored durations (after solve() or optimizeTime();
+    // uavqp_limit_penalty_host).  A trajectory that did not solve carries zero.  Empty on failure.
+    std::vector<double> getLimitPenalty(const uavqp_limit_params& limits) {
+        std::vector<double> phi;
+        if (n_traj_ <= 0 || !ctx_ || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_]) ||
+            coef_.size() != static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_] || status_.size() != static_cast<size_t>(n_traj_))
+            return phi;
+        phi.assign(n_traj_, 0.0);
+        if (uavqp_limit_penalty_host(ctx_, order_, n_traj_, 0, seg_offsets_.data(), T_.data(), coef_.data(), status_.data(), &limits, phi.data(),
+                                     nullptr, nullptr, nullptr) != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            phi.clear();
+        }
+        return phi;
+    }
     const std::vector<double>& objective() const { return objective_; }
     const std::vector<int32_t>& acceptedTrials() const { return accepted_; }
     // Control cost c' P c (integral of the squared r-th derivative, three axes) per trajectory of the current waypoints at the current
@@ -373,7 +417,7 @@ class TrajOptimizer {
     std::vector<double> wp_, T_, bc_, coef_, lo_, hi_, pipe_lo_, pipe_hi_, row_tau_, row_lo_, row_hi_;
     std::vector<int32_t> row_deriv_, first_hit_, repair_deriv_;
     std::vector<double> repair_tau_, repair_lo_, repair_hi_;
-    std::vector<double> objective_;
+    std::vector<double> objective_, peak_;
     std::vector<int32_t> accepted_;
     int rows_k_ = 0;
     uavqp_pipeline_result pipe_result_{};

@@ -93,3 +93,10 @@
 // ---- qp_adjoint.h: backward pass of the equality-constrained solve
 #define UAVQP_ADJOINT_R(R_) UAVQP_INST __global__ void uavqp::solve_backward_kernel<R_>(uavqp::AdjointArgs);
 #define UAVQP_INSTANCES_ADJOINT UAVQP_ADJOINT_R(3) UAVQP_ADJOINT_R(4)
+
+// ---- qp_limits.h: velocity / acceleration limit penalty with its gradients, the steps of the limit-aware duration optimiser
+#define UAVQP_LIMITS_R(R_)                                                                      \
+    UAVQP_INST __global__ void uavqp::limit_penalty_kernel<R_>(uavqp::LimitArgs);                  \
+    UAVQP_INST __global__ void uavqp::time_opt_step_kernel<R_, true, true>(uavqp::TimeOptArgs);    \
+    UAVQP_INST __global__ void uavqp::time_opt_step_kernel<R_, false, true>(uavqp::TimeOptArgs);
+#define UAVQP_INSTANCES_LIMITS UAVQP_LIMITS_R(3) UAVQP_LIMITS_R(4)

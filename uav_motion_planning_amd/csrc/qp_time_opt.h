@@ -134,6 +134,9 @@ __global__ __launch_bounds__(64) void cost_grad_kernel(CostGradArgs a) {
 //   ITER   the trial was solved into `coeff`: accepted iff its status is SOLVED and f_trial <= f_best - armijo * sum_i d_i (u_i - u_trial_i)
 //          (sufficient decrease along the projection arc) -> durations, f_best, gradient replaced, alpha *= grow; else alpha *= shrink.
 //          Then the next trial from the best point (not after the last iteration).
+// LIMITS (uavqp_time_optimize_limits_device; kernels of qp_limits.h run between the solve and the step): f gains the limit penalty
+//          phi[b] of the point the last solve ran at, dJ/dT_i its two gradient parts there, lim_explicit[i] + lim_through[i] (the explicit
+//          one and the one through c*(T), qp_adjoint.h).  LIMITS = false reads none of the three and is the code it was.
 // ---------------------------------------------------------------------------------------------------
 struct TimeOptArgs {
     int n_traj, uniform;
@@ -151,6 +154,9 @@ struct TimeOptArgs {
     int32_t* accepted;        // [n_traj] or null
     double w, t_min, t_max, initial_step, armijo, shrink, grow;
     int propose;              // 0: last step, no further trial
+    const double* phi;            // LIMITS only: [n_traj] penalty at the point of `coeff`
+    const double* lim_explicit;   // LIMITS only: [total] dPhi/dT_i at fixed coefficients
+    const double* lim_through;    // LIMITS only: [total] dPhi/dT_i through the minimiser
 };
 
 template <int R>
@@ -178,7 +184,7 @@ __global__ __launch_bounds__(64) void time_opt_clamp_kernel(TimeOptArgs a) {
     }
 }
 
-template <int R, bool INIT>
+template <int R, bool INIT, bool LIMITS = false>
 __global__ __launch_bounds__(64) void time_opt_step_kernel(TimeOptArgs a) {
     constexpr int NC = 2 * R, LPT = TOPT_LPT;
     const int sub = threadIdx.x % LPT;
@@ -208,7 +214,8 @@ __global__ __launch_bounds__(64) void time_opt_step_kernel(TimeOptArgs a) {
             }
         J = topt_group_sum(J);
         sumT = topt_group_sum(sumT);
-        const double f_new = fma(a.w, sumT, J);
+        double f_new = fma(a.w, sumT, J);
+        if (LIMITS) f_new += (solved && act) ? a.phi[b] : 0.0;
 
         double f_best, alpha = 0.0;
         bool accept;
@@ -225,7 +232,9 @@ __global__ __launch_bounds__(64) void time_opt_step_kernel(TimeOptArgs a) {
         }
         if (accept)
             for (int i = sub; i < M; i += LPT) {
-                a.gbest[s0 + i] = -topt_segment_H<R>(a.coeff + (size_t)3 * NC * s0 + (size_t)i * NC, axs);
+                double gT = -topt_segment_H<R>(a.coeff + (size_t)3 * NC * s0 + (size_t)i * NC, axs);
+                if (LIMITS) gT += a.lim_explicit[s0 + i] + a.lim_through[s0 + i];
+                a.gbest[s0 + i] = gT;
                 if (!INIT) a.times[s0 + i] = a.trial[s0 + i];
             }
         if (live && sub == 0) {

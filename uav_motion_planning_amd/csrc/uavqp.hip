@@ -32,6 +32,7 @@
 #include "obstacle_grid.h"
 #include "qp_time_opt.h"
 #include "qp_adjoint.h"
+#include "qp_limits.h"
 // Measured-slower alternatives kept as bit-identical cross-checks: `make experiments` (-DUAVQP_EXPERIMENTS) only
 #ifdef UAVQP_EXPERIMENTS
 #include "cloud_grid2d.h"
@@ -55,6 +56,7 @@ UAVQP_INSTANCES_ROWS_DUAL
 UAVQP_INSTANCES_CLOUD
 UAVQP_INSTANCES_TIMEOPT
 UAVQP_INSTANCES_ADJOINT
+UAVQP_INSTANCES_LIMITS
 #endif
 
 namespace uavqp {
@@ -1874,6 +1876,11 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
 // Backward pass of the equality-constrained solve
 // ===================================================================================================
 #include "uavqp_adjoint.h"
+
+// ===================================================================================================
+// Velocity / acceleration limit penalty and the limit-aware duration optimiser
+// ===================================================================================================
+#include "uavqp_limits.h"
 
 // ===================================================================================================
 // N3: quadrotor_msgs/PolynomialTrajectory packer (host only)

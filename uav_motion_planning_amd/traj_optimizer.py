@@ -152,6 +152,80 @@ class Context:
         _lib.check(rc, "uavqp_time_optimize_host")
         return times, coeff, status, objective, accepted
 
+    @staticmethod
+    def _limit_params(limits):
+        lp = _lib.LimitParams()
+        _lib.lib().uavqp_default_limit_params(ctypes.byref(lp))
+        for k, v in limits.items():
+            if not hasattr(lp, k) or k == "struct_size":
+                raise ValueError(f"unknown uavqp_limit_params field {k!r}")
+            setattr(lp, k, v)
+        return lp
+
+    def limit_penalty_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, status=None, penalty=None, grad_coeff=None,
+                             grad_times=None, peak=None, **limits):
+        """uavqp_limit_penalty_device on device buffers: the velocity / acceleration limit penalty [n_traj] of solved trajectories, its
+        gradient in the coefficients at fixed durations (layout of coeff), its EXPLICIT gradient in the durations at fixed coefficients
+        [sum M], and the sampled peaks |v| / v_max, |a| / a_max [n_traj][2]; each output may be None.  status (the solve's, optional):
+        trajectories that are not SOLVED get zeros.  limits: fields of uavqp_limit_params that differ from uavqp_default_limit_params.
+        Asynchronous."""
+        lp = self._limit_params(limits)
+        rc = _lib.lib().uavqp_limit_penalty_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff), _ptr(status),
+                                                   ctypes.byref(lp), _ptr(penalty), _ptr(grad_coeff), _ptr(grad_times), _ptr(peak))
+        _lib.check(rc, "uavqp_limit_penalty_device")
+
+    def limit_penalty_host(self, r, seg_offsets, times, coeff, uniform_segments=0, status=None, **limits):
+        """numpy in / numpy out (synchronous).  Returns (penalty [n_traj], grad_coeff, grad_times [sum M], peak [n_traj][2])."""
+        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
+        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total and coeff.size == 3 * 2 * r * total
+        lp = self._limit_params(limits)
+        penalty = np.zeros(n_traj, dtype=np.float64)
+        g_c = np.zeros_like(coeff)
+        g_t = np.zeros(total, dtype=np.float64)
+        peak = np.zeros((n_traj, 2), dtype=np.float64)
+        rc = _lib.lib().uavqp_limit_penalty_host(self._h, r, n_traj, uniform_segments, _ptr(so), _ptr(times), _ptr(coeff), _ptr(status),
+                                                 ctypes.byref(lp), _ptr(penalty), _ptr(g_c), _ptr(g_t), _ptr(peak))
+        _lib.check(rc, "uavqp_limit_penalty_host")
+        return penalty, g_c, g_t, peak
+
+    def time_optimize_limits_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc,
+                                    coeff_out, status_out, objective_out, accepted_out=None, peak_out=None, limits=None, **params):
+        """uavqp_time_optimize_limits_device on device buffers: time_optimize_device with the limit penalty inside the objective
+        (objective_out includes it); peak_out [n_traj][2] receives the sampled |v| / v_max, |a| / a_max at the result.  limits: dict of
+        uavqp_limit_params fields; params: fields of uavqp_time_opt_params.  The penalty is soft (include/uavqp.h).  Asynchronous."""
+        pp = self._time_opt_params(params)
+        lp = self._limit_params(limits or {})
+        rc = _lib.lib().uavqp_time_optimize_limits_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments),
+                                                          _ptr(seg_offsets), _ptr(waypoints), _ptr(times), _ptr(bc), ctypes.byref(pp),
+                                                          _ptr(coeff_out), _ptr(status_out), _ptr(objective_out), _ptr(accepted_out),
+                                                          ctypes.byref(lp), _ptr(peak_out))
+        _lib.check(rc, "uavqp_time_optimize_limits_device")
+
+    def time_optimize_limits_host(self, r, seg_offsets, waypoints, times, bc, limits, uniform_segments=0, **params):
+        """numpy in / numpy out (synchronous).  Returns (times, coeff_flat, status, objective [n_traj][2], accepted, peak [n_traj][2])."""
+        waypoints = np.ascontiguousarray(waypoints, dtype=np.float64)
+        times = np.array(times, dtype=np.float64).ravel()   # a copy: the call updates it in place
+        bc = np.ascontiguousarray(bc, dtype=np.float64)
+        so, n_traj, total, mmax = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total
+        assert waypoints.size == 3 * (total + n_traj), "waypoints must hold sum(M_b + 1) xyz rows"
+        assert bc.size == n_traj * 2 * (r - 1) * 3
+        pp = self._time_opt_params(params)
+        lp = self._limit_params(limits)
+        coeff = np.zeros(3 * 2 * r * total, dtype=np.float64)
+        status = np.zeros(n_traj, dtype=np.int32)
+        objective = np.zeros((n_traj, 2), dtype=np.float64)
+        accepted = np.zeros(n_traj, dtype=np.int32)
+        peak = np.zeros((n_traj, 2), dtype=np.float64)
+        rc = _lib.lib().uavqp_time_optimize_limits_host(self._h, r, n_traj, uniform_segments, max(mmax, 1), _ptr(so), _ptr(waypoints), _ptr(times),
+                                                        _ptr(bc), ctypes.byref(pp), _ptr(coeff), _ptr(status), _ptr(objective), _ptr(accepted),
+                                                        ctypes.byref(lp), _ptr(peak))
+        _lib.check(rc, "uavqp_time_optimize_limits_host")
+        return times, coeff, status, objective, accepted, peak
+
     def solve_backward_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc, coeff,
                               grad_coeff, grad_times=None, grad_waypoints=None, grad_bc=None, status=None):
         """uavqp_solve_backward_device on device buffers: for grad_coeff = dPhi/dcoeff (layout of coeff) the vector-Jacobian products
@@ -478,7 +552,10 @@ class TrajOptimizer:
     solve() -> bool                  True iff every trajectory solved (statuses in .status)
     optimizeTime(time_weight, ...)   equality-constrained problems only: minimises cost + time_weight * sum T over the durations
                                      (uavqp_time_optimize_host), stores the optimised allocation (getTimeAllocation) and the
-                                     coefficients at it; objective [n_traj][2] (start, result) in .objective
+                                     coefficients at it; objective [n_traj][2] (start, result) in .objective.  limits = dict of
+                                     uavqp_limit_params fields: the soft velocity / acceleration penalty joins the objective
+                                     (uavqp_time_optimize_limits_host), .peak [n_traj][2] = sampled |v| / v_max, |a| / a_max at the result
+    getLimitPenalty(**limits)        [n_traj] limit penalty of the stored coefficients at the stored durations
     backward(grad_coeff)             equality-constrained problems only, after solve(): (grad_times, grad_waypoints, grad_bc) of a loss
                                      with d loss / d getPolyCoeff() = grad_coeff, through the solve
     getCost()                        [n_traj] control cost c' P c of the stored coefficients at the stored durations
@@ -497,6 +574,7 @@ class TrajOptimizer:
         self.status = np.zeros(0, dtype=np.int32)
         self.iterations = np.zeros(0, dtype=np.int32)
         self.objective = np.zeros((0, 2))
+        self.peak = np.zeros((0, 2))
 
     def setWaypoints(self, xyz, wp_offsets=None, n_waypoints=None):
         self._wp = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
@@ -556,9 +634,11 @@ class TrajOptimizer:
             self._coef, self.status = self._ctx.solve_batch_host(self._r, self._so, self._wp, self._T, bc)
         return bool(np.all(self.status == _lib.UAVQP_SOLVED))
 
-    def optimizeTime(self, time_weight=None, **params):
+    def optimizeTime(self, time_weight=None, limits=None, **params):
         """Optimises the stored time allocation (the reference's equality rows only: a corridor or rows set raises ValueError).
-        True iff every trajectory is solved at the optimised durations; getPolyCoeff() is the solve at getTimeAllocation()."""
+        True iff every trajectory is solved at the optimised durations; getPolyCoeff() is the solve at getTimeAllocation().
+        limits: None, or a dict of uavqp_limit_params fields ({} = the defaults) -- the soft limit penalty joins the objective and
+        .peak holds the sampled |v| / v_max, |a| / a_max at the result (they may exceed 1: include/uavqp.h)."""
         if self._lo is not None or self._rows is not None:
             raise ValueError("optimizeTime: corridor and general-rows problems are out of scope (include/uavqp.h)")
         if self._wp is None or self._T is None:
@@ -572,9 +652,20 @@ class TrajOptimizer:
             self._ctx.set_settings(warm_start=1, eps_prim_inf=1e-3, max_iter=1000)
         if time_weight is not None:
             params["time_weight"] = float(time_weight)
+        if limits is not None:
+            self._T, self._coef, self.status, self.objective, self.iterations, self.peak = self._ctx.time_optimize_limits_host(
+                self._r, self._so, self._wp, self._T, bc, dict(limits), **params)
+            return bool(np.all(self.status == _lib.UAVQP_SOLVED))
         self._T, self._coef, self.status, self.objective, self.iterations = self._ctx.time_optimize_host(
             self._r, self._so, self._wp, self._T, bc, **params)
         return bool(np.all(self.status == _lib.UAVQP_SOLVED))
+
+    def getLimitPenalty(self, **limits):
+        """[n_traj] limit penalty of the stored coefficients at the stored durations (after solve() or optimizeTime());
+        limits: fields of uavqp_limit_params that differ from the defaults.  Trajectories that did not solve carry zero."""
+        if self._ctx is None or self._coef.size != 3 * 2 * self._r * int(self._so[-1]) or self.status.size != self._so.size - 1:
+            raise _lib.UavqpError("getLimitPenalty: no solved coefficients (call solve() or optimizeTime() first)")
+        return self._ctx.limit_penalty_host(self._r, self._so, self._T, self._coef, status=self.status, **limits)[0]
 
     def backward(self, grad_coeff):
         """After solve() of an equality-constrained problem: (grad_times, grad_waypoints, grad_bc) as numpy for grad_coeff = dPhi/dcoeff in
