@@ -463,6 +463,88 @@ int uavqp_time_optimize_limits_host(uavqp_ctx* ctx, int r, int n_traj, int unifo
                                     double* coeff_out, int32_t* status_out, double* objective_out, int32_t* accepted_out,
                                     const uavqp_limit_params* limits, double* peak_out);
 
+/* Signed Euclidean distance field of an occupancy grid, and the clearance penalty of solved trajectories against it.  Replaces, for one
+ * map held on the device, plan_env/SDFMap: cloudCallback (src/planner/plan_env/src/sdf_map.cpp:836-927), updateESDF3d (:193-327) and
+ * getDistWithGradTrilinear (include/plan_env/sdf_map.h:328-373).
+ * A uavqp_esdf is opaque and owns its device buffers, all allocated by uavqp_esdf_create: nothing is allocated afterwards, every other
+ * entry is asynchronous on the ctx stream and reads nothing back.  Grid: dims voxels of edge `resolution` from `origin`; arrays are
+ * [nx][ny][nz], z fastest (the reference's toAddress).
+ *   create     UAVQP_ERR_INVALID_ARG: a dimension below 1 or above 1024, more than 2^30 voxels, an origin that is not finite, resolution or
+ *              max_dist not finite and positive.  The grid starts all free.  destroy synchronises the ctx stream first.
+ *   set_occupancy_device   d_occ [nx][ny][nz] bytes: 0 free, non-zero occupied (stored as given).
+ *   rasterize_cloud_device cloudCallback :858-906 without its camera window.  For every point p of d_obstacles [n_obs][3] and every integer
+ *              (x, y, z) with |x|, |y| <= inflate_xy and |z| <= inflate_z: q = p + (x, y, z) * resolution in float64,
+ *              id = floor((q - origin) * (1 / resolution)) per axis (the reference's posToIndex: a multiplication with the inverse); if all
+ *              three indices lie inside the grid that voxel is set to 1.  The reference's values are inflate_xy =
+ *              ceil(obstacles_inflation / resolution) and inflate_z = 1.  clear_first != 0 zeroes the grid before marking, 0 accumulates.
+ *              Marking is idempotent (plain byte stores of 1): the result does not depend on the order of the points.
+ *              UAVQP_ERR_INVALID_ARG: a negative inflation, one above 1024, a negative count.
+ *   update_device   updateESDF3d over the whole grid.  sq_pos[v] = the exact integer squared voxel distance from v to the nearest occupied
+ *              voxel, sq_neg[v] = the same to the nearest free voxel; both int32, INT32_MAX where no such voxel exists.
+ *              d_pos = min(resolution * sqrt(sq_pos), max_dist), d_neg likewise; dist = d_pos if d_neg == 0, else d_pos - d_neg + resolution
+ *              (:316-326).  max_dist stands in for the reference's unguarded "no obstacle" value (10000 is its buffer fill, :89-91).
+ *              The integer fields are exactly the Euclidean transform (three separable passes in integers).
+ *   read_device     copies of occupancy / sq_pos / sq_neg / dist into caller buffers of n voxels each; each may be NULL.
+ *   query_device    getDistWithGradTrilinear for d_pts [n][3]: d_dist [n], d_grad [n][3], d_inside [n] bytes, each may be NULL.
+ *              Outside the map (any axis < origin + 1e-4 or > origin + dims * resolution - 1e-4, or not a number): dist = 0, grad = 0,
+ *              inside = 0.  Otherwise idx = floor((pos - 0.5 res - origin) / res), diff = (pos - ((idx + 0.5) res + origin)) / res (both
+ *              divisions as multiplications with 1 / res), the eight values at idx + {0, 1}^3 with every index clamped into the grid
+ *              (boundIndex), and the reference's interpolation and three gradient expressions (:355-370).  The gradient is discontinuous
+ *              across the faces diff = 0.
+ *   query_host      the same from HOST pointers (H2D copy, run, D2H copy, synchronous); the map stays a device object.
+ * UAVQP_ERR_INVALID_ARG everywhere: a NULL esdf, a map of another device; query, penalty, and read of a field before the first update. */
+typedef struct uavqp_esdf uavqp_esdf;
+int uavqp_esdf_create(uavqp_ctx* ctx, const int32_t dims[3], const double origin[3], double resolution, double max_dist, uavqp_esdf** out);
+int uavqp_esdf_destroy(uavqp_ctx* ctx, uavqp_esdf* esdf);
+int uavqp_esdf_set_occupancy_device(uavqp_ctx* ctx, uavqp_esdf* esdf, const uint8_t* d_occ);
+int uavqp_esdf_rasterize_cloud_device(uavqp_ctx* ctx, uavqp_esdf* esdf, const double* d_obstacles, int n_obs, int inflate_xy, int inflate_z,
+                                      int clear_first);
+int uavqp_esdf_update_device(uavqp_ctx* ctx, uavqp_esdf* esdf);
+int uavqp_esdf_read_device(uavqp_ctx* ctx, uavqp_esdf* esdf, uint8_t* d_occ, int32_t* d_sq_pos, int32_t* d_sq_neg, double* d_dist);
+int uavqp_esdf_query_device(uavqp_ctx* ctx, uavqp_esdf* esdf, int n_pts, const double* d_pts, double* d_dist, double* d_grad,
+                            uint8_t* d_inside);
+int uavqp_esdf_query_host(uavqp_ctx* ctx, uavqp_esdf* esdf, int n_pts, const double* pts, double* dist, double* grad, uint8_t* inside);
+
+/* Clearance penalty of solved trajectories against a distance field, with its gradients: the shape of uavqp_limit_penalty_device.  Per
+ * trajectory, K = samples_per_seg, tau_s = s / K, trapezoid weights om_0 = om_K = 1/2, om_s = 1 otherwise, pos(x) = max(0, x),
+ * p = p_i(tau_s T_i) the 3-axis position of segment i, d(p) and grad d the field query above:
+ *   Phi = sum_i (T_i / K) sum_{s=0..K} om_s * weight * pos((d_safe - d(p)) / d_safe)^3        over the samples inside the map
+ * A sample outside the map contributes nothing and is counted in d_outside.  With e = -3 weight pos(.)^2 / d_safe:
+ *   d_penalty     [n_traj] Phi
+ *   d_grad_coeff  layout and basis of coeff ([axis][segment][2r] per trajectory): dPhi/dc at FIXED durations,
+ *                 (T_i / K) om_s e * grad d[axis] * dp/dc per sample (dp/dc_k = t^k)
+ *   d_grad_times  [sum_b M_b]: the EXPLICIT dPhi/dT_i at FIXED coefficients, Phi_i / T_i + (T_i / K) sum_s om_s tau_s e (grad d . v), v the
+ *                 velocity of the sample
+ *   d_min_dist    [n_traj] the smallest sampled distance inside the map (max_dist of the map if no sample is inside)
+ *   d_outside     [n_traj] int32 samples outside the map
+ * Each output may be NULL (all NULL: UAVQP_OK, nothing done).  For coefficients of uavqp_solve_batch_device at d_times, the TOTAL gradient
+ * of Phi in the durations is
+ *       d_grad_times + uavqp_solve_backward_device(g = d_grad_coeff).grad_times,
+ * and grad_waypoints / grad_bc of that same call are the gradients in the waypoints and boundary conditions.
+ *   d_status      [n_traj] status of the solve, or NULL (every trajectory counts as solved).  A trajectory whose status is not UAVQP_SOLVED,
+ *                 or with M < 1, gets zeros (min_dist = max_dist, outside = 0).
+ * Every output element is written exactly once, zeros included.  The additions are in a fixed order: the same bytes run to run and for
+ * any grid.  One launch, asynchronous on the ctx stream, no allocation, no read-back.  The penalty is piecewise smooth: its gradients
+ * jump where a sample crosses a cell face of the trilinear query or a bound of the map (at d = d_safe the cube keeps them continuous).
+ * UAVQP_ERR_INVALID_ARG: r not 3 / 4, a negative count, a wrong struct_size, samples_per_seg < 1, d_safe not finite or <= 0, weight not
+ * finite or < 0, a NULL esdf or one never updated, NULL times / coeff, ragged without offsets.
+ * Out of scope: an optimiser over waypoints or durations that uses the penalty, local-window updates, batches of maps, multi-GPU. */
+typedef struct uavqp_clearance_params {
+    int32_t struct_size;
+    int32_t samples_per_seg;   /* K: K + 1 sample points per segment (default 8) */
+    double d_safe;             /* clearance below which a sample is penalised, m (default 0.5) */
+    double weight;             /* >= 0 (default 1e3) */
+} uavqp_clearance_params;
+void uavqp_default_clearance_params(uavqp_clearance_params* out);   /* callable without a device */
+int uavqp_clearance_penalty_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
+                                   const double* d_coeff, const int32_t* d_status, const uavqp_esdf* esdf,
+                                   const uavqp_clearance_params* params, double* d_penalty, double* d_grad_coeff, double* d_grad_times,
+                                   double* d_min_dist, int32_t* d_outside);
+/* The same from HOST pointers (H2D copy, run, D2H copy, synchronous); esdf stays a device object. */
+int uavqp_clearance_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
+                                 const double* coeff, const int32_t* status, const uavqp_esdf* esdf, const uavqp_clearance_params* params,
+                                 double* penalty, double* grad_coeff, double* grad_times, double* min_dist, int32_t* outside);
+
 /* Batched evaluation of solved trajectories on a uniform time grid.
  * Replaces, for a whole batch, PolyTraj::evaluatePos / evaluateVel / evaluateAcc
  * (src/planner/traj_utils/include/traj_utils/poly_traj.hpp:74-168) as driven by poly_traj_server's

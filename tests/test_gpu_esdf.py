@@ -1,0 +1,503 @@
+"""-m gpu: the distance-field layer (uavqp_esdf_*, uavqp_clearance_penalty_device / _host, esdf.EsdfMap, autograd.clearance_penalty)
+against the numpy reference of tests/esdf_reference.py (brute-force transform, longdouble field / query / penalty).
+
+Tolerances.
+  transform  sq_pos / sq_neg EQUAL to the brute force.  dist within 4 ulp of max(d_pos, d_neg, resolution): one sqrt, one multiply, two
+             additions.
+  rasteriser bytes equal (the reference asserts that no (p + k res - origin) / res lies within 1e-6 of an integer).
+  query      inside equal; dist, and grad * resolution, within 1e-13 of max(|the 8 corner values|, resolution): about 20 float64 operations.
+  penalty    Phi, both gradients, min_dist within 1e-9 of the per-trajectory largest magnitude of that output (the project's parity
+             tolerance; reference and device read the SAME device coefficients); outside equal.  The reference asserts that no sample
+             lies within 1e-6 voxel of a cell face or a map bound and none has |d - d_safe| < 1e-9.
+The seeds below were checked for those margins on the CPU (coefficients of the CPU solve in place of the device's)."""
+import ctypes
+import functools
+import math
+
+import numpy as np
+import pytest
+
+import esdf_reference as E
+import uav_motion_planning_amd as U
+from uav_motion_planning_amd import _lib
+from uav_motion_planning_amd.esdf import EsdfMap
+
+pytestmark = pytest.mark.gpu
+PARITY = 1e-9
+LD = np.longdouble
+
+
+def dev():
+    import torch
+    return torch, torch.device("cuda", 0)
+
+
+def up(x):
+    torch, d = dev()
+    return torch.from_numpy(np.ascontiguousarray(x)).to(d)
+
+
+# ---------------------------------------------------------------------------------------------------------------- transform
+GRIDS = [(1, 37, 1), (65, 3, 2), (5, 67, 3), (3, 2, 130), (33, 31, 17)]
+VARIANTS = ["random_3", "random_60", "corner", "free", "occupied"]
+CASES = [((1, 1, 1), "free"), ((1, 1, 1), "occupied")] + [(g, v) for g in GRIDS for v in VARIANTS]
+RES, MAXD = 0.15, 7.5
+
+
+def occupancy(dims, variant):
+    rng = np.random.default_rng(sum(dims) * 7 + len(variant))
+    if variant == "random_3":
+        return (rng.random(dims) < 0.03).astype(np.uint8)
+    if variant == "random_60":
+        return (rng.random(dims) < 0.60).astype(np.uint8) * 255     # non-zero = occupied
+    occ = np.zeros(dims, dtype=np.uint8)
+    if variant == "corner":
+        occ[-1, -1, -1] = 1
+    if variant == "occupied":
+        occ[:] = 1
+    return occ
+
+
+@functools.lru_cache(maxsize=None)
+def transform_reference(dims, variant):
+    return E.field(occupancy(dims, variant), RES, MAXD)
+
+
+@pytest.mark.parametrize("dims,variant", CASES, ids=[f"{'x'.join(map(str, g))}-{v}" for g, v in CASES])
+def test_transform_is_exact_and_dist_within_4_ulp(gpu_ctx, dims, variant):
+    occ = occupancy(dims, variant)
+    ref = transform_reference(dims, variant)
+    with EsdfMap(gpu_ctx, dims, (0.3, -1.0, 2.0), RES, MAXD) as m:
+        m.set_occupancy(occ)
+        m.update()
+        got = m.read()
+        assert np.array_equal(got["occ"], occ)
+        assert np.array_equal(got["sq_pos"].astype(np.int64), ref["sq_pos"]), "sq_pos differs from the brute force"
+        assert np.array_equal(got["sq_neg"].astype(np.int64), ref["sq_neg"]), "sq_neg differs from the brute force"
+        scale = np.maximum(np.maximum(ref["d_pos"], ref["d_neg"]), LD(RES)).astype(np.float64)
+        ulps = np.abs(got["dist"].astype(LD) - ref["dist"]) / np.spacing(scale).astype(LD)
+        print(f"{dims} {variant}: dist max {float(ulps.max()):.2f} ulp of max(d_pos, d_neg, res)")
+        assert float(ulps.max()) <= 4.0
+        # a second update of the same occupancy: the same bytes (the passes run in place)
+        m.update()
+        again = m.read()
+        for k in got:
+            assert again[k].tobytes() == got[k].tobytes(), k
+
+
+# ---------------------------------------------------------------------------------------------------------------- the scene
+DIMS, ORIGIN, MRES, MMAX = (40, 33, 17), (-5.0, -4.0, 0.0), 0.25, 10000.0
+HI = tuple(o + n * MRES for o, n in zip(ORIGIN, DIMS))
+
+
+def raster_cloud(seed=3):
+    """200 points: most inside, some outside the map, some within one inflation step of each face"""
+    rng = np.random.default_rng(seed)
+    lo, hi = np.array(ORIGIN), np.array(HI)
+    pts = [rng.uniform(lo, hi, size=(140, 3)), rng.uniform(lo - 1.5, hi + 1.5, size=(24, 3))]
+    for ax in range(3):
+        for face, sign in ((lo[ax], 1.0), (hi[ax], -1.0)):
+            p = rng.uniform(lo, hi, size=(6, 3))
+            p[:, ax] = face + sign * rng.uniform(-0.9, 0.9, size=6) * MRES
+            pts.append(p)
+    return np.concatenate(pts)
+
+
+def test_rasteriser_bytes_equal_the_reference(gpu_ctx):
+    cloud = raster_cloud()
+    assert cloud.shape == (200, 3)
+    inside = np.all((cloud >= np.array(ORIGIN)) & (cloud <= np.array(HI)), axis=1)
+    assert 0 < np.count_nonzero(~inside) < 60
+    with EsdfMap(gpu_ctx, DIMS, ORIGIN, MRES) as m:
+        for ixy, iz in ((2, 1), (0, 0)):
+            want, margin = E.rasterize(DIMS, ORIGIN, MRES, cloud, ixy, iz)
+            assert margin >= 1e-6, f"a point sits on a voxel face (margin {float(margin):.2e}): pick another seed"
+            m.set_cloud(cloud, inflate_xy=ixy, inflate_z=iz)
+            got = m.read(sq_pos=False, sq_neg=False, dist=False)["occ"]
+            assert np.array_equal(got, want), f"inflation ({ixy}, {iz}): {np.count_nonzero(got != want)} bytes differ"
+            assert 0 < np.count_nonzero(want) < want.size
+        # clear_first against accumulate: halves of the cloud one after the other
+        a, b = cloud[:100], cloud[100:]
+        both, _ = E.rasterize(DIMS, ORIGIN, MRES, cloud, 1, 1)
+        only_b, _ = E.rasterize(DIMS, ORIGIN, MRES, b, 1, 1)
+        assert not np.array_equal(both, only_b)
+        m.set_cloud(a, inflate_xy=1, inflate_z=1)
+        m.set_cloud(b, inflate_xy=1, inflate_z=1, clear_first=False)
+        assert np.array_equal(m.read(sq_pos=False, sq_neg=False, dist=False)["occ"], both)
+        m.set_cloud(b, inflate_xy=1, inflate_z=1, clear_first=True)
+        assert np.array_equal(m.read(sq_pos=False, sq_neg=False, dist=False)["occ"], only_b)
+        # the facade's mapping of an inflation in metres: ceil(inflation / resolution) in x, y and 1 in z
+        assert m.inflation_steps(0.3) == (2, 1) and m.inflation_steps(0.25) == (1, 1) and m.inflation_steps(0.0) == (0, 1)
+        m.set_cloud(cloud, inflation=0.3)
+        assert np.array_equal(m.read(sq_pos=False, sq_neg=False, dist=False)["occ"], E.rasterize(DIMS, ORIGIN, MRES, cloud, 2, 1)[0])
+
+
+def pillar_points(seed=5):
+    """eight vertical pillars inside the region the trajectories fly through"""
+    rng = np.random.default_rng(seed)
+    xy = rng.uniform((-3.5, -2.5), (3.5, 2.5), size=(8, 2))
+    z = np.arange(0.13, 4.2, 0.21)
+    return np.concatenate([np.column_stack([np.full(z.size, x), np.full(z.size, y), z]) for x, y in xy])
+
+
+@functools.lru_cache(maxsize=None)
+def scene_reference():
+    occ, margin = E.rasterize(DIMS, ORIGIN, MRES, pillar_points(), 1, 1)
+    assert margin >= 1e-6
+    return occ, E.field(occ, MRES, MMAX)
+
+
+@pytest.fixture(scope="module")
+def scene(gpu_ctx):
+    """the map of the query / penalty / autograd tests, built on the device from the pillar cloud; checked against the reference once"""
+    occ, ref = scene_reference()
+    m = EsdfMap(gpu_ctx, DIMS, ORIGIN, MRES, MMAX)
+    m.set_cloud(pillar_points(), inflate_xy=1, inflate_z=1)
+    m.update()
+    got = m.read()
+    assert np.array_equal(got["occ"], occ) and np.array_equal(got["sq_pos"], ref["sq_pos"]) and np.array_equal(got["sq_neg"], ref["sq_neg"])
+    yield m, ref["dist"]
+    m.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- query
+def query_points(seed=21):
+    rng = np.random.default_rng(seed)
+    lo, hi = np.array(ORIGIN), np.array(HI)
+    pts = [rng.uniform(lo + 2e-4, hi - 2e-4, size=(4096, 3))]
+    out = rng.uniform(lo - 1.0, hi + 1.0, size=(64, 3))
+    ax = rng.integers(0, 3, size=64)
+    side = rng.random(64) < 0.5
+    out[np.arange(64), ax] = np.where(side, lo[ax] - rng.uniform(0.01, 1.0, size=64), hi[ax] + rng.uniform(0.01, 1.0, size=64))
+    pts.append(out)
+    for a in range(3):
+        for face, sign in ((lo[a], 1.0), (hi[a], -1.0)):
+            p = rng.uniform(lo + 2e-4, hi - 2e-4, size=(64, 3))
+            p[:, a] = face + sign * rng.uniform(0.002, 0.498, size=64) * MRES     # within half a voxel of the face: a clamped corner
+            pts.append(p)
+    return np.concatenate(pts)
+
+
+def test_query_against_the_reference_and_host_equals_device(gpu_ctx, scene):
+    torch, _ = dev()
+    m, ref_dist = scene
+    pts = query_points()
+    want = E.query(ref_dist, ORIGIN, MRES, pts)
+    assert want["margin"].min() >= 1e-6, f"a point sits on a discontinuity (margin {float(want['margin'].min()):.2e}): pick another seed"
+    assert np.count_nonzero(want["inside"] == 0) == 64 and np.count_nonzero(want["inside"]) == 4096 + 6 * 64
+    d_pts = up(pts)
+    torch.cuda.synchronize()
+    dist, grad, inside = m.query(d_pts)
+    gpu_ctx.synchronize()
+    dist, grad, inside = dist.cpu().numpy(), grad.cpu().numpy(), inside.cpu().numpy()
+    assert np.array_equal(inside, want["inside"])
+    scale = np.maximum(want["scale"], LD(MRES))
+    e_d = float(np.max(np.abs(dist.astype(LD) - want["dist"]) / scale))
+    e_g = float(np.max(np.abs(grad.astype(LD) - want["grad"]) * LD(MRES) / scale[:, None]))
+    print(f"query: dist {e_d:.3e}, grad * res {e_g:.3e} of max(|corner values|, res); {np.count_nonzero(np.abs(want['grad']).sum(axis=1) > 0)} points with a gradient")
+    assert e_d <= 1e-13 and e_g <= 1e-13
+    out = want["inside"] == 0
+    assert dist[out].tobytes() == bytes(8 * 64) and grad[out].tobytes() == bytes(24 * 64)
+    assert np.count_nonzero(np.abs(want["grad"]).sum(axis=1) > 0) > 2000
+    # the host entry: the same bytes
+    h_dist, h_grad, h_inside = m.query(pts)
+    assert h_dist.tobytes() == dist.tobytes() and h_grad.tobytes() == grad.tobytes() and h_inside.tobytes() == inside.tobytes()
+    # NULL outputs are honoured
+    only = torch.full((pts.shape[0],), float("nan"), dtype=torch.float64, device=d_pts.device)
+    rc = _lib.lib().uavqp_esdf_query_device(gpu_ctx._h, m.handle, pts.shape[0], d_pts.data_ptr(), only.data_ptr(), None, None)
+    gpu_ctx.synchronize()
+    assert rc == _lib.UAVQP_OK and only.cpu().numpy().tobytes() == dist.tobytes()
+    assert _lib.lib().uavqp_esdf_query_device(gpu_ctx._h, m.handle, pts.shape[0], d_pts.data_ptr(), None, None, None) == _lib.UAVQP_OK
+
+
+# ---------------------------------------------------------------------------------------------------------------- penalty
+PARAMS = dict(samples_per_seg=6, d_safe=0.6, weight=2e2)
+
+
+def flight_batch(r, uniform, seed):
+    """64 trajectories through the pillars: random walks of 0.6 .. 1.2 m steps at about 1 m/s; every eighth starts at the +x face and
+    flies out of the map.  Uniform: M = 4; ragged: M in {1, 2, 3, 5}."""
+    rng = np.random.default_rng(seed)
+    n = 64
+    Ms = np.full(n, 4) if uniform else rng.choice([1, 2, 3, 5], size=n)
+    if not uniform:
+        Ms[:4] = [1, 2, 3, 5]
+    so = np.zeros(n + 1, dtype=np.int32)
+    so[1:] = np.cumsum(Ms)
+    wps, T = [], []
+    for b in range(n):
+        M = int(Ms[b])
+        p = rng.uniform((-3.8, -2.8, 0.8), (3.8, 2.8, 3.2))
+        d = rng.normal(size=(M, 3)) * np.array([1.0, 1.0, 0.3])
+        if b % 8 == 7:
+            p[0] = 4.6
+            d[:, 0] = np.abs(d[:, 0]) + 1.0
+        step = rng.uniform(0.6, 1.2, size=M)
+        d = d / np.linalg.norm(d, axis=1)[:, None] * step[:, None]
+        wps.append(np.vstack([p, p + np.cumsum(d, axis=0)]))
+        T.append(step * rng.uniform(0.8, 1.25, size=M))
+    bc = np.zeros((n, 2, r - 1, 3))
+    bc[:, 0, 0] = rng.uniform(-0.5, 0.5, size=(n, 3))
+    return dict(r=r, n=n, so=so, wp=np.vstack(wps), T=np.concatenate(T), bc=bc, uni=4 if uniform else 0, mmax=int(Ms.max()))
+
+
+class Flight:
+    """one batch solved on the device, and the clearance penalty through the device-pointer entry"""
+
+    def __init__(self, ctx, b):
+        torch, d = dev()
+        self.torch, self.ctx, self.b = torch, ctx, b
+        self.r, self.n, self.so, self.total = b["r"], b["n"], b["so"], int(b["so"][-1])
+        self.d_so, self.d_wp, self.d_T, self.d_bc = up(b["so"]), up(b["wp"]), up(b["T"]), up(b["bc"])
+        self.coeff = torch.zeros(3 * 2 * self.r * self.total, dtype=torch.float64, device=d)
+        self.status = torch.zeros(self.n, dtype=torch.int32, device=d)
+        torch.cuda.synchronize()
+        ctx.solve_batch_device(self.r, self.n, b["uni"], b["mmax"], self.d_so, self.d_wp, self.d_T, self.d_bc, self.coeff, self.status)
+        ctx.synchronize()
+        assert np.all(self.status.cpu().numpy() == U.UAVQP_SOLVED)
+
+    def penalty(self, esdf, status="own", want=(True,) * 5, fill=float("nan"), **params):
+        """-> [penalty, grad_coeff, grad_times, min_dist, outside] device tensors (None where not wanted), pre-filled"""
+        torch, d = dev()
+        shapes = ((self.n, torch.float64), (3 * 2 * self.r * self.total, torch.float64), (self.total, torch.float64), (self.n, torch.float64),
+                  (self.n, torch.int32))
+        out = [torch.full((s,), fill if t == torch.float64 else -7, dtype=t, device=d) if w else None for (s, t), w in zip(shapes, want)]
+        torch.cuda.synchronize()
+        self.ctx.clearance_penalty_device(self.r, self.n, self.b["uni"], self.d_so, self.d_T, self.coeff, esdf,
+                                          status=self.status if isinstance(status, str) else status, penalty=out[0], grad_coeff=out[1],
+                                          grad_times=out[2], min_dist=out[3], outside=out[4], **dict(PARAMS, **params))
+        self.ctx.synchronize()
+        return out
+
+
+KEYS = ("phi", "grad_coeff", "grad_times", "min_dist", "outside")
+PENALTY_CASES = [(3, True, 31), (4, True, 32), (3, False, 33), (4, False, 34)]
+
+
+@pytest.mark.parametrize("r,uniform,seed", PENALTY_CASES, ids=[f"r{r}-{'uniform' if u else 'ragged'}" for r, u, _ in PENALTY_CASES])
+def test_clearance_penalty_against_the_reference(gpu_ctx, scene, r, uniform, seed):
+    m, ref_dist = scene
+    f = Flight(gpu_ctx, flight_batch(r, uniform, seed))
+    c = f.coeff.cpu().numpy()
+    ref = E.penalty(r, f.so, f.b["T"], c, ref_dist, ORIGIN, MRES, MMAX, **PARAMS)
+    # the case is worth comparing, and no sample sits on a discontinuity of the gradients
+    assert np.count_nonzero(ref["phi"] > 0) >= 8 and np.count_nonzero(ref["phi"] == 0) >= 8 and np.count_nonzero(ref["outside"] > 0) >= 1
+    assert ref["margin"] >= 1e-6 and ref["gap"] >= 1e-9, (float(ref["margin"]), float(ref["gap"]))
+
+    out = f.penalty(m)
+    got = dict(zip(KEYS, (x.cpu().numpy() for x in out)))
+    assert np.array_equal(got["outside"].astype(np.int64), ref["outside"])
+    nc3 = 3 * 2 * r
+    worst = {}
+    for t in range(f.n):
+        s0, s1 = int(f.so[t]), int(f.so[t + 1])
+        for key, sl in (("phi", slice(t, t + 1)), ("grad_coeff", slice(nc3 * s0, nc3 * s1)), ("grad_times", slice(s0, s1)),
+                        ("min_dist", slice(t, t + 1))):
+            want = ref[key][sl]
+            have = got[key][sl].astype(LD)
+            scale = np.max(np.abs(want))
+            err = float(np.max(np.abs(have - want)) / scale) if scale > 0 else float(np.max(np.abs(have)))
+            worst[key] = max(worst.get(key, 0.0), err)
+    print(f"r={r} uniform={uniform}: {np.count_nonzero(ref['phi'] > 0)} penalised, {np.count_nonzero(ref['outside'] > 0)} leave the map; max error "
+          "relative to the per-trajectory largest magnitude: " + ", ".join(f"{k} {v:.3e}" for k, v in worst.items()))
+    for k, v in worst.items():
+        assert v <= PARITY, f"{k}: {v:.3e}"
+    # NULL outputs are honoured: every subset gives the same bytes for what it does return; all NULL is UAVQP_OK
+    for want in ((True, False, False, False, False), (False, True, False, False, False), (False, False, True, False, True),
+                 (False, False, False, True, False)):
+        part = f.penalty(m, want=want)
+        for w, p, full in zip(want, part, out):
+            assert (p is None) == (not w)
+            if w:
+                assert p.cpu().numpy().tobytes() == full.cpu().numpy().tobytes()
+    gpu_ctx.clearance_penalty_device(r, f.n, f.b["uni"], f.d_so, f.d_T, f.coeff, m, **PARAMS)
+    # status NULL: every trajectory counts as solved -- the same bytes here; run to run: identical bytes
+    for again in (f.penalty(m, status=None), f.penalty(m)):
+        for p, full in zip(again, out):
+            assert p.cpu().numpy().tobytes() == full.cpu().numpy().tobytes()
+    # a trajectory that is not SOLVED: zeros, min_dist = max_dist, outside = 0; its neighbours untouched
+    bad = int(np.flatnonzero(ref["phi"] > 0)[0])
+    st = f.status.cpu().numpy().copy()
+    st[bad] = U.UAVQP_MAX_ITER_REACHED
+    flagged = [x.cpu().numpy() for x in f.penalty(m, status=up(st))]
+    b0, b1 = int(f.so[bad]), int(f.so[bad + 1])
+    assert flagged[0][bad] == 0 and flagged[3][bad] == MMAX and flagged[4][bad] == 0
+    assert flagged[1][nc3 * b0:nc3 * b1].tobytes() == bytes(8 * nc3 * (b1 - b0)) and flagged[2][b0:b1].tobytes() == bytes(8 * (b1 - b0))
+    keep = np.arange(f.n) != bad
+    seg_keep = np.repeat(keep, np.diff(f.so))
+    for i, k in enumerate(KEYS):
+        sel = keep if k in ("phi", "min_dist", "outside") else (seg_keep if k == "grad_times" else np.repeat(seg_keep, nc3))
+        assert np.array_equal(flagged[i][sel], got[k][sel]), k
+    # the host entry: the same bytes as the device entry
+    host = gpu_ctx.clearance_penalty_host(r, f.so, f.b["T"], c, m, uniform_segments=f.b["uni"], status=f.status.cpu().numpy(), **PARAMS)
+    for h, k in zip(host, KEYS):
+        assert h.tobytes() == got[k].tobytes(), k
+
+
+def test_clearance_penalty_of_empty_trajectories_is_zero(gpu_ctx, scene):
+    """M = 0 among valid neighbours: zeros, min_dist = max_dist, outside = 0, every element written"""
+    torch, d = dev()
+    m, _ = scene
+    b = flight_batch(3, False, 33)
+    f = Flight(gpu_ctx, b)
+    full = [x.cpu().numpy() for x in f.penalty(m)]
+    so2 = np.concatenate([[0, 0], b["so"][1:4], [b["so"][3]], b["so"][4:]]).astype(np.int32)      # empty trajectories at 0 and 4
+    n2 = so2.size - 1
+    pen, md = torch.full((n2,), float("nan"), dtype=torch.float64, device=d), torch.full((n2,), float("nan"), dtype=torch.float64, device=d)
+    outs = torch.full((n2,), -7, dtype=torch.int32, device=d)
+    torch.cuda.synchronize()
+    gpu_ctx.clearance_penalty_device(3, n2, 0, up(so2), f.d_T, f.coeff, m, penalty=pen, min_dist=md, outside=outs, **PARAMS)
+    gpu_ctx.synchronize()
+    pen, md, outs = pen.cpu().numpy(), md.cpu().numpy(), outs.cpu().numpy()
+    for e in (0, 4):
+        assert pen[e] == 0 and md[e] == MMAX and outs[e] == 0
+    keep = np.ones(n2, dtype=bool)
+    keep[[0, 4]] = False
+    assert pen[keep].tobytes() == full[0].tobytes() and md[keep].tobytes() == full[3].tobytes() and outs[keep].tobytes() == full[4].tobytes()
+
+
+def test_clearance_penalty_guard_bands(gpu_ctx, scene):
+    """every input and output between sentinel bands, ragged and uniform, one output misaligned to 8 bytes: bands intact, results
+    independent of what lies outside the buffers (the arena of tests/test_gpu_guard_bands.py)"""
+    from test_gpu_guard_bands import _both_fills
+    m, _ = scene
+    for r, uniform, seed in ((4, False, 34), (3, True, 31)):
+        b = flight_batch(r, uniform, seed)
+        tot = int(b["so"][-1])
+
+        def run_clearance(ar):
+            d_so, wp, T, bc = ar.put(b["so"]), ar.put(b["wp"]), ar.put(b["T"]), ar.put(b["bc"])
+            co, st = ar.out(tot * 6 * r), ar.out(b["n"], np.int32)
+            gpu_ctx.solve_batch_device(r, b["n"], b["uni"], b["mmax"], d_so, wp, T, bc, co, st)
+            pen, g_c, g_t = ar.out(b["n"]), ar.out(tot * 6 * r, misalign=8), ar.out(tot)
+            md, outs = ar.out(b["n"]), ar.out(b["n"], np.int32)
+            gpu_ctx.clearance_penalty_device(r, b["n"], b["uni"], d_so, T, co, m, status=st, penalty=pen, grad_coeff=g_c, grad_times=g_t,
+                                             min_dist=md, outside=outs, **PARAMS)
+            pts, q_d, q_g, q_in = ar.put(b["wp"]), ar.out(b["wp"].shape[0]), ar.out(b["wp"].shape), ar.out(b["wp"].shape[0], np.uint8)
+            _lib.check(_lib.lib().uavqp_esdf_query_device(gpu_ctx._h, m.handle, b["wp"].shape[0], pts.data_ptr(), q_d.data_ptr(), q_g.data_ptr(),
+                                                          q_in.data_ptr()), "uavqp_esdf_query_device")
+            return {"pen": pen, "g_c": g_c, "g_t": g_t, "md": md, "outs": outs, "q_d": q_d, "q_g": q_g, "q_in": q_in}
+        got = _both_fills(run_clearance)
+        assert np.count_nonzero(got["pen"] > 0) >= 8
+
+
+# ---------------------------------------------------------------------------------------------------------------- autograd
+@pytest.mark.parametrize("uniform", [True, False])
+def test_torch_clearance_penalty_equals_the_c_abi_byte_for_byte(gpu_ctx, scene, uniform):
+    torch, _ = dev()
+    from uav_motion_planning_amd import autograd as A
+    m, _ = scene
+    r, seed = (4, 32) if uniform else (3, 33)
+    f = Flight(gpu_ctx, flight_batch(r, uniform, seed))
+    phi, g_c, g_t, _, _ = f.penalty(m)
+    assert np.count_nonzero(g_c.cpu().numpy()) > 0
+    kw = dict(uniform_segments=f.b["uni"]) if uniform else dict(seg_offsets=f.d_so)
+    # on given coefficients: coeff.grad and times.grad are the two C-ABI gradients
+    coeff = f.coeff.clone().requires_grad_(True)
+    times = f.d_T.clone().requires_grad_(True)
+    out = A.clearance_penalty(gpu_ctx, r, coeff, times, m, status=f.status, **kw, **PARAMS)
+    assert out.detach().cpu().numpy().tobytes() == phi.cpu().numpy().tobytes()
+    out.sum().backward()
+    torch.cuda.synchronize()
+    gpu_ctx.set_stream(None)
+    assert coeff.grad.cpu().numpy().tobytes() == g_c.cpu().numpy().tobytes()
+    assert times.grad.cpu().numpy().tobytes() == g_t.cpu().numpy().tobytes()
+    # behind solve_batch: the gradients of the existing backward pass for g = grad_coeff; times adds the explicit part
+    want_t, want_w = torch.empty_like(f.d_T), torch.empty_like(f.d_wp)
+    gpu_ctx.solve_backward_device(r, f.n, f.b["uni"], f.b["mmax"], f.total, f.d_so, f.d_wp, f.d_T, f.d_bc, f.coeff, g_c, grad_times=want_t,
+                                  grad_waypoints=want_w, status=f.status)
+    gpu_ctx.synchronize()
+    wp = f.d_wp.clone().requires_grad_(True)
+    times2 = f.d_T.clone().requires_grad_(True)
+    kw_s = dict(kw, max_segments=f.b["mmax"]) if not uniform else kw
+    c = A.solve_batch(gpu_ctx, r, wp, times2, f.d_bc, **kw_s)
+    assert c.detach().cpu().numpy().tobytes() == f.coeff.cpu().numpy().tobytes()
+    A.clearance_penalty(gpu_ctx, r, c, times2, m, **kw, **PARAMS).sum().backward()
+    torch.cuda.synchronize()
+    gpu_ctx.set_stream(None)
+    assert wp.grad.cpu().numpy().tobytes() == want_w.cpu().numpy().tobytes()
+    assert times2.grad.cpu().numpy().tobytes() == (want_t + g_t).cpu().numpy().tobytes()
+    assert np.count_nonzero(wp.grad.cpu().numpy()) > 0
+
+
+# ---------------------------------------------------------------------------------------------------------------- arguments
+def test_invalid_arguments_are_refused(gpu_ctx, scene):
+    torch, d = dev()
+    L, INV = _lib.lib(), _lib.UAVQP_ERR_INVALID_ARG
+    m, _ = scene
+
+    def create(dims, origin=(0.0, 0.0, 0.0), res=0.1, max_dist=10.0):
+        h = ctypes.c_void_p()
+        rc = L.uavqp_esdf_create(gpu_ctx._h, ctypes.byref((ctypes.c_int32 * 3)(*dims)), ctypes.byref((ctypes.c_double * 3)(*origin)), res, max_dist,
+                                 ctypes.byref(h))
+        return rc, h
+    for dims in ((0, 4, 4), (4, -1, 4), (4, 4, 1025)):
+        assert create(dims)[0] == INV
+    for kw in (dict(res=0.0), dict(res=-1.0), dict(res=math.inf), dict(res=math.nan), dict(max_dist=0.0), dict(max_dist=math.inf),
+               dict(max_dist=math.nan)):
+        assert create((4, 4, 4), **kw)[0] == INV
+    # (more than 2^30 voxels with every dimension in range needs 1024 x 1024 x 1024 + : not reachable; 1024^3 itself is the bound)
+    rc, h = create((4, 5, 6))
+    assert rc == _lib.UAVQP_OK
+    pts = torch.zeros((4, 3), dtype=torch.float64, device=d)
+    o1, o3, ob = torch.zeros(4, dtype=torch.float64, device=d), torch.zeros((4, 3), dtype=torch.float64, device=d), torch.zeros(4, dtype=torch.uint8, device=d)
+    try:
+        # query and penalty before the first update
+        assert L.uavqp_esdf_query_device(gpu_ctx._h, h, 4, pts.data_ptr(), o1.data_ptr(), o3.data_ptr(), ob.data_ptr()) == INV
+        hp = np.zeros((4, 3))
+        assert L.uavqp_esdf_query_host(gpu_ctx._h, h, 4, hp.ctypes.data, None, None, np.zeros(4, np.uint8).ctypes.data) == INV
+        cp = _lib.ClearanceParams()
+        L.uavqp_default_clearance_params(ctypes.byref(cp))
+        co, T = torch.zeros(18, dtype=torch.float64, device=d), torch.ones(1, dtype=torch.float64, device=d)
+        pen = torch.zeros(1, dtype=torch.float64, device=d)
+        args = lambda esdf, p: (gpu_ctx._h, 3, 1, 1, None, T.data_ptr(), co.data_ptr(), None, esdf, ctypes.byref(p), pen.data_ptr(), None, None, None, None)
+        assert L.uavqp_clearance_penalty_device(*args(h, cp)) == INV
+        # negative inflation, NULL map
+        assert L.uavqp_esdf_rasterize_cloud_device(gpu_ctx._h, h, pts.data_ptr(), 4, -1, 0, 1) == INV
+        assert L.uavqp_esdf_rasterize_cloud_device(gpu_ctx._h, h, pts.data_ptr(), 4, 0, -1, 1) == INV
+        assert L.uavqp_esdf_rasterize_cloud_device(gpu_ctx._h, None, pts.data_ptr(), 4, 0, 0, 1) == INV
+        assert L.uavqp_esdf_update_device(gpu_ctx._h, None) == INV
+        assert L.uavqp_esdf_query_device(gpu_ctx._h, None, 4, pts.data_ptr(), o1.data_ptr(), None, None) == INV
+        assert L.uavqp_clearance_penalty_device(*args(None, cp)) == INV
+        # after an update the same calls pass
+        assert L.uavqp_esdf_update_device(gpu_ctx._h, h) == _lib.UAVQP_OK
+        assert L.uavqp_esdf_query_device(gpu_ctx._h, h, 4, pts.data_ptr(), o1.data_ptr(), o3.data_ptr(), ob.data_ptr()) == _lib.UAVQP_OK
+        assert L.uavqp_clearance_penalty_device(*args(h, cp)) == _lib.UAVQP_OK
+        gpu_ctx.synchronize()
+        # the parameters
+        for field, value in (("struct_size", 8), ("samples_per_seg", 0), ("d_safe", 0.0), ("d_safe", -1.0), ("d_safe", math.nan),
+                             ("weight", -1.0), ("weight", math.inf), ("weight", math.nan)):
+            bad = _lib.ClearanceParams()
+            L.uavqp_default_clearance_params(ctypes.byref(bad))
+            setattr(bad, field, value)
+            assert L.uavqp_clearance_penalty_device(*args(h, bad)) == INV, (field, value)
+            host = L.uavqp_clearance_penalty_host(gpu_ctx._h, 3, 1, 1, None, np.ones(1).ctypes.data, np.zeros(18).ctypes.data, None, h,
+                                                  ctypes.byref(bad), np.zeros(1).ctypes.data, None, None, None, None)
+            assert host == INV, (field, value)
+        assert L.uavqp_clearance_penalty_device(gpu_ctx._h, 5, 1, 1, None, T.data_ptr(), co.data_ptr(), None, h, ctypes.byref(cp), pen.data_ptr(),
+                                                None, None, None, None) == INV
+    finally:
+        assert L.uavqp_esdf_destroy(gpu_ctx._h, h) == _lib.UAVQP_OK
+    with pytest.raises(ValueError):
+        gpu_ctx.clearance_penalty_device(3, 1, 1, None, T, co, m, penalty=pen, no_such_field=1.0)
+    with pytest.raises(U.UavqpError):
+        EsdfMap(gpu_ctx, (4, 4, 2000), (0, 0, 0), 0.1)
+
+
+def test_python_facade_get_clearance_penalty(scene):
+    """TrajOptimizer.getClearancePenalty on a map built on the optimiser's own context, against the reference"""
+    _, ref_dist = scene
+    b = flight_batch(3, False, 33)
+    opt = U.TrajOptimizer(order=3)
+    wo = (b["so"] + np.arange(b["n"] + 1)).astype(np.int64)
+    opt.setWaypoints(b["wp"], wp_offsets=wo)
+    opt.setTimeAllocation(b["T"])
+    opt.setBoundary(b["bc"])
+    assert opt.solve() is True
+    with EsdfMap(opt.context(), DIMS, ORIGIN, MRES, MMAX) as m:
+        m.set_cloud(pillar_points(), inflate_xy=1, inflate_z=1)
+        m.update()
+        phi = opt.get_clearance_penalty(m, **PARAMS)
+    want = E.penalty(3, b["so"], b["T"], opt.getPolyCoeff(), ref_dist, ORIGIN, MRES, MMAX, **PARAMS)["phi"]
+    assert np.count_nonzero(phi) >= 8
+    assert np.max(np.abs(phi - want)) <= PARITY * float(np.max(want))

@@ -57,6 +57,17 @@ SYMBOLS = (
     "uavqp_limit_penalty_host",
     "uavqp_time_optimize_limits_device",
     "uavqp_time_optimize_limits_host",
+    "uavqp_esdf_create",
+    "uavqp_esdf_destroy",
+    "uavqp_esdf_set_occupancy_device",
+    "uavqp_esdf_rasterize_cloud_device",
+    "uavqp_esdf_update_device",
+    "uavqp_esdf_read_device",
+    "uavqp_esdf_query_device",
+    "uavqp_esdf_query_host",
+    "uavqp_default_clearance_params",
+    "uavqp_clearance_penalty_device",
+    "uavqp_clearance_penalty_host",
     "uavqp_eval_batch_device",
     "uavqp_traj_length_device",
     "uavqp_ellipsoid_check_device",
@@ -129,6 +140,11 @@ class LimitParams(ctypes.Structure):
                 ("weight_v", ctypes.c_double), ("weight_a", ctypes.c_double)]
 
 
+class ClearanceParams(ctypes.Structure):
+    """uavqp_clearance_params of include/uavqp.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("samples_per_seg", ctypes.c_int32), ("d_safe", ctypes.c_double), ("weight", ctypes.c_double)]
+
+
 def build(force=False):
     """Compile csrc/*.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
     csrc = os.path.join(_PKG, "csrc")
@@ -195,6 +211,19 @@ def lib():
                                                     ctypes.POINTER(LimitParams), dp]
     L.uavqp_time_optimize_limits_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, ctypes.POINTER(TimeOptParams), dp, ip, dp, ip,
                                                   ctypes.POINTER(LimitParams), dp]
+    L.uavqp_esdf_create.argtypes = [vp, ctypes.POINTER(ctypes.c_int32 * 3), ctypes.POINTER(ctypes.c_double * 3), ctypes.c_double, ctypes.c_double,
+                                    ctypes.POINTER(vp)]
+    L.uavqp_esdf_destroy.argtypes = [vp, vp]
+    L.uavqp_esdf_set_occupancy_device.argtypes = [vp, vp, vp]
+    L.uavqp_esdf_rasterize_cloud_device.argtypes = [vp, vp, dp, i32, i32, i32, i32]
+    L.uavqp_esdf_update_device.argtypes = [vp, vp]
+    L.uavqp_esdf_read_device.argtypes = [vp, vp, vp, ip, ip, dp]
+    L.uavqp_esdf_query_device.argtypes = [vp, vp, i32, dp, dp, dp, vp]
+    L.uavqp_esdf_query_host.argtypes = [vp, vp, i32, dp, dp, dp, vp]
+    L.uavqp_default_clearance_params.argtypes = [ctypes.POINTER(ClearanceParams)]
+    L.uavqp_default_clearance_params.restype = None
+    L.uavqp_clearance_penalty_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, vp, ctypes.POINTER(ClearanceParams), dp, dp, dp, dp, ip]
+    L.uavqp_clearance_penalty_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, vp, ctypes.POINTER(ClearanceParams), dp, dp, dp, dp, ip]
     L.uavqp_eval_batch_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, i32, dp]
     L.uavqp_traj_length_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ctypes.c_double, dp, dp, ip]
     L.uavqp_ellipsoid_check_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, dp, i32,

@@ -192,6 +192,29 @@ class TrajOptimizer {
         }
         return phi;
     }
+    // Clearance penalty per trajectory of the stored coefficients at the stored durations against a distance field (uavqp::EsdfMap of
+    // cpp/esdf_map.h, built on context() and updated; uavqp_clearance_penalty_host).  min_dist / outside, when given, receive the smallest
+    // sampled distance and the count of samples outside the map per trajectory.  A trajectory that did not solve carries zero.  Empty on failure.
+    template <class Map>
+    std::vector<double> getClearancePenalty(const Map& map, const uavqp_clearance_params& params, std::vector<double>* min_dist = nullptr,
+                                            std::vector<int32_t>* outside = nullptr) {
+        std::vector<double> phi;
+        if (n_traj_ <= 0 || !ctx_ || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_]) ||
+            coef_.size() != static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_] || status_.size() != static_cast<size_t>(n_traj_))
+            return phi;
+        phi.assign(n_traj_, 0.0);
+        if (min_dist) min_dist->assign(n_traj_, 0.0);
+        if (outside) outside->assign(n_traj_, 0);
+        if (uavqp_clearance_penalty_host(ctx_, order_, n_traj_, 0, seg_offsets_.data(), T_.data(), coef_.data(), status_.data(), map.handle(), &params,
+                                         phi.data(), nullptr, nullptr, min_dist ? min_dist->data() : nullptr,
+                                         outside ? outside->data() : nullptr) != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            phi.clear();
+        }
+        return phi;
+    }
+    // The context this optimiser solves on (created on first use; nullptr without a device): what a uavqp::EsdfMap is built on.
+    uavqp_ctx* context() { return ensureContext() ? ctx_ : nullptr; }
     const std::vector<double>& objective() const { return objective_; }
     const std::vector<int32_t>& acceptedTrials() const { return accepted_; }
     // Control cost c' P c (integral of the squared r-th derivative, three axes) per trajectory of the current waypoints at the current

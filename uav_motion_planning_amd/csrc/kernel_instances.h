@@ -100,3 +100,10 @@
     UAVQP_INST __global__ void uavqp::time_opt_step_kernel<R_, true, true>(uavqp::TimeOptArgs);    \
     UAVQP_INST __global__ void uavqp::time_opt_step_kernel<R_, false, true>(uavqp::TimeOptArgs);
 #define UAVQP_INSTANCES_LIMITS UAVQP_LIMITS_R(3) UAVQP_LIMITS_R(4)
+
+// ---- qp_esdf.h: distance field passes and the clearance penalty (its plain kernels are defined in k_esdf.hip alone, declared elsewhere)
+#define UAVQP_INSTANCES_ESDF                                                                       \
+    UAVQP_INST __global__ void uavqp::esdf_axis_kernel<false>(uavqp::EsdfArgs, int, int, int, int, int); \
+    UAVQP_INST __global__ void uavqp::esdf_axis_kernel<true>(uavqp::EsdfArgs, int, int, int, int, int);  \
+    UAVQP_INST __global__ void uavqp::clearance_penalty_kernel<3>(uavqp::ClearanceArgs);              \
+    UAVQP_INST __global__ void uavqp::clearance_penalty_kernel<4>(uavqp::ClearanceArgs);

@@ -33,6 +33,7 @@
 #include "qp_time_opt.h"
 #include "qp_adjoint.h"
 #include "qp_limits.h"
+#include "qp_esdf.h"
 // Measured-slower alternatives kept as bit-identical cross-checks: `make experiments` (-DUAVQP_EXPERIMENTS) only
 #ifdef UAVQP_EXPERIMENTS
 #include "cloud_grid2d.h"
@@ -57,6 +58,7 @@ UAVQP_INSTANCES_CLOUD
 UAVQP_INSTANCES_TIMEOPT
 UAVQP_INSTANCES_ADJOINT
 UAVQP_INSTANCES_LIMITS
+UAVQP_INSTANCES_ESDF
 #endif
 
 namespace uavqp {
@@ -1881,6 +1883,11 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
 // Velocity / acceleration limit penalty and the limit-aware duration optimiser
 // ===================================================================================================
 #include "uavqp_limits.h"
+
+// ===================================================================================================
+// Signed distance field of an occupancy grid and the clearance penalty
+// ===================================================================================================
+#include "uavqp_esdf.h"
 
 // ===================================================================================================
 // N3: quadrotor_msgs/PolynomialTrajectory packer (host only)

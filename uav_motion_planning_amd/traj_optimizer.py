@@ -191,6 +191,49 @@ class Context:
         _lib.check(rc, "uavqp_limit_penalty_host")
         return penalty, g_c, g_t, peak
 
+    @staticmethod
+    def _clearance_params(params):
+        cp = _lib.ClearanceParams()
+        _lib.lib().uavqp_default_clearance_params(ctypes.byref(cp))
+        for k, v in params.items():
+            if not hasattr(cp, k) or k == "struct_size":
+                raise ValueError(f"unknown uavqp_clearance_params field {k!r}")
+            setattr(cp, k, v)
+        return cp
+
+    def clearance_penalty_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, esdf, status=None, penalty=None, grad_coeff=None,
+                                 grad_times=None, min_dist=None, outside=None, **params):
+        """uavqp_clearance_penalty_device on device buffers: the clearance penalty [n_traj] of solved trajectories against the distance
+        field `esdf` (an esdf.EsdfMap, updated), its gradient in the coefficients at fixed durations (layout of coeff), its EXPLICIT
+        gradient in the durations at fixed coefficients [sum M], the smallest sampled distance [n_traj] and the int32 count of samples
+        outside the map [n_traj]; each output may be None.  params: fields of uavqp_clearance_params that differ from the defaults
+        (samples_per_seg, d_safe, weight).  Asynchronous."""
+        cp = self._clearance_params(params)
+        rc = _lib.lib().uavqp_clearance_penalty_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff),
+                                                       _ptr(status), getattr(esdf, "handle", esdf), ctypes.byref(cp), _ptr(penalty),
+                                                       _ptr(grad_coeff), _ptr(grad_times), _ptr(min_dist), _ptr(outside))
+        _lib.check(rc, "uavqp_clearance_penalty_device")
+
+    def clearance_penalty_host(self, r, seg_offsets, times, coeff, esdf, uniform_segments=0, status=None, **params):
+        """numpy in / numpy out (synchronous; the map stays on the device).  Returns (penalty [n_traj], grad_coeff, grad_times [sum M],
+        min_dist [n_traj], outside [n_traj] int32)."""
+        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
+        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total and coeff.size == 3 * 2 * r * total
+        cp = self._clearance_params(params)
+        penalty = np.zeros(n_traj, dtype=np.float64)
+        g_c = np.zeros_like(coeff)
+        g_t = np.zeros(total, dtype=np.float64)
+        min_dist = np.zeros(n_traj, dtype=np.float64)
+        outside = np.zeros(n_traj, dtype=np.int32)
+        rc = _lib.lib().uavqp_clearance_penalty_host(self._h, r, n_traj, uniform_segments, _ptr(so), _ptr(times), _ptr(coeff), _ptr(status),
+                                                     getattr(esdf, "handle", esdf), ctypes.byref(cp), _ptr(penalty), _ptr(g_c), _ptr(g_t),
+                                                     _ptr(min_dist), _ptr(outside))
+        _lib.check(rc, "uavqp_clearance_penalty_host")
+        return penalty, g_c, g_t, min_dist, outside
+
     def time_optimize_limits_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc,
                                     coeff_out, status_out, objective_out, accepted_out=None, peak_out=None, limits=None, **params):
         """uavqp_time_optimize_limits_device on device buffers: time_optimize_device with the limit penalty inside the objective
@@ -556,6 +599,8 @@ class TrajOptimizer:
                                      uavqp_limit_params fields: the soft velocity / acceleration penalty joins the objective
                                      (uavqp_time_optimize_limits_host), .peak [n_traj][2] = sampled |v| / v_max, |a| / a_max at the result
     getLimitPenalty(**limits)        [n_traj] limit penalty of the stored coefficients at the stored durations
+    getClearancePenalty(esdf, ...)   [n_traj] clearance penalty of the stored coefficients against an esdf.EsdfMap built on context()
+                                     (also spelled get_clearance_penalty)
     backward(grad_coeff)             equality-constrained problems only, after solve(): (grad_times, grad_waypoints, grad_bc) of a loss
                                      with d loss / d getPolyCoeff() = grad_coeff, through the solve
     getCost()                        [n_traj] control cost c' P c of the stored coefficients at the stored durations
@@ -666,6 +711,23 @@ class TrajOptimizer:
         if self._ctx is None or self._coef.size != 3 * 2 * self._r * int(self._so[-1]) or self.status.size != self._so.size - 1:
             raise _lib.UavqpError("getLimitPenalty: no solved coefficients (call solve() or optimizeTime() first)")
         return self._ctx.limit_penalty_host(self._r, self._so, self._T, self._coef, status=self.status, **limits)[0]
+
+    def getClearancePenalty(self, esdf, **params):
+        """[n_traj] clearance penalty of the stored coefficients at the stored durations against the distance field `esdf` (an
+        esdf.EsdfMap on this optimiser's context -- see context() --, updated); params: fields of uavqp_clearance_params that differ from
+        the defaults.  Trajectories that did not solve carry zero."""
+        if self._ctx is None or self._coef.size != 3 * 2 * self._r * int(self._so[-1]) or self.status.size != self._so.size - 1:
+            raise _lib.UavqpError("getClearancePenalty: no solved coefficients (call solve() or optimizeTime() first)")
+        return self._ctx.clearance_penalty_host(self._r, self._so, self._T, self._coef, esdf, status=self.status, **params)[0]
+
+    get_clearance_penalty = getClearancePenalty
+
+    def context(self):
+        """The Context this optimiser solves on (created on first use): what an esdf.EsdfMap for getClearancePenalty is built on."""
+        if self._ctx is None:
+            self._ctx = Context(self._device)
+            self._ctx.set_settings(warm_start=1, eps_prim_inf=1e-3, max_iter=1000)
+        return self._ctx
 
     def backward(self, grad_coeff):
         """After solve() of an equality-constrained problem: (grad_times, grad_waypoints, grad_bc) as numpy for grad_coeff = dPhi/dcoeff in
