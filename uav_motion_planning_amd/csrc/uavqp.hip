@@ -683,7 +683,7 @@ static bool captured_chain(hipGraph_t graph, std::vector<hipGraphNode_t>& order)
 }
 
 // What uavqp_capture_end hands out: the stages of a replay, each a set of chain graphs that run side by side (uavqp_capture.h:
-// stage_starts).  A capture that is replayed as captured is one stage of one lane.
+// lay_out).  A capture that is replayed as captured is one stage of one lane.
 struct CapturedGraph {
     std::vector<std::vector<hipGraphExec_t>> stage;
     ~CapturedGraph() {
@@ -693,7 +693,7 @@ struct CapturedGraph {
 };
 
 // The same launches as `captured`, ordered by what they touch instead of by when they were enqueued (uavqp_capture.h): independent solves
-// go to different lanes, at most `lanes` of them.  False when the capture is not exactly the recorded launches of
+// go to different lanes, at most `lanes` of them, and a solve that conflicts with an earlier one follows it in that one's lane.  False when the capture is not exactly the recorded launches of
 // uavqp_solve_batch_device, when nothing in it is independent, or when the runtime refuses a step: the caller keeps the captured graph.
 // (Measured: ONE graph with parallel branches replays slower than the captured chain -- the runtime leaves its single-queue fast path --
 //  so every lane of a stage is a chain graph of its own: docs/measurement_log.md.)
@@ -709,25 +709,28 @@ static bool rebuild_captured(uavqp_ctx* ctx, hipGraph_t captured, int lanes, int
         if (hipGraphKernelNodeGetParams(order[k], &p) != hipSuccess) return false;
         if ((l.fn && p.func != l.fn) || p.gridDim.x != l.grid.x || p.gridDim.y != l.grid.y || p.gridDim.z != l.grid.z) return false;
     }
-    const uavqp_capture::Plan plan = uavqp_capture::analyse(ctx->cap_rec, lanes);
-    if (!plan.parallel) return false;
-    std::vector<int> starts = uavqp_capture::stage_starts(plan, lanes);
+    if (n > uavqp_capture::NODES_MAX) return false;
+    const std::vector<char> status_dead = uavqp_capture::dead_status_stores(ctx->cap_rec);
+    const uavqp_capture::Layout lay = uavqp_capture::lay_out(ctx->cap_rec, status_dead, lanes);
+    if (!lay.parallel) return false;
+    std::vector<int> starts = lay.starts;
     starts.push_back((int)n);
     bool side_by_side = false;
+    // (The width of a stage goes by its launches in all, not by how they are spread: a stage that is one long chain and a few single
+    //  solves pays a fork / join for each of those.  A rotation, what the layout is for, deals its chains evenly.)
     for (size_t s = 0; s + 1 < starts.size(); ++s) {
         const int first = starts[s], width = uavqp_capture::lanes_that_pay(starts[s + 1] - first, lanes, nodes_per_lane);
-        side_by_side |= width > 1;
         out.stage.emplace_back();
-        for (int lane = 0; lane < width; ++lane) {   // node k of the stage: lane (k % lanes) % width
+        for (int lane = 0; lane < width; ++lane) {   // node k of the stage: chain lay.lane[k] % width, in capture order
             hipGraph_t graph = nullptr;
-            if (hipGraphCreate(&graph, 0) != hipSuccess) return false;
             hipGraphNode_t prev = nullptr;
             bool ok = true;
             for (int k = first; ok && k < starts[s + 1]; ++k) {
-                if ((k % lanes) % width != lane) continue;
+                if (lay.lane[k] % width != lane) continue;
+                if (!graph && hipGraphCreate(&graph, 0) != hipSuccess) return false;
                 const CapturedLaunch& l = ctx->cap_launch[k];
                 BatchArgs a = l.args;
-                if (plan.status_dead[k]) a.status = nullptr;   // a later solve overwrites every one of them before anything reads one
+                if (status_dead[k]) a.status = nullptr;        // a later solve overwrites every one of them before anything reads one
                 void* kernel_params[1] = {&a};
                 hipKernelNodeParams p = params[k];             // a barrier: as captured
                 if (l.fn) {
@@ -742,12 +745,14 @@ static bool rebuild_captured(uavqp_ctx* ctx, hipGraph_t captured, int lanes, int
                 ok = hipGraphAddKernelNode(&node, graph, prev ? &prev : nullptr, prev ? 1 : 0, &p) == hipSuccess;   // (the arguments are copied into the node)
                 prev = node;
             }
+            if (!graph) continue;   // the lanes of a stage fill from 0 up: a stage with fewer busy lanes than `width` has them in front
             hipGraphExec_t exec = nullptr;
             ok = ok && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
             (void)hipGraphDestroy(graph);
             if (!ok) return false;
             out.stage.back().push_back(exec);
         }
+        side_by_side |= out.stage.back().size() > 1;
     }
     if (!side_by_side) return false;
     // the streams and events the replay forks to and joins through
@@ -768,7 +773,7 @@ extern "C" int uavqp_capture_end(uavqp_ctx* ctx, void** out_graph_exec) {
     } forget{ctx};
     hipGraph_t graph = nullptr;
     UAVQP_HIP(hipStreamEndCapture(ctx->stream, &graph));
-    // UAVQP_CAPTURE_LANES = 1..8 (A/B runs; 1 = replay the chain as captured).  GPU_MAX_HW_QUEUES is only read: a process given fewer
+    // UAVQP_CAPTURE_LANES = 1..8 (A/B runs; 1 = replay the chain as captured; not set: 2, uavqp_capture.h: REPLAY_LANES_DEFAULT).  GPU_MAX_HW_QUEUES is only read: a process given fewer
     // than 4 hardware queues keeps the chain.  UAVQP_CAPTURE_LANE_NODES: the launches a stage must have per lane (default 16).
     const uavqp_capture::Knobs knobs = uavqp_capture::knobs_from_environment();
     const int lanes = ctx->capturing ? knobs.lanes : 1;

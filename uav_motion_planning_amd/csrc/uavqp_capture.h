@@ -1,7 +1,10 @@
-// uavqp_capture.h -- which captured solves may run side by side when their graph is replayed: the dependency analysis behind
-// uavqp_capture_end (uavqp.hip).  A stream capture orders every launch behind the one before it; steps of a launch-bound inner loop
-// usually touch disjoint buffers, and about 30 % of each is the GPU idling at that kernel boundary (docs/measurement_log.md 5.1, 6, 7).
-// Host-only: byte ranges and indices, no HIP type -- compiles without the runtime (tests/cpp/test_capture_deps.cpp).
+// uavqp_capture.h -- which captured solves may run side by side when their graph is replayed, and in which lane each of them goes: the
+// dependency analysis and the lane layout behind uavqp_capture_end (uavqp.hip).  A stream capture orders every launch behind the one
+// before it; steps of a launch-bound inner loop usually touch disjoint buffers, and about 30 % of each is the GPU idling at that kernel
+// boundary (docs/measurement_log.md 5.1, 6, 7).  The replay is laid out by lay_out: a solve follows the solve it conflicts with into that
+// solve's lane, so a rotation over any number of buffer sets is ONE stage of chains.  analyse / stage_starts are the layout before it
+// (lane of node k: k % lanes), kept with their results as the reference the conflict rules are pinned against.
+// Host-only: byte ranges and indices, no HIP type -- compiles without the runtime (tests/cpp/test_capture_deps.cpp, test_capture_lanes.cpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -154,10 +157,94 @@ static inline int lanes_that_pay(int nodes, int lanes, int nodes_per_lane = NODE
     return by_size < 1 ? 1 : (by_size < lanes ? by_size : lanes);
 }
 
+// The layout a capture is replayed with: the lane of every node, the first node of every stage, and whether any stage has two busy lanes.
+// In capture order, with s the first node of the current stage and P the lanes of the nodes of [s, k) that node k conflicts with:
+//   P empty     node k takes the least-loaded lane of the stage (ties: the lowest index), so the lanes of a stage fill from lane 0 up;
+//   P one lane  node k takes it and follows its predecessor in that lane's chain -- the only ordering a stage provides;
+//   P more      the lanes have to meet: a new stage starts at k, in lane 0.
+// A barrier is a stage of its own.  More than NODES_MAX nodes, or one lane: one stage, everything in lane 0.
+// Hence: two conflicting nodes are in different stages (ordered by the join) or in the same lane (ordered by the chain).  Lanes may be
+// merged afterwards in any combination (lane % w): that only adds order.  `status_dead` is dead_status_stores(rec), or all zero.
+// The scan is one conflict test per earlier node of the stage; a node's hull (every byte it reads or writes, a dead status store left
+// out) rejects most pairs in two comparisons, so 4096 nodes stay in the milliseconds.
+struct Layout {
+    std::vector<int> lane, starts;
+    bool parallel = false;
+};
+static inline Layout lay_out(const std::vector<Record>& rec, const std::vector<char>& status_dead, int lanes) {
+    const int n = (int)rec.size();
+    Layout out;
+    out.lane.assign((size_t)n, 0);
+    if (n == 0) return out;
+    if ((size_t)n > NODES_MAX || lanes <= 1 || status_dead.size() != (size_t)n) {
+        out.starts.push_back(0);
+        return out;
+    }
+    if (lanes > LANES_MAX) lanes = LANES_MAX;
+    std::vector<Range> hull((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        Range h;
+        h.lo = UINTPTR_MAX;
+        const Range* part[5] = {&rec[k].read[0], &rec[k].read[1], &rec[k].read[2], &rec[k].coeff, &rec[k].status};
+        for (int q = 0; q < (status_dead[k] ? 4 : 5); ++q) {
+            if (part[q]->empty()) continue;
+            if (part[q]->lo < h.lo) h.lo = part[q]->lo;
+            if (part[q]->hi > h.hi) h.hi = part[q]->hi;
+        }
+        hull[k] = h;
+    }
+    int load[LANES_MAX] = {};
+    int s = 0;
+    bool fresh = true;   // the next node starts a stage
+    for (int k = 0; k < n; ++k) {
+        unsigned met = 0;    // bit l: node k conflicts with a node of lane l of this stage
+        bool cut = fresh || rec[k].barrier;
+        for (int i = s; !cut && i < k; ++i) {
+            if (!hull[i].overlaps(hull[k]) || !conflict(rec[i], status_dead[i] != 0, rec[k], status_dead[k] != 0)) continue;
+            met |= 1u << out.lane[i];
+            cut = (met & (met - 1)) != 0;
+        }
+        if (cut) {
+            out.starts.push_back(k);
+            s = k;
+            for (int l = 0; l < lanes; ++l) load[l] = 0;
+            load[0] = 1;
+            fresh = rec[k].barrier;
+            continue;
+        }
+        int lane = 0;
+        if (met) {
+            while (!(met >> lane & 1)) ++lane;
+        } else {
+            for (int l = 1; l < lanes; ++l)
+                if (load[l] < load[lane]) lane = l;
+        }
+        out.lane[k] = lane;
+        ++load[lane];
+        if (lane != 0) out.parallel = true;   // lane 0 holds the first node of the stage
+    }
+    return out;
+}
+
+// The lanes of a replay when UAVQP_CAPTURE_LANES does not name a count: 2, the ctx stream and ONE stream of the ctx's own.  A lane gains
+// only where its stream has a hardware queue to itself, and HIP neither says nor lets a caller choose which queue a stream gets.  Measured
+// (docs/measurement_log.md, 2026-10-18): the ctx stream and the first lane stream had a queue each in every kind of process; in a plain
+// process the second and third shared those two queues (a kernel trace shows the four streams on two queues, in pairs), so 4 lanes
+// replayed no faster than 2, while in a process whose communication library had created streams first they did not share and 4 lanes were
+// 10 % faster -- a replay whose speed depends on what else the process did before.  Two lanes replay alike in both.  A count that
+// UAVQP_CAPTURE_LANES names is taken as it is (lanes_from_env), and fewer than 4 hardware queues keep the chain either way.
+static constexpr int REPLAY_LANES_DEFAULT = 2;
+static inline int replay_lanes_from_env(const char* lanes_env, const char* hw_queues_env) {
+    const int lanes = lanes_from_env(lanes_env, hw_queues_env);
+    const int asked = lanes_env && *lanes_env ? std::atoi(lanes_env) : 0;
+    if (asked >= 1 && asked <= LANES_MAX) return lanes;
+    return lanes < REPLAY_LANES_DEFAULT ? lanes : REPLAY_LANES_DEFAULT;
+}
+
 // The two knobs as the process environment has them NOW: read when a capture ends (uavqp_capture_end), never on a launch path.
 struct Knobs { int lanes, nodes_per_lane; };
 static inline Knobs knobs_from_environment() {
-    return Knobs{lanes_from_env(std::getenv("UAVQP_CAPTURE_LANES"), std::getenv("GPU_MAX_HW_QUEUES")), lane_nodes_from_env(std::getenv("UAVQP_CAPTURE_LANE_NODES"))};
+    return Knobs{replay_lanes_from_env(std::getenv("UAVQP_CAPTURE_LANES"), std::getenv("GPU_MAX_HW_QUEUES")), lane_nodes_from_env(std::getenv("UAVQP_CAPTURE_LANE_NODES"))};
 }
 
 }  // namespace uavqp_capture
