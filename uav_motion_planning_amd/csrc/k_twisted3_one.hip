@@ -1,0 +1,5 @@
+// k_twisted3_one.hip -- solve_twisted_kernel<3, M, TILE, LPT, true> (qp_twisted.h): the latency shapes for launches of one whole tile per wave.
+#define UAVQP_KERNEL_TU
+#include "qp_twisted.h"
+#include "kernel_instances.h"
+UAVQP_INSTANCES_TWISTED3_ONE

@@ -66,15 +66,18 @@ struct TwistedCfg {
     static_assert(WP_D % 2 == 0 && T_D % 2 == 0 && BC_D % 2 == 0, "tile arrays must be whole 16-B pairs");
 };
 
-template <int R, int M, int TILE, int LPT = 2>
+// ONE (latency shapes): the launch has exactly one WHOLE tile per wave (grid == n_tiles, n_traj % TILE == 0 -- the host checks both):
+// no shifted or guarded tile, no prefetch and no second input buffer, nothing that depends on the batch size; the tile loop makes one trip.
+template <int R, int M, int TILE, int LPT = 2, bool ONE = false>
 __global__ __launch_bounds__(64, 1) void solve_twisted_kernel(BatchArgs a) {
     using C = TwistedCfg<R, M, TILE, LPT>;
     constexpr int NAX = C::NAX;
     constexpr int ND = C::ND, NC = C::NC, NK = C::NK, mL = C::mL, mR = C::mR;
     static_assert(M >= 2, "twisted kernel needs an interior knot");
+    static_assert(!ONE || LPT >= 8, "one tile per wave: latency shapes only");
     static_assert((LPT == 2 && (TILE == 32 || TILE == 16)) || (LPT == 8 && TILE == 8) || (LPT == 16 && TILE == 4), "tile shapes: 2 lanes x 32|16, 8 lanes x 8, 16 lanes x 4");
 
-    __shared__ __attribute__((aligned(16))) double s_in[2][C::IN_D];
+    __shared__ __attribute__((aligned(16))) double s_in[ONE ? 1 : 2][C::IN_D];
     __shared__ __attribute__((aligned(16))) double s_out[C::OUT_D];
     (void)s_out;
 
@@ -86,7 +89,12 @@ __global__ __launch_bounds__(64, 1) void solve_twisted_kernel(BatchArgs a) {
     const int sub = LPT == 16 ? (lane >> 3) & 1 : 0;   // LPT == 16: which half of the own segments this lane pair emits
     const int ax0 = LPT == 2 ? 0 : (axl < 3 ? axl : 2);
     const int m = isR ? mR : mL;
-    const int n_tiles = (a.n_traj + TILE - 1) / TILE;
+    // ONE: this wave's tile is its only one.  The trip count of 1 is hidden from the compiler so that a LOOP remains: everything
+    // invariant (lane indices, addresses, the output descriptor) is then hoisted in front of it, i.e. in front of the wait for the loads
+    // below, where it costs nothing -- in straight-line code it is scheduled behind the wait, on the wave's critical path.
+    int one_trip = 1;
+    if constexpr (ONE) asm volatile("" : "+s"(one_trip));
+    const int n_tiles = ONE ? (int)blockIdx.x + one_trip : (a.n_traj + TILE - 1) / TILE;
 
     // A partial last tile is SHIFTED back so that it ends at the batch end (n_traj >= TILE): it stays on the LDS-DMA path and
     // re-solves a few trajectories of its neighbour -- identical values written twice -- instead of sending one wave through the
@@ -94,14 +102,15 @@ __global__ __launch_bounds__(64, 1) void solve_twisted_kernel(BatchArgs a) {
     // Batches smaller than one tile keep the guarded path.
     auto tile_base = [&](int tile) {
         const int b_ = tile * TILE;
+        if constexpr (ONE) return b_;
         return (a.n_traj >= TILE && b_ + TILE > a.n_traj) ? a.n_traj - TILE : b_;
     };
     constexpr int DMA_AUX = LPT >= 8 ? 2 : 0;
     auto issue_tile = [&](int tile, int buf) {
         const int base = tile_base(tile);
-        const int nv = min(TILE, a.n_traj - base);
+        const int nv = ONE ? TILE : min(TILE, a.n_traj - base);
         double* s = s_in[buf];
-        if (nv == TILE) {
+        if (ONE || nv == TILE) {
             dma_tile<C::WP_D, DMA_AUX>(a.waypoints + (size_t)base * NK * 3, s, lane);
             dma_tile<C::T_D, DMA_AUX>(a.times + (size_t)base * M, s + C::T_OFF, lane);
             dma_tile<C::BC_D, DMA_AUX>(a.bc + (size_t)base * 2 * ND * 3, s + C::BC_OFF, lane);
@@ -117,7 +126,7 @@ __global__ __launch_bounds__(64, 1) void solve_twisted_kernel(BatchArgs a) {
     if ((int)blockIdx.x < n_tiles) issue_tile(blockIdx.x, 0);
     UAVQP_STAMP(6);
 
-    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x, buf ^= 1) {
+    for (int tile = blockIdx.x; tile < n_tiles; tile += (ONE ? 1 : gridDim.x), buf ^= (ONE ? 0 : 1)) {
         // The wait for the FIRST tile sits inside the loop: everything loop-invariant (lane indices, table constants, addresses --
         // ~130 instructions) lands in the loop pre-header, i.e. between the issue of the first loads and this wait, instead of
         // behind it (measured: load wait 2150 -> 1230 cycles per wave, 5.49 -> 5.05 us on the 4096 batch).
@@ -126,10 +135,12 @@ __global__ __launch_bounds__(64, 1) void solve_twisted_kernel(BatchArgs a) {
             wave_lds_sync();
         }
         const int base = tile_base(tile);
-        const int nv = min(TILE, a.n_traj - base);
+        const int nv = ONE ? TILE : min(TILE, a.n_traj - base);
         UAVQP_STAMP(0);
         // prefetch the next tile into the other buffer; it lands while this tile is eliminated
-        if (tile + (int)gridDim.x < n_tiles) issue_tile(tile + gridDim.x, buf ^ 1);
+        if constexpr (!ONE) {
+            if (tile + (int)gridDim.x < n_tiles) issue_tile(tile + gridDim.x, buf ^ 1);
+        }
         UAVQP_STAMP(1);
 
         const double* __restrict__ s_wp = s_in[buf];
@@ -338,7 +349,7 @@ __global__ __launch_bounds__(64, 1) void solve_twisted_kernel(BatchArgs a) {
 
         // The prefetched tile has had the whole elimination to land; this also retires the previous
         // tile's stores (issued before the prefetch) so that the waits below never see them.
-        wait_vmcnt0();
+        if constexpr (!ONE) wait_vmcnt0();
 
         // ---------------- back-substitution + emission of own segments j = m-1 .. 0 ----------------
         bool finite = true;

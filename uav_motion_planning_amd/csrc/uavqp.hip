@@ -46,6 +46,8 @@
 #include "kernel_instances.h"
 UAVQP_INSTANCES_TWISTED3
 UAVQP_INSTANCES_TWISTED4
+UAVQP_INSTANCES_TWISTED3_ONE
+UAVQP_INSTANCES_TWISTED4_ONE
 UAVQP_INSTANCES_GENERIC
 UAVQP_INSTANCES_CORRIDOR
 UAVQP_INSTANCES_CORRIDOR_DUAL
@@ -65,13 +67,16 @@ namespace uavqp {
 // Specialised (R, M) instantiations of the register-resident kernel; everything else takes the generic one.
 typedef void (*twisted_fn)(BatchArgs);
 template <int R, int M>
-static twisted_fn twisted_ptr(int tile) {
+static twisted_fn twisted_ptr(int tile, bool one) {
+    // one: exactly one whole tile per wave -- the instantiation without the tile loop (latency shapes only)
+    if (one && tile == 4) return &solve_twisted_kernel<R, M, 4, 16, true>;
+    if (one && tile == 8) return &solve_twisted_kernel<R, M, 8, 8, true>;
     if (tile == 4) return &solve_twisted_kernel<R, M, 4, 16>;  // two lane pairs per axis: emission split in two (smallest batches)
     if (tile == 8) return &solve_twisted_kernel<R, M, 8, 8>;  // one lane pair per axis (latency shape)
     return tile == 16 ? &solve_twisted_kernel<R, M, 16> : &solve_twisted_kernel<R, M, 32>;
 }
-static twisted_fn find_twisted(int r, int M, int tile) {
-#define UAVQP_CASE(RR, MM) if (r == RR && M == MM) return twisted_ptr<RR, MM>(tile);
+static twisted_fn find_twisted(int r, int M, int tile, bool one) {
+#define UAVQP_CASE(RR, MM) if (r == RR && M == MM) return twisted_ptr<RR, MM>(tile, one);
     UAVQP_CASE(4, 2) UAVQP_CASE(4, 3) UAVQP_CASE(4, 4) UAVQP_CASE(4, 5) UAVQP_CASE(4, 6) UAVQP_CASE(4, 7)
     UAVQP_CASE(4, 8) UAVQP_CASE(4, 9) UAVQP_CASE(4, 10) UAVQP_CASE(4, 12)
     UAVQP_CASE(3, 2) UAVQP_CASE(3, 3) UAVQP_CASE(3, 4) UAVQP_CASE(3, 5) UAVQP_CASE(3, 6) UAVQP_CASE(3, 7)
@@ -449,14 +454,22 @@ extern "C" int uavqp_solve_batch_device(uavqp_ctx* ctx, int r, int n_traj, int u
         // One CU moves only ~10 B/clk, so a small batch is spread over all CUs with fewer trajectories per wave (tile 4: 16 lanes per
         // trajectory, every SIMD busy up to 16 trajectories per CU; tile 8: 8 lanes); a large one wants the full-wave shape that does
         // the least redundant work.  Tile 16 no longer wins anywhere (it stays selectable through uavqp_set_variant).
-        int tile = (n_traj <= 16 * ctx->num_cus) ? 4 : ((n_traj <= 96 * ctx->num_cus) ? 8 : 32);
+        // 2026-10-18, with the one-tile-per-wave instantiations, tiles 4 / 8, us per step (bench.py, medians of three runs): replayed graph of 1500
+        // steps on two lanes  2048: 2.83 / 2.77   3072: 3.09 / 3.12   4096: 3.38 / 3.31;  of 200 steps  3.08 / 3.07, 3.35 / 3.37, 3.65 / 3.53;  of 20
+        // steps (one chain)  5.46 / 5.61, 5.92 / 6.27, 6.08 / 6.35;  eager  5.77 / 5.82, 6.27 / 5.52, 5.73 / 5.88.  Tile 8 is 2-3 % ahead under a
+        // two-lane replay at 4096 and 3-6 % behind in the chain of 20 and isolated: the threshold stays.
+        int tile = (n_traj <= 16 * ctx->num_cus) ? 4 :((n_traj <= 96 * ctx->num_cus) ? 8 : 32);
         if (ctx->tile_override) tile = ctx->tile_override;
-        uavqp::twisted_fn fn = uavqp::find_twisted(r, uniform_segments, tile);
+        const int n_tiles = (n_traj + tile - 1) / tile;
+        const int max_wg = ctx->num_cus * 4;  // 1 wave / SIMD (register-resident state), persistent over tiles
+        const int g = n_tiles < max_wg ? n_tiles : max_wg;
+        // One whole tile per wave (whole tiles only, no more tiles than waves): the instantiation without the shifted and the guarded
+        // tile, the prefetch and the second input buffer (4096 x 8-segment snap: traced kernel 5.24 -> 4.60 us, replayed step 3.60 -> 3.39).  A function of n_traj and the CU count alone, like the tile: eager and captured
+        // launches choose the same kernel.
+        const bool one = g == n_tiles && n_traj % tile == 0;
+        uavqp::twisted_fn fn = uavqp::find_twisted(r, uniform_segments, tile, one);
         if (fn) {
             a.ws = nullptr;
-            const int n_tiles = (n_traj + tile - 1) / tile;
-            const int max_wg = ctx->num_cus * 4;  // 1 wave / SIMD (register-resident state), persistent over tiles
-            int g = n_tiles < max_wg ? n_tiles : max_wg;
             hipLaunchKernelGGL(fn, dim3(g), dim3(64), 0, ctx->stream, a);
             UAVQP_HIP(hipGetLastError());
             if (ctx->capturing) capture_note(ctx, (const void*)fn, dim3(g), dim3(64), 0, &a, r);   // no workspace of the ctx: the one analysable launch
