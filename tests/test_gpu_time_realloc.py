@@ -1,4 +1,4 @@
-"""-m gpu: uavqp_time_reallocate_device (realloc_kernel<3> / <4>, csrc/qp_core_kernels.h) against the np.longdouble restatement of the
+"""-m gpu: uavqp_time_reallocate_device (realloc_kernel<3> / <4>, csrc/qp_samplers.h) against the np.longdouble restatement of the
 rule in include/uavqp.h (tests/time_realloc_reference.py), and the corridor pipeline against the sequence of public entry points its
 header comment describes.
 

@@ -7,6 +7,7 @@
 // flags are identical to the exhaustive scan.
 #pragma once
 #include "qp_core_kernels.h"
+#include "qp_poly.h"
 #include "qp_wave_utils.h"
 
 namespace uavqp {
@@ -160,26 +161,11 @@ struct CorridorRow {
 #pragma unroll
             for (int ax = 0; ax < 3; ++ax) {
                 const double* ca = a.coeff + (size_t)3 * NC * s0 + ((size_t)ax * M + seg) * NC;
-                if (k < M) {
-                    acc[ax] = 2.0 * ca[2];
-                } else {
-                    const double t = a.times[s0 + seg];
-                    double av = 0.0;
-#pragma unroll
-                    for (int j = NC - 1; j >= 2; --j) av = fma(av, t, (double)(j * (j - 1)) * ca[j]);
-                    acc[ax] = av;
-                }
+                acc[ax] = k < M ? 2.0 * ca[2] : poly_deriv<NC, 2>(ca, a.times[s0 + seg]);
             }
         }
-        // kino_astar.cpp:724-727
-        const double n3 = sqrt(acc[0] * acc[0] + acc[1] * acc[1] + (acc[2] + 9.81) * (acc[2] + 9.81));
-        const double b3[3] = {acc[0] / n3, acc[1] / n3, (acc[2] + 9.81) / n3};
-        const double c2y = b3[2], c2z = -b3[1];  // b3 x (1,0,0) = (0, b3z, -b3y)
-        const double n2 = sqrt(c2y * c2y + c2z * c2z);
-        const double b2[3] = {0.0, c2y / n2, c2z / n2};
-        double b1[3] = {b2[1] * b3[2] - b2[2] * b3[1], b2[2] * b3[0] - b2[0] * b3[2], b2[0] * b3[1] - b2[1] * b3[0]};
-        const double n1 = sqrt(b1[0] * b1[0] + b1[1] * b1[1] + b1[2] * b1[2]);
-        b1[0] /= n1; b1[1] /= n1; b1[2] /= n1;
+        double b1[3], b2[3], b3[3];
+        poly_body_frame(acc, b1, b2, b3);
         b3v[0] = b3[0]; b3v[1] = b3[1]; b3v[2] = b3[2];
         const double wr = 1.0 / (a.robot_r * a.robot_r), wh = 1.0 / (a.robot_h * a.robot_h);
         qxx = (b1[0] * b1[0] + b2[0] * b2[0]) * wr + b3[0] * b3[0] * wh;
@@ -562,52 +548,27 @@ __global__ __launch_bounds__(64) void ellipsoid_grid_kernel(EllipsoidGridArgs a)
         const bool live = g < total;
         const int b = live ? (int)(g / a.n_samples) : 0;
         const int s = live ? (int)(g - (long long)b * a.n_samples) : 0;
-        int s0 = 0, M = 0;
-        if (live) {
-            if (a.uniform > 0) { M = a.uniform; s0 = b * M; } else { s0 = a.seg_offsets[b]; M = a.seg_offsets[b + 1] - s0; }
-        }
-        const double* __restrict__ T = a.times + s0;
-        double t = a.t0 + s * dt;
-        int idx = 0;
-        while (idx < M && t > T[idx] + 1e-4) { t -= T[idx]; ++idx; }
+        const auto [s0, M] = live ? poly_span(a.uniform, a.seg_offsets, b) : PolySpan{0, 0};
+        const PolySeg at = M >= 1 ? poly_segment(a.times + s0, M, a.t0 + s * dt) : PolySeg{0, 0.0, false};
         // Past the end the sample is the end point.  All trajectories are sampled on one grid (the pipeline's dt comes from the LONGEST of
         // the batch), so a trajectory of average length has most of its samples there -- and every one after the first repeats that
         // one's verdict at a larger index: it cannot lower first_hit.  Left out when no per-sample flags are asked for.  (Whether the
         // previous sample is past the end is its lane's own finding, one lane down; lane 0 has nobody to ask and is simply tested.)
-        const int past = (M >= 1 && idx == M) ? 1 : 0;
+        const int past = at.past ? 1 : 0;
         const int past_prev = __shfl_up(past, 1, 64);
         const bool repeats = !a.flags && past && s > 0 && lane > 0 && past_prev;
         const bool act = live && M >= 1 && !repeats;   // (M < 1: zero-segment trajectory, flagged invalid by the solver: reported collision-free)
         bool hit = false;
         int cnt = 0;
         if (act) {
-            if (idx == M) { --idx; t = T[idx]; }
             double f[12], acc[3];
 #pragma unroll
             for (int ax = 0; ax < 3; ++ax) {
-                const double* ca = a.coeff + (size_t)3 * NC * s0 + ((size_t)ax * M + idx) * NC;
-                double pv = 0.0, av = 0.0;
-#pragma unroll
-                for (int j = NC - 1; j >= 0; --j) pv = fma(pv, t, ca[j]);
-#pragma unroll
-                for (int j = NC - 1; j >= 2; --j) av = fma(av, t, (double)(j * (j - 1)) * ca[j]);
-                f[ax] = pv;
-                acc[ax] = av;
+                const double* ca = a.coeff + (size_t)3 * NC * s0 + ((size_t)ax * M + at.idx) * NC;
+                f[ax] = poly_deriv<NC, 0>(ca, at.t);
+                acc[ax] = poly_deriv<NC, 2>(ca, at.t);
             }
-            // kino_astar.cpp:724-727
-            const double n3 = sqrt(acc[0] * acc[0] + acc[1] * acc[1] + (acc[2] + 9.81) * (acc[2] + 9.81));
-            const double b3[3] = {acc[0] / n3, acc[1] / n3, (acc[2] + 9.81) / n3};
-            const double c2[3] = {0.0, b3[2], -b3[1]};  // b3 x (1,0,0)
-            const double n2 = sqrt(c2[1] * c2[1] + c2[2] * c2[2]);
-            const double b2[3] = {0.0, c2[1] / n2, c2[2] / n2};
-            const double c1[3] = {b2[1] * b3[2] - b2[2] * b3[1], b2[2] * b3[0] - b2[0] * b3[2], b2[0] * b3[1] - b2[1] * b3[0]};
-            const double n1 = sqrt(c1[0] * c1[0] + c1[1] * c1[1] + c1[2] * c1[2]);
-#pragma unroll
-            for (int ax = 0; ax < 3; ++ax) {
-                f[3 + ax] = c1[ax] / n1;
-                f[6 + ax] = b2[ax];
-                f[9 + ax] = b3[ax];
-            }
+            poly_body_frame(acc, f + 3, f + 6, f + 9);
             int lo_c[3], hi_c[3];
 #pragma unroll
             for (int ax = 0; ax < 3; ++ax) {

@@ -220,6 +220,8 @@ __global__ __launch_bounds__(ESDF_BLOCK) void esdf_query_kernel(EsdfQueryArgs a)
 template <int R>
 __global__ __launch_bounds__(64) void clearance_penalty_kernel(ClearanceArgs a) {
     constexpr int NC = 2 * R, LPT = TOPT_LPT;
+    // (the loop of topt_for_each_group written out: through the lambda the compiler stops peeling the sample loop, which moves the last bits
+    // of the penalty and of its time gradient -- docs/measurement_log.md)
     const int sub = threadIdx.x % LPT;
     const long long n_lanes = (long long)a.n_traj * LPT;
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -228,10 +230,7 @@ __global__ __launch_bounds__(64) void clearance_penalty_kernel(ClearanceArgs a) 
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < n_round; g += stride) {
         const bool live = g < n_lanes;
         const int b = live ? (int)(g / LPT) : 0;
-        int s0 = 0, M = 0;
-        if (live) {
-            if (a.uniform > 0) { M = a.uniform; s0 = b * M; } else { s0 = a.seg_offsets[b]; M = a.seg_offsets[b + 1] - s0; }
-        }
+        const auto [s0, M] = live ? poly_span(a.uniform, a.seg_offsets, b) : PolySpan{0, 0};
         const size_t axs = (size_t)NC * (M > 0 ? M : 0);
         const bool solved = live && M > 0 && (!a.status || a.status[b] == UAVQP_SOLVED);
         double Phi = 0.0, neg_min = -INFINITY;   // (the minimum as a maximum of negatives: topt_group_max)

@@ -9,7 +9,7 @@
 //     dPhi/dT_i         = Phi_i / T_i + (T_i / K) sum_s om_s tau_s [ c_v v.a + c_a a.j ]                      (coefficients fixed)
 // The total gradient in the durations adds the part through c*(T): uavqp_solve_backward_device with g = dPhi/dc.
 //
-// Lanes.  The idiom of qp_time_opt.h: eight lanes per trajectory, sub-lane j owns segments j, j + 8, ..., sums by the xor butterfly, whole
+// Lanes.  The lane groups of qp_poly.h: eight lanes per trajectory, sub-lane j owns segments j, j + 8, ..., sums by the xor butterfly, whole
 // waves take part.  A lane loads the 3 * 2r coefficients of its segment once, evaluates v, a, j of the three axes at the K + 1 points by
 // Horner, keeps the 3 * 2r partial sums of dPhi/dc in registers and stores them once per segment: every output element is written exactly
 // once (zeros included), and the order of the additions is fixed by the sample and segment indices alone.
@@ -70,6 +70,8 @@ __device__ inline void lim_store(double* __restrict__ p, const double (&x)[NC], 
 template <int R>
 __global__ __launch_bounds__(64) void limit_penalty_kernel(LimitArgs a) {
     constexpr int NC = 2 * R, LPT = TOPT_LPT;
+    // (the loop of topt_for_each_group written out, as in clearance_penalty_kernel: through the lambda the compiler shapes the sample loop
+    // differently -- docs/measurement_log.md)
     const int sub = threadIdx.x % LPT;
     const long long n_lanes = (long long)a.n_traj * LPT;
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -78,10 +80,7 @@ __global__ __launch_bounds__(64) void limit_penalty_kernel(LimitArgs a) {
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < n_round; g += stride) {
         const bool live = g < n_lanes;
         const int b = live ? (int)(g / LPT) : 0;
-        int s0 = 0, M = 0;
-        if (live) {
-            if (a.uniform > 0) { M = a.uniform; s0 = b * M; } else { s0 = a.seg_offsets[b]; M = a.seg_offsets[b + 1] - s0; }
-        }
+        const auto [s0, M] = live ? poly_span(a.uniform, a.seg_offsets, b) : PolySpan{0, 0};
         const size_t axs = (size_t)NC * (M > 0 ? M : 0);
         const bool solved = live && M > 0 && (!a.status || a.status[b] == UAVQP_SOLVED);
         double Phi = 0.0, vv_max = 0.0, aa_max = 0.0;

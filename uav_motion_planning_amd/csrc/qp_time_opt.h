@@ -11,24 +11,15 @@
 //   r = 3: H = j^2 - 2 s a + 2 c v          r = 4: H = s^2 - 2 c j + 2 p a - 2 q v        (v a j s c p q = derivatives 1..7 at t = 0)
 // This holds for the equality-constrained solve (and for knot boxes); NOT for rows placed at a fraction of T_i.
 //
-// Lanes.  The lane-group idiom of realloc_kernel (qp_core_kernels.h): eight lanes per trajectory, sub-lane j takes segments j, j + 8, ...,
-// sums are combined with three xor-shuffles (a butterfly: every lane of the group ends with the same bits, and the order of the additions is
-// fixed by the segment index alone -- the same result run to run and for any grid), grid-stride over whole waves.
+// Lanes.  The lane groups of qp_poly.h (topt_for_each_group, topt_group_sum / topt_group_max), as realloc_kernel (qp_samplers.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/uavqp.h"
+#include "qp_poly.h"
 
 namespace uavqp {
-
-constexpr int TOPT_LPT = 8;   // lanes per trajectory
-
-__host__ __device__ constexpr double topt_falling(int k, int d) {   // k! / (k - d)!
-    double f = 1.0;
-    for (int j = 0; j < d; ++j) f *= (double)(k - j);
-    return f;
-}
 
 // c' P c of one segment, three axes (c: the segment's coefficients of axis 0, axis stride in doubles)
 template <int R>
@@ -74,17 +65,6 @@ __device__ inline double topt_segment_H(const double* __restrict__ c, size_t axi
     return H;
 }
 
-__device__ inline double topt_group_sum(double x) {
-#pragma unroll
-    for (int d = 1; d < TOPT_LPT; d <<= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
-__device__ inline double topt_group_max(double x) {
-#pragma unroll
-    for (int d = 1; d < TOPT_LPT; d <<= 1) x = fmax(x, __shfl_xor(x, d, 64));
-    return x;
-}
-
 // ---------------------------------------------------------------------------------------------------
 // cost[b] = J_b, grad[s0_b + i] = dJ_b / dT_i of solved trajectories (either output may be null)
 // ---------------------------------------------------------------------------------------------------
@@ -100,17 +80,8 @@ struct CostGradArgs {
 template <int R>
 __global__ __launch_bounds__(64) void cost_grad_kernel(CostGradArgs a) {
     constexpr int NC = 2 * R, LPT = TOPT_LPT;
-    const int sub = threadIdx.x % LPT;
-    const long long n_lanes = (long long)a.n_traj * LPT;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    const long long n_round = (n_lanes + stride - 1) / stride * stride;  // whole waves take part in the shuffles
-    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < n_round; g += stride) {
-        const bool live = g < n_lanes;
-        const int b = live ? (int)(g / LPT) : 0;
-        int s0 = 0, M = 0;
-        if (live) {
-            if (a.uniform > 0) { M = a.uniform; s0 = b * M; } else { s0 = a.seg_offsets[b]; M = a.seg_offsets[b + 1] - s0; }
-        }
+    topt_for_each_group(a.n_traj, [&](bool live, int b, int sub) {
+        const auto [s0, M] = live ? poly_span(a.uniform, a.seg_offsets, b) : PolySpan{0, 0};
         const size_t axs = (size_t)NC * (M > 0 ? M : 0);
         double J = 0.0;
         for (int i = sub; i < M; i += LPT) {
@@ -120,7 +91,7 @@ __global__ __launch_bounds__(64) void cost_grad_kernel(CostGradArgs a) {
         }
         J = topt_group_sum(J);
         if (live && a.cost && sub == 0) a.cost[b] = J;
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -162,17 +133,8 @@ struct TimeOptArgs {
 template <int R>
 __global__ __launch_bounds__(64) void time_opt_clamp_kernel(TimeOptArgs a) {
     constexpr int LPT = TOPT_LPT;
-    const int sub = threadIdx.x % LPT;
-    const long long n_lanes = (long long)a.n_traj * LPT;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    const long long n_round = (n_lanes + stride - 1) / stride * stride;
-    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < n_round; g += stride) {
-        const bool live = g < n_lanes;
-        const int b = live ? (int)(g / LPT) : 0;
-        int s0 = 0, M = 0;
-        if (live) {
-            if (a.uniform > 0) { M = a.uniform; s0 = b * M; } else { s0 = a.seg_offsets[b]; M = a.seg_offsets[b + 1] - s0; }
-        }
+    topt_for_each_group(a.n_traj, [&](bool live, int b, int sub) {
+        const auto [s0, M] = live ? poly_span(a.uniform, a.seg_offsets, b) : PolySpan{0, 0};
         double bad = 0.0;
         for (int i = sub; i < M; i += LPT) {
             const double T = a.times[s0 + i];
@@ -181,24 +143,15 @@ __global__ __launch_bounds__(64) void time_opt_clamp_kernel(TimeOptArgs a) {
         bad = topt_group_max(bad);
         if (bad == 0.0)
             for (int i = sub; i < M; i += LPT) a.times[s0 + i] = fmin(fmax(a.times[s0 + i], a.t_min), a.t_max);
-    }
+    });
 }
 
 template <int R, bool INIT, bool LIMITS = false>
 __global__ __launch_bounds__(64) void time_opt_step_kernel(TimeOptArgs a) {
     constexpr int NC = 2 * R, LPT = TOPT_LPT;
-    const int sub = threadIdx.x % LPT;
-    const long long n_lanes = (long long)a.n_traj * LPT;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    const long long n_round = (n_lanes + stride - 1) / stride * stride;
-    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < n_round; g += stride) {
-        const bool live = g < n_lanes;
-        const int b = live ? (int)(g / LPT) : 0;
-        int s0 = 0, M = 0;
-        if (live) {
-            if (a.uniform > 0) { M = a.uniform; s0 = b * M; } else { s0 = a.seg_offsets[b]; M = a.seg_offsets[b + 1] - s0; }
-            if (M < 0) M = 0;
-        }
+    topt_for_each_group(a.n_traj, [&](bool live, int b, int sub) {
+        const PolySpan sp = live ? poly_span(a.uniform, a.seg_offsets, b) : PolySpan{0, 0};
+        const int s0 = sp.s0, M = sp.M > 0 ? sp.M : 0;
         const size_t axs = (size_t)NC * M;
         const double* __restrict__ T_eval = INIT ? a.times : a.trial;
         const bool solved = live && M > 0 && a.status[b] == UAVQP_SOLVED;
@@ -250,7 +203,7 @@ __global__ __launch_bounds__(64) void time_opt_step_kernel(TimeOptArgs a) {
                 a.fbest[b] = f_best;
             }
         }
-        if (!a.propose) continue;   // (uniform over the grid: no shuffle follows)
+        if (!a.propose) return;   // (uniform over the grid: no shuffle follows)
 
         // the next trial from the best point
         double dmax = 0.0;
@@ -282,7 +235,7 @@ __global__ __launch_bounds__(64) void time_opt_step_kernel(TimeOptArgs a) {
             a.alpha[b] = alpha;
             a.need[b] = a.armijo * need;
         }
-    }
+    });
 }
 
 }  // namespace uavqp

@@ -20,6 +20,7 @@
 #include "uavqp_comm.h"
 
 #include "qp_core_kernels.h"
+#include "qp_samplers.h"
 
 
 #include "qp_twisted.h"

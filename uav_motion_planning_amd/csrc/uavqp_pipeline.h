@@ -198,15 +198,6 @@ struct RepairRowsArgs {
     int solvable_only;                     // pipeline: no rows for trajectories the rows solve cannot take (M < 2 or M > 63)
 };
 
-// the segment of sample s and the time in it: the rule of uavqp_eval_batch_device / the check kernels (past the end: the end point)
-__device__ __forceinline__ int repair_sample_segment(const double* T, int M, double t0, double dt, int s, double& t) {
-    t = t0 + s * dt;
-    int idx = 0;
-    while (idx < M && t > T[idx] + 1e-4) { t -= T[idx]; ++idx; }
-    if (idx == M) { --idx; t = T[idx]; }
-    return idx;
-}
-
 // clearance g(a) = min over ALL points of |E^-1 (o - a)| (the metric of the check kernels, frame f = b1, b2, b3) and its arg-min (lowest
 // index on a tie), across the wave; every lane returns the same pair
 __device__ __forceinline__ double repair_clearance(const RepairRowsArgs& a, const double* p, const double* f, double ir, double ih, int& arg) {
@@ -240,8 +231,7 @@ __global__ __launch_bounds__(64) void repair_rows_kernel(RepairRowsArgs a) {
     const double dt = a.tmax_bits ? __longlong_as_double((long long)*a.tmax_bits) / (double)(a.n_samples - 1) : a.dt;
     const double ir = 1.0 / a.robot_r, ih = 1.0 / a.robot_h;
     for (int b = blockIdx.x; b < a.n_traj; b += gridDim.x) {
-        int s0, M;
-        if (a.uniform > 0) { M = a.uniform; s0 = b * M; } else { s0 = a.seg_offsets[b]; M = a.seg_offsets[b + 1] - s0; }
+        const auto [s0, M] = poly_span(a.uniform, a.seg_offsets, b);
         const bool skip = M < 1 || a.n_samples < 1 || (a.solvable_only && (M < 2 || M > 63)) || (a.first_hit && a.first_hit[b] >= a.n_samples);
         int count = 0;
         if (!skip) {
@@ -252,8 +242,7 @@ __global__ __launch_bounds__(64) void repair_rows_kernel(RepairRowsArgs a) {
                 int first = -1, last = -1;
                 if (i < M) {
                     for (int s = 0; s < a.n_samples; ++s) {
-                        double t;
-                        const int idx = repair_sample_segment(T, M, a.t0, dt, s, t);
+                        const int idx = poly_segment(T, M, a.t0 + s * dt).idx;   // (the rule of the check kernels)
                         if (idx < i) continue;
                         if (idx > i) break;
                         const bool f = fl[s] != 0;
@@ -269,34 +258,16 @@ __global__ __launch_bounds__(64) void repair_rows_kernel(RepairRowsArgs a) {
                 const bool want = first >= 0;
                 double tau = 0.0, p[3] = {0.0, 0.0, 0.0}, fr[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
                 if (want) {
-                    double t;
-                    (void)repair_sample_segment(T, M, a.t0, dt, (first + last) >> 1, t);
+                    const double t = poly_segment(T, M, a.t0 + ((first + last) >> 1) * dt).t;
                     tau = fmin(fmax(t / T[i], 1.0 / 32.0), 31.0 / 32.0);
                     double acc[3];
 #pragma unroll
                     for (int ax = 0; ax < 3; ++ax) {
                         const double* ca = a.coeff + (size_t)3 * NC * s0 + ((size_t)ax * M + i) * NC;
-                        double pv = 0.0, av = 0.0;
-#pragma unroll
-                        for (int j = NC - 1; j >= 0; --j) pv = fma(pv, t, ca[j]);
-#pragma unroll
-                        for (int j = NC - 1; j >= 2; --j) av = fma(av, t, (double)(j * (j - 1)) * ca[j]);
-                        p[ax] = pv;
-                        acc[ax] = av;
+                        p[ax] = poly_deriv<NC, 0>(ca, t);
+                        acc[ax] = poly_deriv<NC, 2>(ca, t);
                     }
-                    // kino_astar.cpp:724-727, as in the check kernels
-                    const double n3 = sqrt(acc[0] * acc[0] + acc[1] * acc[1] + (acc[2] + 9.81) * (acc[2] + 9.81));
-                    const double b3[3] = {acc[0] / n3, acc[1] / n3, (acc[2] + 9.81) / n3};
-                    const double n2 = sqrt(b3[2] * b3[2] + b3[1] * b3[1]);
-                    const double b2[3] = {0.0, b3[2] / n2, -b3[1] / n2};
-                    const double c1[3] = {b2[1] * b3[2] - b2[2] * b3[1], b2[2] * b3[0] - b2[0] * b3[2], b2[0] * b3[1] - b2[1] * b3[0]};
-                    const double n1 = sqrt(c1[0] * c1[0] + c1[1] * c1[1] + c1[2] * c1[2]);
-#pragma unroll
-                    for (int ax = 0; ax < 3; ++ax) {
-                        fr[ax] = c1[ax] / n1;
-                        fr[3 + ax] = b2[ax];
-                        fr[6 + ax] = b3[ax];
-                    }
+                    poly_body_frame(acc, fr, fr + 3, fr + 6);   // (as in the check kernels)
                 }
                 unsigned long long todo = __ballot(want);
                 while (todo) {
