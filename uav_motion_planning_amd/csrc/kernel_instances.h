@@ -16,20 +16,21 @@
 #endif
 
 // ---- qp_twisted.h: solve_twisted_kernel<R, M, TILE, LPT, ONE>, the (R, M) pairs of find_twisted() x the four tile shapes
-#define UAVQP_TWISTED_SHAPES(R_, M_)                                                      \
-    UAVQP_INST __global__ void uavqp::solve_twisted_kernel<R_, M_, 4, 16>(uavqp::BatchArgs); \
-    UAVQP_INST __global__ void uavqp::solve_twisted_kernel<R_, M_, 8, 8>(uavqp::BatchArgs);  \
-    UAVQP_INST __global__ void uavqp::solve_twisted_kernel<R_, M_, 16, 2>(uavqp::BatchArgs); \
-    UAVQP_INST __global__ void uavqp::solve_twisted_kernel<R_, M_, 32, 2>(uavqp::BatchArgs);
+// (UAVQP_TWISTED_SIG: the one flat parameter list of the family, qp_twisted.h)
+#define UAVQP_TWISTED_SHAPES(R_, M_)                                                          \
+    UAVQP_INST __global__ void uavqp::solve_twisted_kernel<R_, M_, 4, 16>(UAVQP_TWISTED_SIG);     \
+    UAVQP_INST __global__ void uavqp::solve_twisted_kernel<R_, M_, 8, 8>(UAVQP_TWISTED_SIG);      \
+    UAVQP_INST __global__ void uavqp::solve_twisted_kernel<R_, M_, 16, 2>(UAVQP_TWISTED_SIG);     \
+    UAVQP_INST __global__ void uavqp::solve_twisted_kernel<R_, M_, 32, 2>(UAVQP_TWISTED_SIG);
 // (two translation units, k_twisted3.hip / k_twisted4.hip: 80 instantiations are the longest compile of the library)
 #define UAVQP_TWISTED_PAIRS4(X) X(4, 2) X(4, 3) X(4, 4) X(4, 5) X(4, 6) X(4, 7) X(4, 8) X(4, 9) X(4, 10) X(4, 12)
 #define UAVQP_TWISTED_PAIRS3(X) X(3, 2) X(3, 3) X(3, 4) X(3, 5) X(3, 6) X(3, 7) X(3, 8) X(3, 10) X(3, 12) X(3, 16)
 #define UAVQP_INSTANCES_TWISTED3 UAVQP_TWISTED_PAIRS3(UAVQP_TWISTED_SHAPES)
 #define UAVQP_INSTANCES_TWISTED4 UAVQP_TWISTED_PAIRS4(UAVQP_TWISTED_SHAPES)
 // the latency shapes once more for launches of exactly one whole tile per wave (ONE = true; k_twisted3_one.hip / k_twisted4_one.hip)
-#define UAVQP_TWISTED_SHAPES_ONE(R_, M_)                                                          \
-    UAVQP_INST __global__ void uavqp::solve_twisted_kernel<R_, M_, 4, 16, true>(uavqp::BatchArgs); \
-    UAVQP_INST __global__ void uavqp::solve_twisted_kernel<R_, M_, 8, 8, true>(uavqp::BatchArgs);
+#define UAVQP_TWISTED_SHAPES_ONE(R_, M_)                                                            \
+    UAVQP_INST __global__ void uavqp::solve_twisted_kernel<R_, M_, 4, 16, true>(UAVQP_TWISTED_SIG); \
+    UAVQP_INST __global__ void uavqp::solve_twisted_kernel<R_, M_, 8, 8, true>(UAVQP_TWISTED_SIG);
 #define UAVQP_INSTANCES_TWISTED3_ONE UAVQP_TWISTED_PAIRS3(UAVQP_TWISTED_SHAPES_ONE)
 #define UAVQP_INSTANCES_TWISTED4_ONE UAVQP_TWISTED_PAIRS4(UAVQP_TWISTED_SHAPES_ONE)
 

@@ -68,8 +68,34 @@ struct TwistedCfg {
 
 // ONE (latency shapes): the launch has exactly one WHOLE tile per wave (grid == n_tiles, n_traj % TILE == 0 -- the host checks both):
 // no shifted or guarded tile, no prefetch and no second input buffer, nothing that depends on the batch size; the tile loop makes one trip.
+//
+// Arguments: FLAT, one signature for every tile shape, the three arrays the LDS-DMA needs in front.  The translation units of this kernel
+// are compiled with the leading six arguments preloaded into SGPRs at wave launch (csrc/Makefile: TWISTED_FLAGS; a struct passed by
+// value is never preloaded): a wave issues its input loads without first fetching pointers from the kernarg segment, which is a fresh,
+// scalar-cache-cold address for every launch.  The host marshals them in one place: TwistedParams (uavqp.hip).
+#ifdef UAVQP_PHASE_TIMING
+#define UAVQP_TWISTED_STAMPS_PARAM , long long* stamps
+#define UAVQP_TWISTED_STAMPS_INIT , stamps
+#else
+#define UAVQP_TWISTED_STAMPS_PARAM
+#define UAVQP_TWISTED_STAMPS_INIT
+#endif
+#define UAVQP_TWISTED_SIG const double*, const double*, const double*, double*, int32_t*, int UAVQP_TWISTED_STAMPS_PARAM
+struct TwistedArgs {   // what the body reads: the kernel's own arguments under the names they had in BatchArgs
+    const double* waypoints;
+    const double* times;
+    const double* bc;
+    double* coeff;
+    int32_t* status;
+    int n_traj;
+#ifdef UAVQP_PHASE_TIMING
+    long long* stamps;
+#endif
+};
 template <int R, int M, int TILE, int LPT = 2, bool ONE = false>
-__global__ __launch_bounds__(64, 1) void solve_twisted_kernel(BatchArgs a) {
+__global__ __launch_bounds__(64, 1) void solve_twisted_kernel(const double* waypoints, const double* times, const double* bc, double* coeff,
+                                                              int32_t* status, int n_traj UAVQP_TWISTED_STAMPS_PARAM) {
+    const TwistedArgs a{waypoints, times, bc, coeff, status, n_traj UAVQP_TWISTED_STAMPS_INIT};
     using C = TwistedCfg<R, M, TILE, LPT>;
     constexpr int NAX = C::NAX;
     constexpr int ND = C::ND, NC = C::NC, NK = C::NK, mL = C::mL, mR = C::mR;

@@ -66,7 +66,32 @@ UAVQP_INSTANCES_ESDF
 
 namespace uavqp {
 // Specialised (R, M) instantiations of the register-resident kernel; everything else takes the generic one.
-typedef void (*twisted_fn)(BatchArgs);
+typedef void (*twisted_fn)(UAVQP_TWISTED_SIG);
+// The ONE place where a BatchArgs becomes the flat argument list of solve_twisted_kernel (qp_twisted.h), in the kernel's order: the eager
+// launch and the rebuilt graph node both pass `ptr` (the runtime copies the values at the call).
+struct TwistedParams {
+    const double* waypoints;
+    const double* times;
+    const double* bc;
+    double* coeff;
+    int32_t* status;
+    int n_traj;
+#ifdef UAVQP_PHASE_TIMING
+    long long* stamps;
+    void* ptr[7];
+#else
+    void* ptr[6];
+#endif
+    explicit TwistedParams(const BatchArgs& a) : waypoints(a.waypoints), times(a.times), bc(a.bc), coeff(a.coeff), status(a.status), n_traj(a.n_traj) {
+        ptr[0] = &waypoints; ptr[1] = &times; ptr[2] = &bc; ptr[3] = &coeff; ptr[4] = &status; ptr[5] = &n_traj;
+#ifdef UAVQP_PHASE_TIMING
+        stamps = a.stamps;
+        ptr[6] = &stamps;
+#endif
+    }
+    TwistedParams(const TwistedParams&) = delete;   // (ptr points into the object itself)
+    TwistedParams& operator=(const TwistedParams&) = delete;
+};
 template <int R, int M>
 static twisted_fn twisted_ptr(int tile, bool one) {
     // one: exactly one whole tile per wave -- the instantiation without the tile loop (latency shapes only)
@@ -165,7 +190,7 @@ struct CapturedLaunch {
     const void* fn = nullptr;
     dim3 grid, block;
     unsigned int lds_bytes = 0;
-    BatchArgs args{};  // (a barrier launch is re-added with the parameters of its captured node: not every such kernel takes a BatchArgs)
+    BatchArgs args{};  // fn != null: a solve_twisted_kernel launch, re-added through TwistedParams (a barrier launch is re-added with the parameters of its captured node)
 };
 
 struct uavqp_ctx {
@@ -471,8 +496,8 @@ extern "C" int uavqp_solve_batch_device(uavqp_ctx* ctx, int r, int n_traj, int u
         uavqp::twisted_fn fn = uavqp::find_twisted(r, uniform_segments, tile, one);
         if (fn) {
             a.ws = nullptr;
-            hipLaunchKernelGGL(fn, dim3(g), dim3(64), 0, ctx->stream, a);
-            UAVQP_HIP(hipGetLastError());
+            uavqp::TwistedParams tp(a);
+            UAVQP_HIP(hipLaunchKernel((const void*)fn, dim3(g), dim3(64), tp.ptr, 0, ctx->stream));
             if (ctx->capturing) capture_note(ctx, (const void*)fn, dim3(g), dim3(64), 0, &a, r);   // no workspace of the ctx: the one analysable launch
             return UAVQP_OK;
         }
@@ -745,7 +770,7 @@ static bool rebuild_captured(uavqp_ctx* ctx, hipGraph_t captured, int lanes, int
                 const CapturedLaunch& l = ctx->cap_launch[k];
                 BatchArgs a = l.args;
                 if (status_dead[k]) a.status = nullptr;        // a later solve overwrites every one of them before anything reads one
-                void* kernel_params[1] = {&a};
+                uavqp::TwistedParams tp(a);                    // (every analysable launch is a solve_twisted_kernel: capture_note)
                 hipKernelNodeParams p = params[k];             // a barrier: as captured
                 if (l.fn) {
                     p = hipKernelNodeParams{};
@@ -753,7 +778,7 @@ static bool rebuild_captured(uavqp_ctx* ctx, hipGraph_t captured, int lanes, int
                     p.gridDim = l.grid;
                     p.blockDim = l.block;
                     p.sharedMemBytes = l.lds_bytes;
-                    p.kernelParams = kernel_params;
+                    p.kernelParams = tp.ptr;
                 }
                 hipGraphNode_t node = nullptr;
                 ok = hipGraphAddKernelNode(&node, graph, prev ? &prev : nullptr, prev ? 1 : 0, &p) == hipSuccess;   // (the arguments are copied into the node)
