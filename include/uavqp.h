@@ -528,7 +528,8 @@ int uavqp_esdf_query_host(uavqp_ctx* ctx, uavqp_esdf* esdf, int n_pts, const dou
  * jump where a sample crosses a cell face of the trilinear query or a bound of the map (at d = d_safe the cube keeps them continuous).
  * UAVQP_ERR_INVALID_ARG: r not 3 / 4, a negative count, a wrong struct_size, samples_per_seg < 1, d_safe not finite or <= 0, weight not
  * finite or < 0, a NULL esdf or one never updated, NULL times / coeff, ragged without offsets.
- * Out of scope: an optimiser over waypoints or durations that uses the penalty, local-window updates, batches of maps, multi-GPU. */
+ * An optimiser over the waypoints that uses the penalty: uavqp_waypoint_optimize_device below.
+ * Out of scope: an optimiser over durations that uses the penalty, local-window updates, batches of maps, multi-GPU. */
 typedef struct uavqp_clearance_params {
     int32_t struct_size;
     int32_t samples_per_seg;   /* K: K + 1 sample points per segment (default 8) */
@@ -544,6 +545,95 @@ int uavqp_clearance_penalty_device(uavqp_ctx* ctx, int r, int n_traj, int unifor
 int uavqp_clearance_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
                                  const double* coeff, const int32_t* status, const uavqp_esdf* esdf, const uavqp_clearance_params* params,
                                  double* penalty, double* grad_coeff, double* grad_times, double* min_dist, int32_t* outside);
+
+/* EXACT gradient of the control cost with respect to the waypoints: the counterpart of uavqp_cost_time_gradient_device (no reference
+ * counterpart).  Per trajectory, from the coefficients a solve wrote, in WAYPOINT layout -- all M_b + 1 knots, both ends included:
+ *   grad[seg_offsets[b] + b + k][axis] = dJ_b / dp_k = 2 (-1)^(r-1) (2r-1)! (c_{k-1,2r-1} - c_{k,2r-1})
+ * c_{i,2r-1} the leading coefficient of segment i on that axis; at k = 0 only the second term, at k = M only the first.  r = 3:
+ * 240 (c_{k-1,5} - c_{k,5}); r = 4: -10080 (c_{k-1,7} - c_{k,7}).  (r integrations by parts of the variation of J; the terms in the knot
+ * derivatives vanish at the minimiser -- free and stationary at an interior knot, fixed at an end --, p^(2r) = 0 inside a segment and
+ * p^(2r-1) is constant along it.)  The end rows are the derivatives with respect to the end POSITIONS at fixed boundary derivatives.
+ * The gradient is that of the OPTIMAL cost: meaningful for coefficients of uavqp_solve_batch_* (corridor and general-rows solves are out
+ * of scope).  It equals uavqp_solve_backward_device(g = 2 P c).grad_waypoints up to rounding, without a factorisation.  The durations do
+ * not enter, so there is no d_times argument.
+ *   d_status  [n_traj] status of the solve, or NULL (every trajectory counts as solved).  A trajectory whose status is not UAVQP_SOLVED, or
+ *             with M < 1, gets zeros.
+ *   d_grad    [sum_b (M_b + 1)][3]; NULL: UAVQP_OK, nothing done.  Every element is written exactly once.
+ * UAVQP_ERR_INVALID_ARG: r not 3 / 4, a negative count, NULL coeff, ragged without offsets.  One launch, asynchronous on the ctx stream, no
+ * allocation, no read-back. */
+int uavqp_cost_waypoint_gradient_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
+                                        const double* d_coeff, const int32_t* d_status, double* d_grad);
+/* The same from HOST pointers (H2D copy, run, D2H copy, synchronous). */
+int uavqp_cost_waypoint_gradient_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets,
+                                      const double* coeff, const int32_t* status, double* grad);
+
+/* Optimisation of the INTERIOR WAYPOINTS against a distance field: a gradient-based planner back-end in the style of GCOPTER / EGO-Planner
+ * (no reference counterpart: the reference never moves a searched waypoint).  Per trajectory, with the durations, the boundary derivatives
+ * and both end waypoints fixed,
+ *       minimise over p_1 .. p_{M-1}   f(p) = smooth_weight * J(p) + Phi(c*(p), T)
+ *       subject to                     |p_k[axis] - p_k^start[axis]| <= max_move      for every interior knot and axis
+ * J the control cost at the minimiser c*(p) of the equality-constrained QP, Phi exactly the penalty of uavqp_clearance_penalty_device
+ * against `esdf`.  c*(p) stays the minimiser of J alone (the QP does not see the penalty), so
+ *       df/dp_k = smooth_weight * uavqp_cost_waypoint_gradient_device_k + uavqp_solve_backward_device(g = dPhi/dc).grad_waypoints_k.
+ * Method (that of uavqp_time_optimize_device): projected gradient descent with Armijo backtracking along the projection arc.  Direction
+ * d_k = (df/dp_k) / s_k with the per-knot scale s_k = T_{k-1}^-(2r-1) + T_k^-(2r-1) > 0 (J scales like T^-(2r-1): one step length then
+ * serves knots between short and between long segments; -d is still a descent direction), a component zero where the box blocks it.
+ * The first alpha makes the largest |alpha d| equal to initial_step metres.  A trial p - alpha d, clamped into the box, is accepted iff its
+ * solve ends UAVQP_SOLVED and f_trial <= f - armijo_c * sum_k (df/dp_k) . (p_k - p_trial_k); accepted: alpha *= grow, rejected:
+ * alpha *= shrink.  f never increases.  A trajectory without a direction at the start (no interior knot, or a gradient that is zero in
+ * every component the box leaves free) proposes nothing and accepts nothing.
+ * Host-side C++ sequencing of
+ *       anchor copy, solve, penalty, backward, step, max_iters x { solve at the trial waypoints, penalty, backward, step }, solve, penalty
+ * (the last penalty only for d_min_dist_out / d_outside_out): every accept / reject is taken per trajectory ON THE DEVICE, nothing is read
+ * back, the number of launches depends on max_iters alone.  The additions are in a fixed order: the same bytes run to run and for any
+ * grid.  Asynchronous on the ctx stream (a first call of a given size allocates the workspace).
+ *   d_waypoints      [sum_b (M_b + 1)][3] IN: the start, OUT: the accepted waypoints.  The two end knots of every trajectory come back byte
+ *                    for byte; so does every knot of a trajectory that is not UAVQP_SOLVED at the start (e.g. a non-positive duration:
+ *                    UAVQP_INVALID_INPUT) -- it keeps its status and takes no part.
+ *   d_times, d_bc    as for uavqp_solve_batch_device; not changed
+ *   esdf, clearance  validated as for uavqp_clearance_penalty_device
+ *   d_coeff_out      the solve AT the waypoints handed back: bit for bit what uavqp_solve_batch_device writes for them
+ *   d_status_out     [n_traj] status of that solve (may be NULL)
+ *   d_objective_out  [n_traj][2]: f at the start, f at the result (NaN, NaN for a trajectory that took no part)
+ *   d_accepted_out   [n_traj] int32 accepted trials (may be NULL)
+ *   d_min_dist_out   [n_traj], d_outside_out [n_traj] int32: the penalty's two diagnostics at the result (each may be NULL)
+ *   params           uavqp_default_waypoint_opt_params fills the defaults; UAVQP_ERR_INVALID_ARG for a wrong struct_size, max_iters < 0,
+ *                    smooth_weight < 0, max_move <= 0 (INFINITY is allowed: no box), initial_step <= 0, armijo_c outside (0, 1), shrink
+ *                    outside (0, 1), grow < 1 or any other non-finite value.  max_iters = 0: the plain solve, both objective columns equal,
+ *                    the waypoints untouched.
+ * UAVQP_ERR_INVALID_ARG also: r not 3 / 4, a negative count, a NULL esdf or one never updated, invalid clearance parameters, a NULL
+ * waypoints / times / bc / coeff_out / objective_out, ragged without offsets or with max_segments < 1, uniform with total_segments !=
+ * uniform_segments * n_traj.
+ * WHAT THE RESULT IS.  A sample outside the map contributes nothing to Phi, so f JUMPS DOWN where a sample leaves the map: max_move is the
+ * caller's handle to keep the trajectories inside (check d_outside_out).  The penalty is piecewise smooth (its gradient jumps across the
+ * cell faces of the trilinear query), so the method converges to a point where no descent step of the tried lengths is left, not to a
+ * stationary point in the classical sense.  The result is a LOCAL minimum of a SOFT penalty: at finite weight a trajectory may end closer
+ * than d_safe, and a start on the symmetric saddle of an obstacle (gradient zero) does not move.  uavqp_ellipsoid_check_* afterwards
+ * remains the hard test.
+ * Out of scope: corridor and general-rows solves, joint optimisation of the durations (alternate with uavqp_time_optimize_device),
+ * multi-GPU (shard the batch as for the solve: trajectories are independent). */
+typedef struct uavqp_waypoint_opt_params {
+    int32_t struct_size;
+    int32_t max_iters;      /* trials per trajectory (default 64) */
+    double smooth_weight;   /* weight of the control cost J, >= 0 (default 1) */
+    double max_move;        /* half edge of the box around every start waypoint, m, > 0, may be INFINITY (default 2) */
+    double initial_step;    /* largest move of a waypoint component in the first trial, m (default 0.1) */
+    double armijo_c;        /* sufficient-decrease constant (default 1e-4) */
+    double shrink;          /* step factor after a rejected trial (default 0.5) */
+    double grow;            /* ... after an accepted one (default 2) */
+} uavqp_waypoint_opt_params;
+void uavqp_default_waypoint_opt_params(uavqp_waypoint_opt_params* out);   /* callable without a device */
+int uavqp_waypoint_optimize_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                                   const int32_t* d_seg_offsets, double* d_waypoints, const double* d_times, const double* d_bc,
+                                   const uavqp_esdf* esdf, const uavqp_clearance_params* clearance, const uavqp_waypoint_opt_params* params,
+                                   double* d_coeff_out, int32_t* d_status_out, double* d_objective_out, int32_t* d_accepted_out,
+                                   double* d_min_dist_out, int32_t* d_outside_out);
+/* The same from HOST pointers (H2D copy, run, D2H copy, synchronous; waypoints is updated in place; the map stays a device object; the
+ * coefficients of a trajectory that is not UAVQP_SOLVED come back as they do from uavqp_solve_batch_host). */
+int uavqp_waypoint_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                                 double* waypoints, const double* times, const double* bc, const uavqp_esdf* esdf,
+                                 const uavqp_clearance_params* clearance, const uavqp_waypoint_opt_params* params, double* coeff_out,
+                                 int32_t* status_out, double* objective_out, int32_t* accepted_out, double* min_dist_out, int32_t* outside_out);
 
 /* Batched evaluation of solved trajectories on a uniform time grid.
  * Replaces, for a whole batch, PolyTraj::evaluatePos / evaluateVel / evaluateAcc

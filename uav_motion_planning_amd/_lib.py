@@ -68,6 +68,11 @@ SYMBOLS = (
     "uavqp_default_clearance_params",
     "uavqp_clearance_penalty_device",
     "uavqp_clearance_penalty_host",
+    "uavqp_cost_waypoint_gradient_device",
+    "uavqp_cost_waypoint_gradient_host",
+    "uavqp_default_waypoint_opt_params",
+    "uavqp_waypoint_optimize_device",
+    "uavqp_waypoint_optimize_host",
     "uavqp_eval_batch_device",
     "uavqp_traj_length_device",
     "uavqp_ellipsoid_check_device",
@@ -143,6 +148,12 @@ class LimitParams(ctypes.Structure):
 class ClearanceParams(ctypes.Structure):
     """uavqp_clearance_params of include/uavqp.h."""
     _fields_ = [("struct_size", ctypes.c_int32), ("samples_per_seg", ctypes.c_int32), ("d_safe", ctypes.c_double), ("weight", ctypes.c_double)]
+
+
+class WaypointOptParams(ctypes.Structure):
+    """uavqp_waypoint_opt_params of include/uavqp.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("max_iters", ctypes.c_int32), ("smooth_weight", ctypes.c_double), ("max_move", ctypes.c_double),
+                ("initial_step", ctypes.c_double), ("armijo_c", ctypes.c_double), ("shrink", ctypes.c_double), ("grow", ctypes.c_double)]
 
 
 def build(force=False):
@@ -224,6 +235,14 @@ def lib():
     L.uavqp_default_clearance_params.restype = None
     L.uavqp_clearance_penalty_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, vp, ctypes.POINTER(ClearanceParams), dp, dp, dp, dp, ip]
     L.uavqp_clearance_penalty_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, vp, ctypes.POINTER(ClearanceParams), dp, dp, dp, dp, ip]
+    L.uavqp_cost_waypoint_gradient_device.argtypes = [vp, i32, i32, i32, ip, dp, ip, dp]
+    L.uavqp_cost_waypoint_gradient_host.argtypes = [vp, i32, i32, i32, ip, dp, ip, dp]
+    L.uavqp_default_waypoint_opt_params.argtypes = [ctypes.POINTER(WaypointOptParams)]
+    L.uavqp_default_waypoint_opt_params.restype = None
+    L.uavqp_waypoint_optimize_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(ClearanceParams),
+                                                 ctypes.POINTER(WaypointOptParams), dp, ip, dp, ip, dp, ip]
+    L.uavqp_waypoint_optimize_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(ClearanceParams),
+                                               ctypes.POINTER(WaypointOptParams), dp, ip, dp, ip, dp, ip]
     L.uavqp_eval_batch_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, i32, dp]
     L.uavqp_traj_length_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ctypes.c_double, dp, dp, ip]
     L.uavqp_ellipsoid_check_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, dp, i32,

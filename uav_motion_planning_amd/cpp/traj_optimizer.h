@@ -213,6 +213,59 @@ class TrajOptimizer {
         }
         return phi;
     }
+    // Optimisation of the interior waypoints against a distance field (include/uavqp.h uavqp_waypoint_optimize_host; the reference's
+    // equality rows only: false when a corridor or rows are set): minimises, per trajectory, smooth_weight * cost + clearance penalty over
+    // the interior waypoints inside a box of half edge max_move around the start.  map: a uavqp::EsdfMap of cpp/esdf_map.h built on
+    // context() and updated.  On return waypoints() = the optimised waypoints (end knots untouched), getPolyCoeff() = the solve at them,
+    // objective() = [n_traj][2] f at the start / at the result, acceptedTrials() per trajectory, minDist() / outsideSamples() the penalty's
+    // diagnostics at the result.  params: null = uavqp_default_waypoint_opt_params; smooth_weight >= 0 overrides its weight.  The penalty is
+    // soft and the result a local minimum: uavqp_ellipsoid_check_* afterwards remains the hard test.
+    template <class Map>
+    bool optimizeWaypoints(const Map& map, const uavqp_clearance_params& clearance, double smooth_weight = -1.0,
+                           const uavqp_waypoint_opt_params* params = nullptr) {
+        if (n_traj_ <= 0 || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_])) return false;
+        if (!lo_.empty() || rows_k_ > 0) {
+            std::cout << "solver solve failed! (optimizeWaypoints: corridor and general-rows problems are out of scope)" << std::endl;
+            return false;
+        }
+        if (!ensureContext()) return false;
+        if (bc_.empty()) bc_.assign(static_cast<size_t>(n_traj_) * 2 * (order_ - 1) * 3, 0.0);
+        uavqp_waypoint_opt_params pp;
+        if (params) pp = *params; else uavqp_default_waypoint_opt_params(&pp);
+        if (smooth_weight >= 0.0) pp.smooth_weight = smooth_weight;
+        coef_.assign(static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_], 0.0);
+        status_.assign(n_traj_, 0);
+        objective_.assign(static_cast<size_t>(2) * n_traj_, 0.0);
+        accepted_.assign(n_traj_, 0);
+        min_dist_.assign(n_traj_, 0.0);
+        outside_.assign(n_traj_, 0);
+        const int rc = uavqp_waypoint_optimize_host(ctx_, order_, n_traj_, 0, 0, seg_offsets_.data(), wp_.data(), T_.data(), bc_.data(), map.handle(),
+                                                    &clearance, &pp, coef_.data(), status_.data(), objective_.data(), accepted_.data(),
+                                                    min_dist_.data(), outside_.data());
+        if (rc != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            return false;
+        }
+        for (int32_t s : status_) if (s != UAVQP_SOLVED) return false;
+        return true;
+    }
+    const std::vector<double>& waypoints() const { return wp_; }
+    const std::vector<double>& minDist() const { return min_dist_; }
+    const std::vector<int32_t>& outsideSamples() const { return outside_; }
+    // Gradient of the control cost of the stored coefficients in the waypoints, [sum (M + 1)][3], both ends of every trajectory included
+    // (after solve() of an equality-constrained problem; uavqp_cost_waypoint_gradient_host).  Empty on failure.
+    std::vector<double> getCostWaypointGradient() {
+        std::vector<double> grad;
+        if (n_traj_ <= 0 || !ctx_ || !lo_.empty() || rows_k_ > 0 ||
+            coef_.size() != static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_] || status_.size() != static_cast<size_t>(n_traj_))
+            return grad;
+        grad.assign(wp_.size(), 0.0);
+        if (uavqp_cost_waypoint_gradient_host(ctx_, order_, n_traj_, 0, seg_offsets_.data(), coef_.data(), status_.data(), grad.data()) != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            grad.clear();
+        }
+        return grad;
+    }
     // The context this optimiser solves on (created on first use; nullptr without a device): what a uavqp::EsdfMap is built on.
     uavqp_ctx* context() { return ensureContext() ? ctx_ : nullptr; }
     const std::vector<double>& objective() const { return objective_; }
@@ -440,7 +493,8 @@ class TrajOptimizer {
     std::vector<double> wp_, T_, bc_, coef_, lo_, hi_, pipe_lo_, pipe_hi_, row_tau_, row_lo_, row_hi_;
     std::vector<int32_t> row_deriv_, first_hit_, repair_deriv_;
     std::vector<double> repair_tau_, repair_lo_, repair_hi_;
-    std::vector<double> objective_, peak_;
+    std::vector<double> objective_, peak_, min_dist_;
+    std::vector<int32_t> outside_;
     std::vector<int32_t> accepted_;
     int rows_k_ = 0;
     uavqp_pipeline_result pipe_result_{};

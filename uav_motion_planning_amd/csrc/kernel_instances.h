@@ -114,3 +114,10 @@
     UAVQP_INST __global__ void uavqp::esdf_axis_kernel<true>(uavqp::EsdfArgs, int, int, int, int, int);  \
     UAVQP_INST __global__ void uavqp::clearance_penalty_kernel<3>(uavqp::ClearanceArgs);              \
     UAVQP_INST __global__ void uavqp::clearance_penalty_kernel<4>(uavqp::ClearanceArgs);
+
+// ---- qp_waypoint_opt.h: waypoint gradient of the control cost, the steps of the waypoint optimiser
+#define UAVQP_WPOPT_R(R_)                                                                          \
+    UAVQP_INST __global__ void uavqp::cost_waypoint_grad_kernel<R_>(uavqp::WaypointGradArgs);         \
+    UAVQP_INST __global__ void uavqp::waypoint_opt_step_kernel<R_, true>(uavqp::WaypointOptArgs);     \
+    UAVQP_INST __global__ void uavqp::waypoint_opt_step_kernel<R_, false>(uavqp::WaypointOptArgs);
+#define UAVQP_INSTANCES_WPOPT UAVQP_WPOPT_R(3) UAVQP_WPOPT_R(4)

@@ -35,6 +35,7 @@
 #include "qp_adjoint.h"
 #include "qp_limits.h"
 #include "qp_esdf.h"
+#include "qp_waypoint_opt.h"
 // Measured-slower alternatives kept as bit-identical cross-checks: `make experiments` (-DUAVQP_EXPERIMENTS) only
 #ifdef UAVQP_EXPERIMENTS
 #include "cloud_grid2d.h"
@@ -62,6 +63,7 @@ UAVQP_INSTANCES_TIMEOPT
 UAVQP_INSTANCES_ADJOINT
 UAVQP_INSTANCES_LIMITS
 UAVQP_INSTANCES_ESDF
+UAVQP_INSTANCES_WPOPT
 #endif
 
 namespace uavqp {
@@ -1932,6 +1934,11 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
 // Signed distance field of an occupancy grid and the clearance penalty
 // ===================================================================================================
 #include "uavqp_esdf.h"
+
+// ===================================================================================================
+// Waypoint gradient of the control cost and the waypoint optimiser against the distance field
+// ===================================================================================================
+#include "uavqp_waypoint_opt.h"
 
 // ===================================================================================================
 // N3: quadrotor_msgs/PolynomialTrajectory packer (host only)

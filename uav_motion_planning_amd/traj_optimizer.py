@@ -234,6 +234,80 @@ class Context:
         _lib.check(rc, "uavqp_clearance_penalty_host")
         return penalty, g_c, g_t, min_dist, outside
 
+    @staticmethod
+    def _waypoint_opt_params(params):
+        pp = _lib.WaypointOptParams()
+        _lib.lib().uavqp_default_waypoint_opt_params(ctypes.byref(pp))
+        for k, v in params.items():
+            if not hasattr(pp, k) or k == "struct_size":
+                raise ValueError(f"unknown uavqp_waypoint_opt_params field {k!r}")
+            setattr(pp, k, v)
+        return pp
+
+    def cost_waypoint_gradient_device(self, r, n_traj, uniform_segments, seg_offsets, coeff, grad, status=None):
+        """uavqp_cost_waypoint_gradient_device: grad [sum (M + 1)][3] = d cost / d p_k at the minimiser of the equality-constrained solve,
+        all knots of every trajectory, both ends included (device buffers).  status (the solve's, optional): trajectories that are not
+        SOLVED get zeros.  Asynchronous."""
+        rc = _lib.lib().uavqp_cost_waypoint_gradient_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(coeff), _ptr(status),
+                                                            _ptr(grad))
+        _lib.check(rc, "uavqp_cost_waypoint_gradient_device")
+
+    def cost_waypoint_gradient_host(self, r, seg_offsets, coeff, uniform_segments=0, status=None):
+        """numpy in / numpy out (synchronous).  Returns grad [sum (M + 1)][3]."""
+        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        if uniform_segments > 0:
+            so, total = None, coeff.size // (3 * 2 * r)
+            n_traj = total // uniform_segments
+        else:
+            so = np.ascontiguousarray(seg_offsets, dtype=np.int32)
+            n_traj, total = so.size - 1, int(so[-1])
+        assert coeff.size == 3 * 2 * r * total
+        grad = np.zeros((total + n_traj, 3), dtype=np.float64)
+        rc = _lib.lib().uavqp_cost_waypoint_gradient_host(self._h, r, n_traj, uniform_segments, _ptr(so), _ptr(coeff), _ptr(status), _ptr(grad))
+        _lib.check(rc, "uavqp_cost_waypoint_gradient_host")
+        return grad
+
+    def waypoint_optimize_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc, esdf,
+                                 coeff_out, status_out, objective_out, accepted_out=None, min_dist_out=None, outside_out=None, clearance=None,
+                                 **params):
+        """uavqp_waypoint_optimize_device on device buffers: `waypoints` holds the start and receives the optimised interior waypoints
+        (end knots untouched), coeff_out the solve at them, objective_out [n_traj][2] f = smooth_weight * cost + clearance penalty against
+        `esdf` (an esdf.EsdfMap, updated) at the start and at the result, min_dist_out / outside_out the penalty's diagnostics at the
+        result.  clearance: dict of uavqp_clearance_params fields; params: fields of uavqp_waypoint_opt_params that differ from the
+        defaults.  The penalty is soft and the result a local minimum (include/uavqp.h).  Asynchronous."""
+        pp = self._waypoint_opt_params(params)
+        cp = self._clearance_params(clearance or {})
+        rc = _lib.lib().uavqp_waypoint_optimize_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), _ptr(seg_offsets),
+                                                       _ptr(waypoints), _ptr(times), _ptr(bc), getattr(esdf, "handle", esdf), ctypes.byref(cp),
+                                                       ctypes.byref(pp), _ptr(coeff_out), _ptr(status_out), _ptr(objective_out),
+                                                       _ptr(accepted_out), _ptr(min_dist_out), _ptr(outside_out))
+        _lib.check(rc, "uavqp_waypoint_optimize_device")
+
+    def waypoint_optimize_host(self, r, seg_offsets, waypoints, times, bc, esdf, uniform_segments=0, clearance=None, **params):
+        """numpy in / numpy out (synchronous; the map stays on the device).  Returns (waypoints [sum (M + 1)][3], coeff_flat, status,
+        objective [n_traj][2], accepted, min_dist [n_traj], outside [n_traj] int32)."""
+        waypoints = np.array(waypoints, dtype=np.float64).reshape(-1, 3)   # a copy: the call updates it in place
+        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
+        bc = np.ascontiguousarray(bc, dtype=np.float64)
+        so, n_traj, total, mmax = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total
+        assert waypoints.size == 3 * (total + n_traj), "waypoints must hold sum(M_b + 1) xyz rows"
+        assert bc.size == n_traj * 2 * (r - 1) * 3
+        pp = self._waypoint_opt_params(params)
+        cp = self._clearance_params(clearance or {})
+        coeff = np.zeros(3 * 2 * r * total, dtype=np.float64)
+        status = np.zeros(n_traj, dtype=np.int32)
+        objective = np.zeros((n_traj, 2), dtype=np.float64)
+        accepted = np.zeros(n_traj, dtype=np.int32)
+        min_dist = np.zeros(n_traj, dtype=np.float64)
+        outside = np.zeros(n_traj, dtype=np.int32)
+        rc = _lib.lib().uavqp_waypoint_optimize_host(self._h, r, n_traj, uniform_segments, max(mmax, 1), _ptr(so), _ptr(waypoints), _ptr(times),
+                                                     _ptr(bc), getattr(esdf, "handle", esdf), ctypes.byref(cp), ctypes.byref(pp), _ptr(coeff),
+                                                     _ptr(status), _ptr(objective), _ptr(accepted), _ptr(min_dist), _ptr(outside))
+        _lib.check(rc, "uavqp_waypoint_optimize_host")
+        return waypoints, coeff, status, objective, accepted, min_dist, outside
+
     def time_optimize_limits_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc,
                                     coeff_out, status_out, objective_out, accepted_out=None, peak_out=None, limits=None, **params):
         """uavqp_time_optimize_limits_device on device buffers: time_optimize_device with the limit penalty inside the objective
@@ -601,6 +675,11 @@ class TrajOptimizer:
     getLimitPenalty(**limits)        [n_traj] limit penalty of the stored coefficients at the stored durations
     getClearancePenalty(esdf, ...)   [n_traj] clearance penalty of the stored coefficients against an esdf.EsdfMap built on context()
                                      (also spelled get_clearance_penalty)
+    optimizeWaypoints(esdf, ...)     equality-constrained problems only: moves the interior waypoints to minimise smooth_weight * cost +
+                                     clearance penalty against an esdf.EsdfMap built on context() (uavqp_waypoint_optimize_host); stores
+                                     the optimised waypoints (getWaypoints) and the coefficients at them; .objective as for optimizeTime,
+                                     .min_dist / .outside [n_traj] the penalty's diagnostics at the result
+    getCostWaypointGradient()        [sum (M_b + 1)][3] gradient of getCost() in the waypoints, both ends of every trajectory included
     backward(grad_coeff)             equality-constrained problems only, after solve(): (grad_times, grad_waypoints, grad_bc) of a loss
                                      with d loss / d getPolyCoeff() = grad_coeff, through the solve
     getCost()                        [n_traj] control cost c' P c of the stored coefficients at the stored durations
@@ -620,6 +699,8 @@ class TrajOptimizer:
         self.iterations = np.zeros(0, dtype=np.int32)
         self.objective = np.zeros((0, 2))
         self.peak = np.zeros((0, 2))
+        self.min_dist = np.zeros(0)
+        self.outside = np.zeros(0, dtype=np.int32)
 
     def setWaypoints(self, xyz, wp_offsets=None, n_waypoints=None):
         self._wp = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
@@ -704,6 +785,39 @@ class TrajOptimizer:
         self._T, self._coef, self.status, self.objective, self.iterations = self._ctx.time_optimize_host(
             self._r, self._so, self._wp, self._T, bc, **params)
         return bool(np.all(self.status == _lib.UAVQP_SOLVED))
+
+    def optimizeWaypoints(self, esdf, smooth_weight=None, clearance=None, **params):
+        """Optimises the stored interior waypoints against the distance field `esdf` (an esdf.EsdfMap on this optimiser's context -- see
+        context() --, updated); the reference's equality rows only: a corridor or rows set raises ValueError.  True iff every trajectory
+        is solved at the optimised waypoints; getPolyCoeff() is the solve at getWaypoints().  clearance: dict of uavqp_clearance_params
+        fields; params: fields of uavqp_waypoint_opt_params that differ from the defaults.  The penalty is soft: .min_dist may end below
+        d_safe, and .outside counts the samples that left the map (include/uavqp.h)."""
+        if self._lo is not None or self._rows is not None:
+            raise ValueError("optimizeWaypoints: corridor and general-rows problems are out of scope (include/uavqp.h)")
+        if self._wp is None or self._T is None:
+            return False
+        n_traj = self._so.size - 1
+        if self._T.size != int(self._so[-1]):
+            return False
+        bc = self._bc if self._bc is not None else np.zeros((n_traj, 2, self._r - 1, 3))
+        ctx = self.context()
+        if smooth_weight is not None:
+            params["smooth_weight"] = float(smooth_weight)
+        self._wp, self._coef, self.status, self.objective, self.iterations, self.min_dist, self.outside = ctx.waypoint_optimize_host(
+            self._r, self._so, self._wp, self._T, bc, esdf, clearance=clearance, **params)
+        return bool(np.all(self.status == _lib.UAVQP_SOLVED))
+
+    def getWaypoints(self):
+        return self._wp.copy()
+
+    def getCostWaypointGradient(self):
+        """[sum (M_b + 1)][3] gradient of the control cost of the stored coefficients in the waypoints, all knots of every trajectory
+        (after solve() of an equality-constrained problem, optimizeTime() or optimizeWaypoints()).  Trajectories that did not solve carry zeros."""
+        if self._lo is not None or self._rows is not None:
+            raise ValueError("getCostWaypointGradient: corridor and general-rows problems are out of scope (include/uavqp.h)")
+        if self._ctx is None or self._coef.size != 3 * 2 * self._r * int(self._so[-1]) or self.status.size != self._so.size - 1:
+            raise _lib.UavqpError("getCostWaypointGradient: no solved coefficients (call solve() first)")
+        return self._ctx.cost_waypoint_gradient_host(self._r, self._so, self._coef, status=self.status)
 
     def getLimitPenalty(self, **limits):
         """[n_traj] limit penalty of the stored coefficients at the stored durations (after solve() or optimizeTime());
