@@ -528,8 +528,9 @@ int uavqp_esdf_query_host(uavqp_ctx* ctx, uavqp_esdf* esdf, int n_pts, const dou
  * jump where a sample crosses a cell face of the trilinear query or a bound of the map (at d = d_safe the cube keeps them continuous).
  * UAVQP_ERR_INVALID_ARG: r not 3 / 4, a negative count, a wrong struct_size, samples_per_seg < 1, d_safe not finite or <= 0, weight not
  * finite or < 0, a NULL esdf or one never updated, NULL times / coeff, ragged without offsets.
- * An optimiser over the waypoints that uses the penalty: uavqp_waypoint_optimize_device below.
- * Out of scope: an optimiser over durations that uses the penalty, local-window updates, batches of maps, multi-GPU. */
+ * An optimiser over the waypoints that uses the penalty: uavqp_waypoint_optimize_device below; over waypoints AND durations, together with
+ * the limit penalty: uavqp_spacetime_optimize_device.
+ * Out of scope: local-window updates, batches of maps, multi-GPU. */
 typedef struct uavqp_clearance_params {
     int32_t struct_size;
     int32_t samples_per_seg;   /* K: K + 1 sample points per segment (default 8) */
@@ -610,8 +611,8 @@ int uavqp_cost_waypoint_gradient_host(uavqp_ctx* ctx, int r, int n_traj, int uni
  * stationary point in the classical sense.  The result is a LOCAL minimum of a SOFT penalty: at finite weight a trajectory may end closer
  * than d_safe, and a start on the symmetric saddle of an obstacle (gradient zero) does not move.  uavqp_ellipsoid_check_* afterwards
  * remains the hard test.
- * Out of scope: corridor and general-rows solves, joint optimisation of the durations (alternate with uavqp_time_optimize_device),
- * multi-GPU (shard the batch as for the solve: trajectories are independent). */
+ * Joint optimisation of the durations: uavqp_spacetime_optimize_device below.
+ * Out of scope: corridor and general-rows solves, multi-GPU (shard the batch as for the solve: trajectories are independent). */
 typedef struct uavqp_waypoint_opt_params {
     int32_t struct_size;
     int32_t max_iters;      /* trials per trajectory (default 64) */
@@ -634,6 +635,118 @@ int uavqp_waypoint_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_
                                  double* waypoints, const double* times, const double* bc, const uavqp_esdf* esdf,
                                  const uavqp_clearance_params* clearance, const uavqp_waypoint_opt_params* params, double* coeff_out,
                                  int32_t* status_out, double* objective_out, int32_t* accepted_out, double* min_dist_out, int32_t* outside_out);
+
+/* Fused flight penalty: the limit penalty and the clearance penalty of solved trajectories in ONE launch (the hot path of
+ * uavqp_spacetime_optimize_device below).  Per trajectory
+ *       Phi = Phi_lim + Phi_clr
+ * Phi_lim exactly the formula of uavqp_limit_penalty_device with `limits`, Phi_clr exactly that of uavqp_clearance_penalty_device with
+ * `clearance` against `esdf`; each part keeps its own samples_per_seg.
+ *   d_penalty     [n_traj] Phi
+ *   d_grad_coeff  layout of coeff ([axis][segment][2r] per trajectory): dPhi/dc at FIXED durations, the sum of both parts
+ *   d_grad_times  [sum_b M_b]: the EXPLICIT dPhi/dT_i at FIXED coefficients, the sum of both parts
+ *   d_peak        [n_traj][2] as uavqp_limit_penalty_device writes it
+ *   d_min_dist    [n_traj], d_outside [n_traj] int32 as uavqp_clearance_penalty_device writes them
+ * Each output may be NULL (all NULL: UAVQP_OK, nothing done).  The TOTAL gradients of Phi in the durations and in the waypoints come out of
+ * one uavqp_solve_backward_device(g = d_grad_coeff): d_grad_times + its grad_times, and its grad_waypoints.
+ * A lane loads the coefficients and the duration of a segment once and runs both sets of samples over them.  With weight_v = weight_a = 0
+ * the limit part contributes nothing, with clearance weight 0 the clearance part contributes nothing (the diagnostics of a part are
+ * still those of its own entry).  d_status, unsolved trajectories and M < 1 as for the two entries: zeros, min_dist = max_dist.
+ * Every output element is written exactly once, zeros included.  The additions are in a fixed order: the same bytes run to run and for
+ * any grid.  One launch, asynchronous on the ctx stream, no allocation, no read-back.  Piecewise smooth, as the clearance penalty is.
+ * UAVQP_ERR_INVALID_ARG: whatever either of the two entries refuses. */
+int uavqp_flight_penalty_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
+                                const double* d_coeff, const int32_t* d_status, const uavqp_esdf* esdf, const uavqp_limit_params* limits,
+                                const uavqp_clearance_params* clearance, double* d_penalty, double* d_grad_coeff, double* d_grad_times,
+                                double* d_peak, double* d_min_dist, int32_t* d_outside);
+/* The same from HOST pointers (H2D copy, run, D2H copy, synchronous); esdf stays a device object. */
+int uavqp_flight_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
+                              const double* coeff, const int32_t* status, const uavqp_esdf* esdf, const uavqp_limit_params* limits,
+                              const uavqp_clearance_params* clearance, double* penalty, double* grad_coeff, double* grad_times, double* peak,
+                              double* min_dist, int32_t* outside);
+
+/* JOINT optimisation of the interior waypoints and the durations under both penalties: what a GCOPTER / MINCO-style back-end gives -- a
+ * trajectory that is smooth, short in time, within v_max / a_max and clear of obstacles -- as one call (no reference counterpart).  Per
+ * trajectory, with the boundary derivatives and both end waypoints fixed,
+ *       minimise over p_1 .. p_{M-1}, T_0 .. T_{M-1}   f(p, T) = smooth_weight * J + time_weight * sum_i T_i + Phi(c*(p, T), T)
+ *       subject to   |p_k[axis] - p_k^start[axis]| <= max_move,   t_min <= T_i <= t_max
+ * J the control cost at the minimiser c*(p, T) of the equality-constrained QP (the QP does not see the penalty), Phi the fused flight
+ * penalty above.  Gradients, all from entries above:
+ *       df/dp_k = smooth_weight * uavqp_cost_waypoint_gradient_device_k + uavqp_solve_backward_device(g = dPhi/dc).grad_waypoints_k
+ *       df/dT_i = -smooth_weight * H_i + time_weight + (explicit dPhi/dT_i) + uavqp_solve_backward_device(g = dPhi/dc).grad_times_i
+ * (H_i: uavqp_cost_time_gradient_device; one backward call gives both backward terms.)
+ * Method (that of uavqp_waypoint_optimize_device and uavqp_time_optimize_device, joined): projected gradient descent with Armijo
+ * backtracking along the projection arc, in p and in u_i = log T_i.  Directions: d^p_k = (df/dp_k) / s_k, s_k = T_{k-1}^-(2r-1) + T_k^-(2r-1)
+ * at the current best durations, a component zero where the box blocks it; d^u_i = T_i df/dT_i, zero where a bound blocks it.  The two
+ * blocks have different units, so each gets a scale fixed at the start: sigma_p = initial_step_move / max |d^p|, sigma_u =
+ * initial_step_log / max |d^u| (a scale is 0 when its maximum is 0 or not finite); alpha starts at 1, or at 0 if both scales are 0 (such a
+ * trajectory proposes nothing and accepts nothing).  A positive diagonal scaling keeps -(sigma_p d^p, sigma_u d^u) a descent direction.
+ * Trial: p_t = clamp(p - alpha sigma_p d^p), T_t = clamp(T exp(-alpha sigma_u d^u)); accepted iff alpha > 0, its solve ends UAVQP_SOLVED
+ * and  f_trial <= f - armijo_c * [ sum_k (df/dp_k) . (p_k - p_t,k) + sum_i d^u_i log(T_i / T_t,i) ];  accepted: alpha *= grow, rejected:
+ * alpha *= shrink.  ONE accept / reject per trajectory and trial; f never increases.  A trajectory with M = 1 takes part through its duration alone.
+ * Host-side C++ sequencing of
+ *       anchor copy, clamp, solve, flight penalty, backward, step,
+ *       max_iters x { solve at the trial waypoints and durations, flight penalty, backward, step }, solve, flight penalty
+ * (the last penalty only for the three diagnostics): four launches per iteration, every decision ON THE DEVICE, nothing read back, the
+ * number of launches depends on max_iters alone.  The additions are in a fixed order: the same bytes run to run and for any grid.
+ * Asynchronous on the ctx stream (a first call of a given size allocates the workspace).
+ *   d_waypoints      [sum_b (M_b + 1)][3] IN: the start, OUT: the accepted waypoints; the two end knots come back byte for byte
+ *   d_times          [sum_b M_b] IN: the start, OUT: the accepted durations.  Durations of a trajectory that are all positive and finite
+ *                    are first projected into [t_min, t_max] (as uavqp_time_optimize_device does)
+ *                    A trajectory that is not UAVQP_SOLVED at the start (e.g. a non-positive duration: UAVQP_INVALID_INPUT) keeps its status,
+ *                    waypoints and durations byte for byte and takes no part -- except that the projection above comes before the first
+ *                    solve: a trajectory with all-positive, finite durations that fails to solve for another reason (a waypoint that
+ *                    is not finite) comes back with its durations projected, as from uavqp_time_optimize_device.
+ *   d_bc             as for uavqp_solve_batch_device; not changed
+ *   esdf, limits, clearance   validated as for uavqp_flight_penalty_device
+ *   d_coeff_out      the solve AT what is handed back: bit for bit what uavqp_solve_batch_device writes for it; d_status_out [n_traj] its
+ *                    status (may be NULL)
+ *   d_objective_out  [n_traj][2]: f at the start (after the projection of the durations), f at the result (NaN, NaN: took no part)
+ *   d_accepted_out   [n_traj] int32 accepted trials (may be NULL)
+ *   d_peak_out [n_traj][2], d_min_dist_out [n_traj], d_outside_out [n_traj] int32: the penalty's diagnostics at the result (each may be NULL)
+ *   params           uavqp_default_spacetime_params fills the defaults (those of the two optimisers it joins; max_iters from the CPU study of
+ *                    DESIGN.md section 5.20).  UAVQP_ERR_INVALID_ARG for a wrong struct_size, max_iters < 0 or > 100000, smooth_weight < 0,
+ *                    time_weight <= 0, t_min <= 0, t_min > t_max, max_move <= 0 (INFINITY is allowed: no box), an initial step <= 0,
+ *                    armijo_c outside (0, 1), shrink outside (0, 1), grow < 1 or any other non-finite value.  max_iters = 0: the plain
+ *                    solve, both objective columns equal, waypoints and durations untouched apart from the projection.
+ * UAVQP_ERR_INVALID_ARG also: r not 3 / 4, a negative count, NULL waypoints / times / bc / coeff_out / objective_out, ragged without offsets
+ * or with max_segments < 1, uniform with total_segments != uniform_segments * n_traj.
+ * WHAT THE RESULT IS.  Both penalties are SOFT: at finite weights the result may exceed a limit by a few per cent and may end closer than
+ * d_safe.  A sample outside the map contributes nothing to the clearance part, so f JUMPS DOWN where a sample leaves the map: max_move is
+ * the caller's handle (check d_outside_out).  The clearance part is piecewise smooth (its gradient jumps across the cell faces of the
+ * trilinear query), so the method converges to a point where no descent step of the tried lengths is left; the result is a LOCAL minimum,
+ * and a start on the symmetric saddle of an obstacle does not move sideways.  The two scales are fixed at the FIRST gradient: from a start far
+ * outside the limits (a gradient of 1e7 in the durations) the duration block moves slowly once the penalty has gone, and alternating
+ * uavqp_time_optimize_limits_device with uavqp_waypoint_optimize_device, which re-scales at every call, ended lower with the same number of
+ * solves; a second call of this entry re-scales too.  The hard tests remain uavqp_time_reallocate_device (limits: it
+ * then has far less to stretch) and uavqp_ellipsoid_check_* (collisions).
+ * Out of scope: corridor and general-rows solves, capture into a graph, multi-GPU (shard the batch as for the solve), quasi-Newton directions. */
+typedef struct uavqp_spacetime_params {
+    int32_t struct_size;
+    int32_t max_iters;          /* trials per trajectory (default 32) */ 
+    double smooth_weight;       /* weight of the control cost J, >= 0 (default 1) */
+    double time_weight;         /* weight of the total duration, > 0 (default 50) */
+    double t_min;               /* bounds of every duration, s (defaults 1e-2, 1e2) */
+    double t_max;
+    double max_move;            /* half edge of the box around every start waypoint, m, > 0, may be INFINITY (default 2) */
+    double initial_step_move;   /* largest move of a waypoint component in the first trial, m (default 0.1) */
+    double initial_step_log;    /* largest change of log T_i in the first trial (default 0.1) */
+    double armijo_c;            /* sufficient-decrease constant (default 1e-4) */
+    double shrink;              /* step factor after a rejected trial (default 0.5) */
+    double grow;                /* ... after an accepted one (default 2) */
+} uavqp_spacetime_params;
+void uavqp_default_spacetime_params(uavqp_spacetime_params* out);   /* callable without a device */
+int uavqp_spacetime_optimize_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                                    const int32_t* d_seg_offsets, double* d_waypoints, double* d_times, const double* d_bc,
+                                    const uavqp_esdf* esdf, const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
+                                    const uavqp_spacetime_params* params, double* d_coeff_out, int32_t* d_status_out, double* d_objective_out,
+                                    int32_t* d_accepted_out, double* d_peak_out, double* d_min_dist_out, int32_t* d_outside_out);
+/* The same from HOST pointers (H2D copy, run, D2H copy, synchronous; waypoints and times are updated in place; the map stays a device
+ * object; the coefficients of a trajectory that is not UAVQP_SOLVED come back as they do from uavqp_solve_batch_host). */
+int uavqp_spacetime_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                                  double* waypoints, double* times, const double* bc, const uavqp_esdf* esdf, const uavqp_limit_params* limits,
+                                  const uavqp_clearance_params* clearance, const uavqp_spacetime_params* params, double* coeff_out,
+                                  int32_t* status_out, double* objective_out, int32_t* accepted_out, double* peak_out, double* min_dist_out,
+                                  int32_t* outside_out);
 
 /* Batched evaluation of solved trajectories on a uniform time grid.
  * Replaces, for a whole batch, PolyTraj::evaluatePos / evaluateVel / evaluateAcc

@@ -73,6 +73,11 @@ SYMBOLS = (
     "uavqp_default_waypoint_opt_params",
     "uavqp_waypoint_optimize_device",
     "uavqp_waypoint_optimize_host",
+    "uavqp_flight_penalty_device",
+    "uavqp_flight_penalty_host",
+    "uavqp_default_spacetime_params",
+    "uavqp_spacetime_optimize_device",
+    "uavqp_spacetime_optimize_host",
     "uavqp_eval_batch_device",
     "uavqp_traj_length_device",
     "uavqp_ellipsoid_check_device",
@@ -154,6 +159,13 @@ class WaypointOptParams(ctypes.Structure):
     """uavqp_waypoint_opt_params of include/uavqp.h."""
     _fields_ = [("struct_size", ctypes.c_int32), ("max_iters", ctypes.c_int32), ("smooth_weight", ctypes.c_double), ("max_move", ctypes.c_double),
                 ("initial_step", ctypes.c_double), ("armijo_c", ctypes.c_double), ("shrink", ctypes.c_double), ("grow", ctypes.c_double)]
+
+
+class SpacetimeParams(ctypes.Structure):
+    """uavqp_spacetime_params of include/uavqp.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("max_iters", ctypes.c_int32), ("smooth_weight", ctypes.c_double), ("time_weight", ctypes.c_double),
+                ("t_min", ctypes.c_double), ("t_max", ctypes.c_double), ("max_move", ctypes.c_double), ("initial_step_move", ctypes.c_double),
+                ("initial_step_log", ctypes.c_double), ("armijo_c", ctypes.c_double), ("shrink", ctypes.c_double), ("grow", ctypes.c_double)]
 
 
 def build(force=False):
@@ -243,6 +255,16 @@ def lib():
                                                  ctypes.POINTER(WaypointOptParams), dp, ip, dp, ip, dp, ip]
     L.uavqp_waypoint_optimize_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(ClearanceParams),
                                                ctypes.POINTER(WaypointOptParams), dp, ip, dp, ip, dp, ip]
+    L.uavqp_flight_penalty_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, vp, ctypes.POINTER(LimitParams), ctypes.POINTER(ClearanceParams),
+                                              dp, dp, dp, dp, dp, ip]
+    L.uavqp_flight_penalty_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, vp, ctypes.POINTER(LimitParams), ctypes.POINTER(ClearanceParams),
+                                            dp, dp, dp, dp, dp, ip]
+    L.uavqp_default_spacetime_params.argtypes = [ctypes.POINTER(SpacetimeParams)]
+    L.uavqp_default_spacetime_params.restype = None
+    L.uavqp_spacetime_optimize_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(LimitParams),
+                                                  ctypes.POINTER(ClearanceParams), ctypes.POINTER(SpacetimeParams), dp, ip, dp, ip, dp, dp, ip]
+    L.uavqp_spacetime_optimize_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(LimitParams),
+                                                ctypes.POINTER(ClearanceParams), ctypes.POINTER(SpacetimeParams), dp, ip, dp, ip, dp, dp, ip]
     L.uavqp_eval_batch_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, i32, dp]
     L.uavqp_traj_length_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ctypes.c_double, dp, dp, ip]
     L.uavqp_ellipsoid_check_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, dp, i32,

@@ -163,6 +163,52 @@ def _clearance_function():
     return _Clearance
 
 
+_Flight = None
+
+
+def _flight_function():
+    global _Flight
+    if _Flight is not None:
+        return _Flight
+    import torch
+
+    class FlightPenalty(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, coeff, times, ctx, r, esdf, seg_offsets, uniform_segments, status, limits, clearance):
+            for name, t in (("coeff", coeff), ("times", times)):
+                if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+                    raise ValueError(f"flight_penalty: {name} must be a contiguous float64 tensor on the GPU")
+            total = times.numel()
+            n_traj = total // uniform_segments if uniform_segments > 0 else seg_offsets.numel() - 1
+            if coeff.numel() != 3 * 2 * r * total:
+                raise ValueError("flight_penalty: coeff must hold 3 * 2r doubles per segment")
+            phi = torch.empty(n_traj, dtype=torch.float64, device=times.device)
+            g_c = torch.empty_like(coeff)
+            g_t = torch.empty_like(times)
+            ctx.set_stream(torch.cuda.current_stream(times.device).cuda_stream)
+            ctx.flight_penalty_device(r, n_traj, uniform_segments, seg_offsets, times.detach(), coeff.detach(), esdf, status=status,
+                                      penalty=phi, grad_coeff=g_c, grad_times=g_t, limits=limits, clearance=clearance)
+            if uniform_segments > 0:
+                counts = torch.full((n_traj,), uniform_segments, dtype=torch.int64, device=times.device)
+            else:
+                counts = (seg_offsets[1:] - seg_offsets[:-1]).to(torch.int64)
+            fctx.save_for_backward(g_c, g_t, counts)
+            fctx.nc = 3 * 2 * r
+            return phi
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable   # the gradients come from a raw kernel: no second derivative through them
+        def backward(fctx, grad_phi):
+            g_c, g_t, counts = fctx.saved_tensors
+            need_c, need_t = fctx.needs_input_grad[:2]
+            out_c = g_c * torch.repeat_interleave(grad_phi, counts * fctx.nc) if need_c else None
+            out_t = g_t * torch.repeat_interleave(grad_phi, counts) if need_t else None
+            return out_c, out_t, None, None, None, None, None, None, None, None
+
+    _Flight = FlightPenalty
+    return _Flight
+
+
 def solve_batch(ctx, r, waypoints, times, bc, seg_offsets=None, uniform_segments=0, max_segments=0, check_status=False, return_status=False):
     """Differentiable uavqp_solve_batch_device.  ctx: a Context on the tensors' device.  waypoints [sum (M_b + 1)][3], times [sum M_b],
     bc [n_traj][2][r-1][3]; seg_offsets: int32 device tensor [n_traj + 1] (ragged; max_segments = the longest trajectory, read back from
@@ -200,3 +246,15 @@ def clearance_penalty(ctx, r, coeff, times, esdf, seg_offsets=None, uniform_segm
     if uniform_segments <= 0 and seg_offsets is None:
         raise ValueError("clearance_penalty: ragged batches need seg_offsets")
     return _clearance_function().apply(coeff, times, ctx, int(r), esdf, seg_offsets, int(uniform_segments), status, dict(params))
+
+
+def flight_penalty(ctx, r, coeff, times, esdf, seg_offsets=None, uniform_segments=0, status=None, limits=None, clearance=None):
+    """Differentiable uavqp_flight_penalty_device: limit penalty + clearance penalty [n_traj] of coeff (layout of solve_batch's result) at
+    the durations `times` [sum M_b] against the distance field `esdf` (an esdf.EsdfMap on ctx, updated), in one launch.  limits / clearance:
+    dicts of uavqp_limit_params / uavqp_clearance_params fields that differ from the defaults.  status: optional int32 status tensor of
+    the solve.  The gradient in `times` is the explicit part; with coeff = solve_batch(..., times, ...) torch adds the part through the
+    solve, and waypoints.grad / bc.grad come from the same backward pass."""
+    if uniform_segments <= 0 and seg_offsets is None:
+        raise ValueError("flight_penalty: ragged batches need seg_offsets")
+    return _flight_function().apply(coeff, times, ctx, int(r), esdf, seg_offsets, int(uniform_segments), status, dict(limits or {}),
+                                    dict(clearance or {}))

@@ -249,6 +249,58 @@ class TrajOptimizer {
         for (int32_t s : status_) if (s != UAVQP_SOLVED) return false;
         return true;
     }
+    // Joint optimisation of the interior waypoints AND the durations under both penalties (include/uavqp.h uavqp_spacetime_optimize_host;
+    // the reference's equality rows only: false when a corridor or rows are set): minimises, per trajectory, smooth_weight * cost +
+    // time_weight * sum T + limit penalty + clearance penalty against `map` (a uavqp::EsdfMap of cpp/esdf_map.h built on context() and
+    // updated).  On return waypoints() / timeAllocation() = the optimised point, getPolyCoeff() = the solve at it, objective() =
+    // [n_traj][2] f at the start / at the result, acceptedTrials() per trajectory, peak() / minDist() / outsideSamples() the penalties'
+    // diagnostics at the result.  params: null = uavqp_default_spacetime_params.  Both penalties are soft and the result a local minimum:
+    // uavqp_time_reallocate_device and uavqp_ellipsoid_check_* afterwards remain the hard tests.
+    template <class Map>
+    bool optimizeTrajectory(const Map& map, const uavqp_limit_params& limits, const uavqp_clearance_params& clearance,
+                            const uavqp_spacetime_params* params = nullptr) {
+        if (n_traj_ <= 0 || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_])) return false;
+        if (!lo_.empty() || rows_k_ > 0) {
+            std::cout << "solver solve failed! (optimizeTrajectory: corridor and general-rows problems are out of scope)" << std::endl;
+            return false;
+        }
+        if (!ensureContext()) return false;
+        if (bc_.empty()) bc_.assign(static_cast<size_t>(n_traj_) * 2 * (order_ - 1) * 3, 0.0);
+        uavqp_spacetime_params pp;
+        if (params) pp = *params; else uavqp_default_spacetime_params(&pp);
+        coef_.assign(static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_], 0.0);
+        status_.assign(n_traj_, 0);
+        objective_.assign(static_cast<size_t>(2) * n_traj_, 0.0);
+        accepted_.assign(n_traj_, 0);
+        peak_.assign(static_cast<size_t>(2) * n_traj_, 0.0);
+        min_dist_.assign(n_traj_, 0.0);
+        outside_.assign(n_traj_, 0);
+        const int rc = uavqp_spacetime_optimize_host(ctx_, order_, n_traj_, 0, 0, seg_offsets_.data(), wp_.data(), T_.data(), bc_.data(), map.handle(),
+                                                     &limits, &clearance, &pp, coef_.data(), status_.data(), objective_.data(), accepted_.data(),
+                                                     peak_.data(), min_dist_.data(), outside_.data());
+        if (rc != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            return false;
+        }
+        for (int32_t s : status_) if (s != UAVQP_SOLVED) return false;
+        return true;
+    }
+    // Limit penalty + clearance penalty per trajectory of the stored coefficients at the stored durations, in one launch
+    // (uavqp_flight_penalty_host).  A trajectory that did not solve carries zero.  Empty on failure.
+    template <class Map>
+    std::vector<double> getFlightPenalty(const Map& map, const uavqp_limit_params& limits, const uavqp_clearance_params& clearance) {
+        std::vector<double> phi;
+        if (n_traj_ <= 0 || !ctx_ || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_]) ||
+            coef_.size() != static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_] || status_.size() != static_cast<size_t>(n_traj_))
+            return phi;
+        phi.assign(n_traj_, 0.0);
+        if (uavqp_flight_penalty_host(ctx_, order_, n_traj_, 0, seg_offsets_.data(), T_.data(), coef_.data(), status_.data(), map.handle(), &limits,
+                                      &clearance, phi.data(), nullptr, nullptr, nullptr, nullptr, nullptr) != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            phi.clear();
+        }
+        return phi;
+    }
     const std::vector<double>& waypoints() const { return wp_; }
     const std::vector<double>& minDist() const { return min_dist_; }
     const std::vector<int32_t>& outsideSamples() const { return outside_; }

@@ -121,3 +121,10 @@
     UAVQP_INST __global__ void uavqp::waypoint_opt_step_kernel<R_, true>(uavqp::WaypointOptArgs);     \
     UAVQP_INST __global__ void uavqp::waypoint_opt_step_kernel<R_, false>(uavqp::WaypointOptArgs);
 #define UAVQP_INSTANCES_WPOPT UAVQP_WPOPT_R(3) UAVQP_WPOPT_R(4)
+
+// ---- qp_spacetime.h: the fused flight penalty (limits + clearance in one launch), the steps of the joint waypoint / duration optimiser
+#define UAVQP_SPACETIME_R(R_)                                                                   \
+    UAVQP_INST __global__ void uavqp::flight_penalty_kernel<R_>(uavqp::FlightArgs);                \
+    UAVQP_INST __global__ void uavqp::spacetime_step_kernel<R_, true>(uavqp::SpacetimeArgs);       \
+    UAVQP_INST __global__ void uavqp::spacetime_step_kernel<R_, false>(uavqp::SpacetimeArgs);
+#define UAVQP_INSTANCES_SPACETIME UAVQP_SPACETIME_R(3) UAVQP_SPACETIME_R(4)

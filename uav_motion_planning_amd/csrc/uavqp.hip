@@ -36,6 +36,7 @@
 #include "qp_limits.h"
 #include "qp_esdf.h"
 #include "qp_waypoint_opt.h"
+#include "qp_spacetime.h"
 // Measured-slower alternatives kept as bit-identical cross-checks: `make experiments` (-DUAVQP_EXPERIMENTS) only
 #ifdef UAVQP_EXPERIMENTS
 #include "cloud_grid2d.h"
@@ -64,6 +65,7 @@ UAVQP_INSTANCES_ADJOINT
 UAVQP_INSTANCES_LIMITS
 UAVQP_INSTANCES_ESDF
 UAVQP_INSTANCES_WPOPT
+UAVQP_INSTANCES_SPACETIME
 #endif
 
 namespace uavqp {
@@ -1939,6 +1941,11 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
 // Waypoint gradient of the control cost and the waypoint optimiser against the distance field
 // ===================================================================================================
 #include "uavqp_waypoint_opt.h"
+
+// ===================================================================================================
+// Fused flight penalty (limits + clearance) and the joint optimiser of waypoints and durations
+// ===================================================================================================
+#include "uavqp_spacetime.h"
 
 // ===================================================================================================
 // N3: quadrotor_msgs/PolynomialTrajectory packer (host only)

@@ -308,6 +308,93 @@ class Context:
         _lib.check(rc, "uavqp_waypoint_optimize_host")
         return waypoints, coeff, status, objective, accepted, min_dist, outside
 
+    @staticmethod
+    def _spacetime_params(params):
+        pp = _lib.SpacetimeParams()
+        _lib.lib().uavqp_default_spacetime_params(ctypes.byref(pp))
+        for k, v in params.items():
+            if not hasattr(pp, k) or k == "struct_size":
+                raise ValueError(f"unknown uavqp_spacetime_params field {k!r}")
+            setattr(pp, k, v)
+        return pp
+
+    def flight_penalty_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, esdf, status=None, penalty=None, grad_coeff=None,
+                              grad_times=None, peak=None, min_dist=None, outside=None, limits=None, clearance=None):
+        """uavqp_flight_penalty_device on device buffers: limit penalty + clearance penalty against `esdf` (an esdf.EsdfMap, updated) in
+        one launch -- the sum [n_traj], its gradient in the coefficients at fixed durations, its EXPLICIT gradient in the durations, and
+        the diagnostics of both parts (peak [n_traj][2], min_dist [n_traj], outside [n_traj] int32); each output may be None.  limits /
+        clearance: dicts of uavqp_limit_params / uavqp_clearance_params fields that differ from the defaults.  Asynchronous."""
+        lp, cp = self._limit_params(limits or {}), self._clearance_params(clearance or {})
+        rc = _lib.lib().uavqp_flight_penalty_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff), _ptr(status),
+                                                    getattr(esdf, "handle", esdf), ctypes.byref(lp), ctypes.byref(cp), _ptr(penalty),
+                                                    _ptr(grad_coeff), _ptr(grad_times), _ptr(peak), _ptr(min_dist), _ptr(outside))
+        _lib.check(rc, "uavqp_flight_penalty_device")
+
+    def flight_penalty_host(self, r, seg_offsets, times, coeff, esdf, uniform_segments=0, status=None, limits=None, clearance=None):
+        """numpy in / numpy out (synchronous; the map stays on the device).  Returns (penalty [n_traj], grad_coeff, grad_times [sum M],
+        peak [n_traj][2], min_dist [n_traj], outside [n_traj] int32)."""
+        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
+        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total and coeff.size == 3 * 2 * r * total
+        lp, cp = self._limit_params(limits or {}), self._clearance_params(clearance or {})
+        penalty = np.zeros(n_traj, dtype=np.float64)
+        g_c = np.zeros_like(coeff)
+        g_t = np.zeros(total, dtype=np.float64)
+        peak = np.zeros((n_traj, 2), dtype=np.float64)
+        min_dist = np.zeros(n_traj, dtype=np.float64)
+        outside = np.zeros(n_traj, dtype=np.int32)
+        rc = _lib.lib().uavqp_flight_penalty_host(self._h, r, n_traj, uniform_segments, _ptr(so), _ptr(times), _ptr(coeff), _ptr(status),
+                                                  getattr(esdf, "handle", esdf), ctypes.byref(lp), ctypes.byref(cp), _ptr(penalty), _ptr(g_c),
+                                                  _ptr(g_t), _ptr(peak), _ptr(min_dist), _ptr(outside))
+        _lib.check(rc, "uavqp_flight_penalty_host")
+        return penalty, g_c, g_t, peak, min_dist, outside
+
+    def spacetime_optimize_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc, esdf,
+                                  coeff_out, status_out, objective_out, accepted_out=None, peak_out=None, min_dist_out=None, outside_out=None,
+                                  limits=None, clearance=None, **params):
+        """uavqp_spacetime_optimize_device on device buffers: `waypoints` and `times` hold the start and receive the jointly optimised
+        interior waypoints and durations, coeff_out the solve at them, objective_out [n_traj][2] f = smooth_weight * cost + time_weight *
+        sum T + limit penalty + clearance penalty against `esdf` at the start and at the result; peak_out / min_dist_out / outside_out the
+        penalties' diagnostics at the result.  limits / clearance: dicts of uavqp_limit_params / uavqp_clearance_params fields; params:
+        fields of uavqp_spacetime_params that differ from the defaults.  Both penalties are soft and the result is a local minimum
+        (include/uavqp.h).  Asynchronous."""
+        pp = self._spacetime_params(params)
+        lp, cp = self._limit_params(limits or {}), self._clearance_params(clearance or {})
+        rc = _lib.lib().uavqp_spacetime_optimize_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), _ptr(seg_offsets),
+                                                        _ptr(waypoints), _ptr(times), _ptr(bc), getattr(esdf, "handle", esdf), ctypes.byref(lp),
+                                                        ctypes.byref(cp), ctypes.byref(pp), _ptr(coeff_out), _ptr(status_out),
+                                                        _ptr(objective_out), _ptr(accepted_out), _ptr(peak_out), _ptr(min_dist_out),
+                                                        _ptr(outside_out))
+        _lib.check(rc, "uavqp_spacetime_optimize_device")
+
+    def spacetime_optimize_host(self, r, seg_offsets, waypoints, times, bc, esdf, uniform_segments=0, limits=None, clearance=None, **params):
+        """numpy in / numpy out (synchronous; the map stays on the device).  Returns (waypoints [sum (M + 1)][3], times [sum M], coeff_flat,
+        status, objective [n_traj][2], accepted, peak [n_traj][2], min_dist [n_traj], outside [n_traj] int32)."""
+        waypoints = np.array(waypoints, dtype=np.float64).reshape(-1, 3)   # copies: the call updates both in place
+        times = np.array(times, dtype=np.float64).ravel()
+        bc = np.ascontiguousarray(bc, dtype=np.float64)
+        so, n_traj, total, mmax = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total
+        assert waypoints.size == 3 * (total + n_traj), "waypoints must hold sum(M_b + 1) xyz rows"
+        assert bc.size == n_traj * 2 * (r - 1) * 3
+        pp = self._spacetime_params(params)
+        lp, cp = self._limit_params(limits or {}), self._clearance_params(clearance or {})
+        coeff = np.zeros(3 * 2 * r * total, dtype=np.float64)
+        status = np.zeros(n_traj, dtype=np.int32)
+        objective = np.zeros((n_traj, 2), dtype=np.float64)
+        accepted = np.zeros(n_traj, dtype=np.int32)
+        peak = np.zeros((n_traj, 2), dtype=np.float64)
+        min_dist = np.zeros(n_traj, dtype=np.float64)
+        outside = np.zeros(n_traj, dtype=np.int32)
+        rc = _lib.lib().uavqp_spacetime_optimize_host(self._h, r, n_traj, uniform_segments, max(mmax, 1), _ptr(so), _ptr(waypoints), _ptr(times),
+                                                      _ptr(bc), getattr(esdf, "handle", esdf), ctypes.byref(lp), ctypes.byref(cp),
+                                                      ctypes.byref(pp), _ptr(coeff), _ptr(status), _ptr(objective), _ptr(accepted), _ptr(peak),
+                                                      _ptr(min_dist), _ptr(outside))
+        _lib.check(rc, "uavqp_spacetime_optimize_host")
+        return waypoints, times, coeff, status, objective, accepted, peak, min_dist, outside
+
     def time_optimize_limits_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc,
                                     coeff_out, status_out, objective_out, accepted_out=None, peak_out=None, limits=None, **params):
         """uavqp_time_optimize_limits_device on device buffers: time_optimize_device with the limit penalty inside the objective
@@ -679,6 +766,11 @@ class TrajOptimizer:
                                      clearance penalty against an esdf.EsdfMap built on context() (uavqp_waypoint_optimize_host); stores
                                      the optimised waypoints (getWaypoints) and the coefficients at them; .objective as for optimizeTime,
                                      .min_dist / .outside [n_traj] the penalty's diagnostics at the result
+    optimizeTrajectory(esdf, ...)    equality-constrained problems only: moves the interior waypoints AND the durations together to
+                                     minimise smooth_weight * cost + time_weight * sum T + limit penalty + clearance penalty
+                                     (uavqp_spacetime_optimize_host); stores waypoints, durations and coefficients; .objective,
+                                     .iterations, .peak, .min_dist, .outside as above
+    getFlightPenalty(esdf, ...)      [n_traj] limit + clearance penalty of the stored coefficients in one launch
     getCostWaypointGradient()        [sum (M_b + 1)][3] gradient of getCost() in the waypoints, both ends of every trajectory included
     backward(grad_coeff)             equality-constrained problems only, after solve(): (grad_times, grad_waypoints, grad_bc) of a loss
                                      with d loss / d getPolyCoeff() = grad_coeff, through the solve
@@ -806,6 +898,36 @@ class TrajOptimizer:
         self._wp, self._coef, self.status, self.objective, self.iterations, self.min_dist, self.outside = ctx.waypoint_optimize_host(
             self._r, self._so, self._wp, self._T, bc, esdf, clearance=clearance, **params)
         return bool(np.all(self.status == _lib.UAVQP_SOLVED))
+
+    def optimizeTrajectory(self, esdf, limits=None, clearance=None, **params):
+        """Optimises the stored interior waypoints AND the stored time allocation together (uavqp_spacetime_optimize_host): minimises
+        smooth_weight * cost + time_weight * sum T + limit penalty + clearance penalty against the distance field `esdf` (an esdf.EsdfMap
+        on this optimiser's context -- see context() --, updated).  The reference's equality rows only: a corridor or rows set raises
+        ValueError.  True iff every trajectory is solved at the result; getPolyCoeff() is the solve at getWaypoints() and
+        getTimeAllocation().  limits / clearance: dicts of uavqp_limit_params / uavqp_clearance_params fields; params: fields of
+        uavqp_spacetime_params that differ from the defaults (an unknown field raises ValueError).  .objective [n_traj][2] (start,
+        result), .iterations accepted trials, .peak [n_traj][2], .min_dist, .outside the penalties' diagnostics at the result.  Both
+        penalties are soft (include/uavqp.h)."""
+        if self._lo is not None or self._rows is not None:
+            raise ValueError("optimizeTrajectory: corridor and general-rows problems are out of scope (include/uavqp.h)")
+        Context._spacetime_params(params)   # (an unknown field is refused before anything runs)
+        if self._wp is None or self._T is None:
+            return False
+        n_traj = self._so.size - 1
+        if self._T.size != int(self._so[-1]):
+            return False
+        bc = self._bc if self._bc is not None else np.zeros((n_traj, 2, self._r - 1, 3))
+        ctx = self.context()
+        (self._wp, self._T, self._coef, self.status, self.objective, self.iterations, self.peak, self.min_dist,
+         self.outside) = ctx.spacetime_optimize_host(self._r, self._so, self._wp, self._T, bc, esdf, limits=limits, clearance=clearance, **params)
+        return bool(np.all(self.status == _lib.UAVQP_SOLVED))
+
+    def getFlightPenalty(self, esdf, limits=None, clearance=None):
+        """[n_traj] limit penalty + clearance penalty of the stored coefficients at the stored durations against `esdf`, in one launch
+        (uavqp_flight_penalty_host).  Trajectories that did not solve carry zero."""
+        if self._ctx is None or self._coef.size != 3 * 2 * self._r * int(self._so[-1]) or self.status.size != self._so.size - 1:
+            raise _lib.UavqpError("getFlightPenalty: no solved coefficients (call solve() first)")
+        return self._ctx.flight_penalty_host(self._r, self._so, self._T, self._coef, esdf, status=self.status, limits=limits, clearance=clearance)[0]
 
     def getWaypoints(self):
         return self._wp.copy()
