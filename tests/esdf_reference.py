@@ -2,6 +2,7 @@
 written from the semantics stated in the header and not from the kernels.
 
   * squared distances by BRUTE FORCE: every voxel against every occupied (free) voxel, in integers -- no separable passes, no envelope;
+    and, for grids the brute force cannot afford, by one exact min-plus pass per axis over every pair of a line (separable_sq);
   * the field, the rasteriser, the trilinear query and the penalty in np.longdouble;
   * every query point comes with its MARGIN in voxels: the smallest distance of (pos - origin) / res - 0.5 to an integer on any axis
     (the faces across which the trilinear gradient jumps) and of the position to the two 1e-4 map bounds; the penalty also reports the
@@ -36,10 +37,32 @@ def brute_sq(mask):
     return out
 
 
-def field(occ, resolution, max_dist):
-    """occ [nx][ny][nz] (non-zero = occupied) -> dict sq_pos, sq_neg (int64), d_pos, d_neg, dist (longdouble)"""
+def separable_sq(mask):
+    """The same function as brute_sq by the separability of the squared Euclidean distance: with f = 0 on True voxels and "none"
+    elsewhere, one exact pass  out[p] = min_q f[q] + (p - q)^2  along each axis in turn.  int64; every q of a line is visited for every p
+    (no early exit, no tiling), so the cost is (the sum of the dimensions) x (the voxels) and a grid too large for brute_sq stays cheap.
+    "None" is 2^40 between the passes: above every true value (< 3 * 2^20) plus every (p - q)^2, far below the int64 range."""
+    mask = np.asarray(mask, dtype=bool)
+    none = np.int64(1) << 40
+    f = np.where(mask, np.int64(0), none)
+    for axis in range(3):
+        g = np.moveaxis(f, axis, 0)
+        p = np.arange(g.shape[0], dtype=np.int64).reshape(-1, 1, 1)
+        out = np.full(g.shape, none, dtype=np.int64)
+        for q in range(g.shape[0]):
+            np.minimum(out, g[q][None] + (p - q) ** 2, out=out)
+        f = np.moveaxis(out, 0, axis)
+    return np.where(f >= none, np.int64(INT32_MAX), f)
+
+
+SQ = {"brute": brute_sq, "separable": separable_sq}
+
+
+def field(occ, resolution, max_dist, sq="brute"):
+    """occ [nx][ny][nz] (non-zero = occupied) -> dict sq_pos, sq_neg (int64), d_pos, d_neg, dist (longdouble); sq names the function
+    that gives the squared distances: "brute" (brute_sq) or "separable" (separable_sq)"""
     occ = np.asarray(occ) != 0
-    sq_pos, sq_neg = brute_sq(occ), brute_sq(~occ)
+    sq_pos, sq_neg = SQ[sq](occ), SQ[sq](~occ)
     res, md = LD(resolution), LD(max_dist)
     d_pos = np.minimum(res * np.sqrt(sq_pos.astype(LD)), md)
     d_neg = np.minimum(res * np.sqrt(sq_neg.astype(LD)), md)

@@ -7,7 +7,11 @@ soundness of the reference the GPU tests compare against (tests/esdf_reference.p
     multilinear, so the scheme's error is pure rounding; estimated at step h against h / 2 it must stay under 1e-5 of the largest
     gradient entry, and the analytic gradient within 10 x that estimate (the criterion of tests/test_limit_penalty_contract.py);
   * the reference penalty's two gradients against central differences of its own Phi, same criterion, under the margin conditions
-    (no sample within 1e-6 voxel of a face or a map bound, none with |d - d_safe| < 1e-9)."""
+    (no sample within 1e-6 voxel of a face or a map bound, none with |d - d_safe| < 1e-9);
+  * the second exact transform, separable_sq (one min-plus pass per axis), against the brute force on the thin grids that
+    tests/test_gpu_esdf.py takes past one LDS tile, and against scipy's exact Euclidean transform on the one grid the brute force cannot
+    afford -- the reference of that grid on the device;
+  * the seeds of the long clearance batch (tests/esdf_scene.py: long_flight_batch) still qualify, on the coefficients of the CPU solve."""
 import ctypes
 import os
 import re
@@ -16,6 +20,7 @@ import numpy as np
 import pytest
 
 import esdf_reference as E
+import esdf_scene as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LD = np.longdouble
@@ -71,6 +76,86 @@ def test_brute_force_transform_agrees_with_the_envelope_passes(dims, density, se
         assert np.all(f["sq_pos"] == 0) and np.all(f["sq_neg"] == E.INT32_MAX) and np.all(f["dist"] == LD(0.1) - LD(2.5))
     # signs: positive outside obstacles, not positive inside
     assert np.all(f["dist"][~occ] > 0) and np.all(f["dist"][occ] <= 0)
+
+
+BRUTE_TILED = [g for g, (_, sq) in S.TILED_GRIDS.items() if sq == "brute"]
+FULL_TILED = [g for g, (_, sq) in S.TILED_GRIDS.items() if sq == "separable"]
+
+
+@pytest.mark.parametrize("dims", BRUTE_TILED + S.GRIDS, ids=lambda g: "x".join(map(str, g)))
+def test_separable_transform_equals_the_brute_force(dims):
+    for variant in ("random_3", "random_60"):
+        occ = S.occupancy(dims, variant) != 0
+        assert 0 < np.count_nonzero(occ) < occ.size or occ.size < 64, "a random grid with no or only occupied voxels says nothing"
+        for mask in (occ, ~occ):
+            want, got = E.brute_sq(mask), E.separable_sq(mask)
+            assert got.dtype == np.int64 and np.array_equal(got, want), (dims, variant)
+
+
+def test_separable_transform_of_an_empty_mask_is_int32_max():
+    assert np.all(E.separable_sq(np.zeros((3, 4, 5), dtype=bool)) == E.INT32_MAX)
+    assert np.all(E.separable_sq(np.ones((3, 4, 5), dtype=bool)) == 0)
+    f = E.field(np.zeros((3, 4, 5), dtype=np.uint8), 0.1, 2.5, sq="separable")
+    g = E.field(np.zeros((3, 4, 5), dtype=np.uint8), 0.1, 2.5)
+    assert all(np.array_equal(f[k], g[k]) for k in f)
+
+
+@pytest.mark.parametrize("dims", FULL_TILED, ids=lambda g: "x".join(map(str, g)))
+def test_separable_transform_equals_scipy_on_the_full_grid(dims):
+    ndimage = pytest.importorskip("scipy.ndimage")
+    assert len(FULL_TILED) == 1
+    for variant in ("random_3", "random_60"):
+        occ = S.occupancy(dims, variant) != 0
+        for mask in (occ, ~occ):
+            # (distance_transform_edt: the distance of every non-zero element to the nearest zero; squares below 2^15 are exact in float64)
+            want = np.rint(ndimage.distance_transform_edt(~mask) ** 2).astype(np.int64)
+            assert np.array_equal(E.separable_sq(mask), want), (dims, variant)
+
+
+def test_tiled_grids_reach_the_launch_shapes_they_are_there_for():
+    """from the dimensions alone: more than one z tile per outer index, or a completely full tile, in the pass each grid names"""
+    for dims, (passes, _) in S.TILED_GRIDS.items():
+        shape = S.launch_shape(dims)
+        for p in passes:
+            full, last, blocks = shape[p]
+            assert blocks >= 2 or full == S.TILE, (dims, p, shape[p])
+    assert S.launch_shape((3, 100, 100))["y"] == (8100, 1900, 2) and S.launch_shape((100, 3, 100))["x"] == (8100, 1900, 2)
+    assert S.launch_shape((1024, 2, 9))["x"] == (8192, 1024, 2) and S.launch_shape((1024, 2, 9))["z"][2] == 3
+    assert S.launch_shape((2, 1024, 8))["y"] == (8192, 8192, 1)
+    assert S.launch_shape((3, 3, 1024))["z"] == (8192, 1024, 2)
+    assert S.launch_shape((100, 90, 95))["y"] == (8190, 360, 2) and S.launch_shape((100, 90, 95))["x"] == (8100, 1400, 2)
+    for dims in S.GRIDS:        # the older grids: one tile per outer index in both passes
+        assert S.launch_shape(dims)["y"][2] == 1 and S.launch_shape(dims)["x"][2] == 1
+
+
+@pytest.mark.parametrize("r", [3, 4])
+def test_long_clearance_batch_seeds_qualify(oracle, r):
+    """13 trajectories, M from {1, 9, 11, 16, 17}: margins, at least 4 penalised and 3 free trajectories, one that leaves the map, and at
+    least 3 whose gradient reaches a segment of index >= 8 (the second round of a sub-lane of clearance_penalty_kernel)"""
+    b = S.long_flight_batch(r)
+    assert b["n"] == 13 and b["n"] % 8 != 0 and b["mmax"] == 17
+    _, ref = S.scene_reference()
+    pen = E.penalty(r, b["so"], b["T"], S.cpu_coeff(oracle, b), ref["dist"], S.ORIGIN, S.MRES, S.MMAX, **S.PARAMS)
+    assert S.long_batch_qualifies(b, pen) == []
+
+
+@pytest.mark.parametrize("r", [3, 4])
+def test_base_batch_of_the_past_one_grid_tests_qualifies(oracle, r):
+    """the 61 trajectories tests/test_gpu_beyond_one_grid.py tiles: margins of the clearance samples, and both penalties active on at least
+    8 and inactive on at least 8 trajectories -- whichever trajectory is the invalid one (the GPU test places it by the device's CU count)"""
+    import limit_penalty_reference as L
+    import spacetime_reference as R
+    _, ref = S.scene_reference()
+    b = S.base_flight_batch(r)
+    assert b["n"] == 61 and set(np.diff(b["so"]).tolist()) == {1, 2, 3}
+    c = S.cpu_coeff(oracle, b)
+    clr = E.penalty(r, b["so"], b["T"], c, ref["dist"], S.ORIGIN, S.MRES, S.MMAX, **S.PARAMS)
+    lim = L.penalty(r, b["so"], b["T"], c, **R.LIMITS_OF[r])
+    assert S.base_batch_qualifies(b, clr, lim) == []
+    # one trajectory less changes each count by at most one
+    for pen in (clr, lim):
+        assert np.count_nonzero(pen["phi"] > 0) >= 9 and np.count_nonzero(pen["phi"] == 0) >= 8
+    assert np.count_nonzero(clr["outside"] > 0) >= 2
 
 
 def small_map(seed):

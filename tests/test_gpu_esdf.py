@@ -2,22 +2,26 @@
 against the numpy reference of tests/esdf_reference.py (brute-force transform, longdouble field / query / penalty).
 
 Tolerances.
-  transform  sq_pos / sq_neg EQUAL to the brute force.  dist within 4 ulp of max(d_pos, d_neg, resolution): one sqrt, one multiply, two
-             additions.
+  transform  sq_pos / sq_neg EQUAL to the brute force (on the one grid that tiles both the y and the x pass: to the reference's exact
+             separable passes, which tests/test_esdf_contract.py pins against the brute force and scipy).  dist within 4 ulp of
+             max(d_pos, d_neg, resolution): one sqrt, one multiply, two additions.
   rasteriser bytes equal (the reference asserts that no (p + k res - origin) / res lies within 1e-6 of an integer).
   query      inside equal; dist, and grad * resolution, within 1e-13 of max(|the 8 corner values|, resolution): about 20 float64 operations.
   penalty    Phi, both gradients, min_dist within 1e-9 of the per-trajectory largest magnitude of that output (the project's parity
              tolerance; reference and device read the SAME device coefficients); outside equal.  The reference asserts that no sample
              lies within 1e-6 voxel of a cell face or a map bound and none has |d - d_safe| < 1e-9.
-The seeds below were checked for those margins on the CPU (coefficients of the CPU solve in place of the device's)."""
+The seeds were checked for those margins on the CPU (coefficients of the CPU solve in place of the device's).  Grids, scene, points and
+batches are built in tests/esdf_scene.py, which the CPU contract tests share."""
 import ctypes
-import functools
 import math
 
 import numpy as np
 import pytest
 
 import esdf_reference as E
+import esdf_scene as S
+from esdf_scene import (DIMS, GRIDS, HI, MAXD, MMAX, MRES, ORIGIN, PARAMS, RES, VARIANTS, flight_batch, occupancy, pillar_points, query_points,
+                        raster_cloud, transform_reference)
 import uav_motion_planning_amd as U
 from uav_motion_planning_amd import _lib
 from uav_motion_planning_amd.esdf import EsdfMap
@@ -38,33 +42,18 @@ def up(x):
 
 
 # ---------------------------------------------------------------------------------------------------------------- transform
-GRIDS = [(1, 37, 1), (65, 3, 2), (5, 67, 3), (3, 2, 130), (33, 31, 17)]
-VARIANTS = ["random_3", "random_60", "corner", "free", "occupied"]
-CASES = [((1, 1, 1), "free"), ((1, 1, 1), "occupied")] + [(g, v) for g in GRIDS for v in VARIANTS]
-RES, MAXD = 0.15, 7.5
-
-
-def occupancy(dims, variant):
-    rng = np.random.default_rng(sum(dims) * 7 + len(variant))
-    if variant == "random_3":
-        return (rng.random(dims) < 0.03).astype(np.uint8)
-    if variant == "random_60":
-        return (rng.random(dims) < 0.60).astype(np.uint8) * 255     # non-zero = occupied
-    occ = np.zeros(dims, dtype=np.uint8)
-    if variant == "corner":
-        occ[-1, -1, -1] = 1
-    if variant == "occupied":
-        occ[:] = 1
-    return occ
-
-
-@functools.lru_cache(maxsize=None)
-def transform_reference(dims, variant):
-    return E.field(occupancy(dims, variant), RES, MAXD)
+# (grids, occupancies and their references: tests/esdf_scene.py)
+CASES = [((1, 1, 1), "free"), ((1, 1, 1), "occupied")] + [(g, v) for g in GRIDS for v in VARIANTS] + S.TILED_CASES
 
 
 @pytest.mark.parametrize("dims,variant", CASES, ids=[f"{'x'.join(map(str, g))}-{v}" for g, v in CASES])
 def test_transform_is_exact_and_dist_within_4_ulp(gpu_ctx, dims, variant):
+    if dims in S.TILED_GRIDS:
+        # from the dimensions alone: the grid still takes the pass it names past one tile per outer index, or fills a tile completely
+        shape = S.launch_shape(dims)
+        for axis in S.TILED_GRIDS[dims][0]:
+            full, last, blocks = shape[axis]
+            assert blocks >= 2 or full == S.TILE, f"{dims}: the {axis} pass stays within one partly filled tile {shape[axis]}"
     occ = occupancy(dims, variant)
     ref = transform_reference(dims, variant)
     with EsdfMap(gpu_ctx, dims, (0.3, -1.0, 2.0), RES, MAXD) as m:
@@ -86,21 +75,7 @@ def test_transform_is_exact_and_dist_within_4_ulp(gpu_ctx, dims, variant):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the scene
-DIMS, ORIGIN, MRES, MMAX = (40, 33, 17), (-5.0, -4.0, 0.0), 0.25, 10000.0
-HI = tuple(o + n * MRES for o, n in zip(ORIGIN, DIMS))
-
-
-def raster_cloud(seed=3):
-    """200 points: most inside, some outside the map, some within one inflation step of each face"""
-    rng = np.random.default_rng(seed)
-    lo, hi = np.array(ORIGIN), np.array(HI)
-    pts = [rng.uniform(lo, hi, size=(140, 3)), rng.uniform(lo - 1.5, hi + 1.5, size=(24, 3))]
-    for ax in range(3):
-        for face, sign in ((lo[ax], 1.0), (hi[ax], -1.0)):
-            p = rng.uniform(lo, hi, size=(6, 3))
-            p[:, ax] = face + sign * rng.uniform(-0.9, 0.9, size=6) * MRES
-            pts.append(p)
-    return np.concatenate(pts)
+# (the map, its clouds and points: tests/esdf_scene.py)
 
 
 def test_rasteriser_bytes_equal_the_reference(gpu_ctx):
@@ -132,52 +107,15 @@ def test_rasteriser_bytes_equal_the_reference(gpu_ctx):
         assert np.array_equal(m.read(sq_pos=False, sq_neg=False, dist=False)["occ"], E.rasterize(DIMS, ORIGIN, MRES, cloud, 2, 1)[0])
 
 
-def pillar_points(seed=5):
-    """eight vertical pillars inside the region the trajectories fly through"""
-    rng = np.random.default_rng(seed)
-    xy = rng.uniform((-3.5, -2.5), (3.5, 2.5), size=(8, 2))
-    z = np.arange(0.13, 4.2, 0.21)
-    return np.concatenate([np.column_stack([np.full(z.size, x), np.full(z.size, y), z]) for x, y in xy])
-
-
-@functools.lru_cache(maxsize=None)
-def scene_reference():
-    occ, margin = E.rasterize(DIMS, ORIGIN, MRES, pillar_points(), 1, 1)
-    assert margin >= 1e-6
-    return occ, E.field(occ, MRES, MMAX)
-
-
 @pytest.fixture(scope="module")
 def scene(gpu_ctx):
     """the map of the query / penalty / autograd tests, built on the device from the pillar cloud; checked against the reference once"""
-    occ, ref = scene_reference()
-    m = EsdfMap(gpu_ctx, DIMS, ORIGIN, MRES, MMAX)
-    m.set_cloud(pillar_points(), inflate_xy=1, inflate_z=1)
-    m.update()
-    got = m.read()
-    assert np.array_equal(got["occ"], occ) and np.array_equal(got["sq_pos"], ref["sq_pos"]) and np.array_equal(got["sq_neg"], ref["sq_neg"])
-    yield m, ref["dist"]
+    m, ref_dist = S.build_scene(gpu_ctx)
+    yield m, ref_dist
     m.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------- query
-def query_points(seed=21):
-    rng = np.random.default_rng(seed)
-    lo, hi = np.array(ORIGIN), np.array(HI)
-    pts = [rng.uniform(lo + 2e-4, hi - 2e-4, size=(4096, 3))]
-    out = rng.uniform(lo - 1.0, hi + 1.0, size=(64, 3))
-    ax = rng.integers(0, 3, size=64)
-    side = rng.random(64) < 0.5
-    out[np.arange(64), ax] = np.where(side, lo[ax] - rng.uniform(0.01, 1.0, size=64), hi[ax] + rng.uniform(0.01, 1.0, size=64))
-    pts.append(out)
-    for a in range(3):
-        for face, sign in ((lo[a], 1.0), (hi[a], -1.0)):
-            p = rng.uniform(lo + 2e-4, hi - 2e-4, size=(64, 3))
-            p[:, a] = face + sign * rng.uniform(0.002, 0.498, size=64) * MRES     # within half a voxel of the face: a clamped corner
-            pts.append(p)
-    return np.concatenate(pts)
-
-
 def test_query_against_the_reference_and_host_equals_device(gpu_ctx, scene):
     torch, _ = dev()
     m, ref_dist = scene
@@ -210,37 +148,40 @@ def test_query_against_the_reference_and_host_equals_device(gpu_ctx, scene):
     assert _lib.lib().uavqp_esdf_query_device(gpu_ctx._h, m.handle, pts.shape[0], d_pts.data_ptr(), None, None, None) == _lib.UAVQP_OK
 
 
+def test_query_on_a_map_written_by_two_blocks_per_row(gpu_ctx):
+    """(3, 100, 100): every z row of the field was written by two blocks of the y pass (z < 81 and z >= 81) -- the reads of the query and
+    of the penalty against such a map.  The margins and the tolerance of the query test above."""
+    torch, _ = dev()
+    q = S.TILED_QUERY
+    assert S.launch_shape(q["dims"])["y"][2] == 2
+    ref = transform_reference(q["dims"], q["variant"])
+    pts = S.tiled_query_points()
+    assert pts.shape == (512, 3)
+    want = E.query(ref["dist"], q["origin"], RES, pts)
+    assert want["margin"].min() >= 1e-6, f"a point sits on a discontinuity (margin {float(want['margin'].min()):.2e}): pick another seed"
+    assert np.count_nonzero(want["inside"] == 0) == 48
+    hi_z = pts[:, 2] >= q["origin"][2] + 81.5 * RES      # both corners in z lie in the second tile
+    assert np.count_nonzero(hi_z & (want["inside"] == 1)) >= 40 and np.count_nonzero(~hi_z & (want["inside"] == 1)) >= 200
+    with EsdfMap(gpu_ctx, q["dims"], q["origin"], RES, MAXD) as m:
+        m.set_occupancy(occupancy(q["dims"], q["variant"]))
+        m.update()
+        d_pts = up(pts)
+        torch.cuda.synchronize()
+        dist, grad, inside = m.query(d_pts)
+        gpu_ctx.synchronize()
+        dist, grad, inside = dist.cpu().numpy(), grad.cpu().numpy(), inside.cpu().numpy()
+    assert np.array_equal(inside, want["inside"])
+    scale = np.maximum(want["scale"], LD(RES))
+    e_d = float(np.max(np.abs(dist.astype(LD) - want["dist"]) / scale))
+    e_g = float(np.max(np.abs(grad.astype(LD) - want["grad"]) * LD(RES) / scale[:, None]))
+    print(f"tiled query: dist {e_d:.3e}, grad * res {e_g:.3e} of max(|corner values|, res)")
+    assert e_d <= 1e-13 and e_g <= 1e-13
+    out = want["inside"] == 0
+    assert dist[out].tobytes() == bytes(8 * 48) and grad[out].tobytes() == bytes(24 * 48)
+    assert np.count_nonzero(np.abs(want["grad"]).sum(axis=1) > 0) > 400
+
+
 # ---------------------------------------------------------------------------------------------------------------- penalty
-PARAMS = dict(samples_per_seg=6, d_safe=0.6, weight=2e2)
-
-
-def flight_batch(r, uniform, seed):
-    """64 trajectories through the pillars: random walks of 0.6 .. 1.2 m steps at about 1 m/s; every eighth starts at the +x face and
-    flies out of the map.  Uniform: M = 4; ragged: M in {1, 2, 3, 5}."""
-    rng = np.random.default_rng(seed)
-    n = 64
-    Ms = np.full(n, 4) if uniform else rng.choice([1, 2, 3, 5], size=n)
-    if not uniform:
-        Ms[:4] = [1, 2, 3, 5]
-    so = np.zeros(n + 1, dtype=np.int32)
-    so[1:] = np.cumsum(Ms)
-    wps, T = [], []
-    for b in range(n):
-        M = int(Ms[b])
-        p = rng.uniform((-3.8, -2.8, 0.8), (3.8, 2.8, 3.2))
-        d = rng.normal(size=(M, 3)) * np.array([1.0, 1.0, 0.3])
-        if b % 8 == 7:
-            p[0] = 4.6
-            d[:, 0] = np.abs(d[:, 0]) + 1.0
-        step = rng.uniform(0.6, 1.2, size=M)
-        d = d / np.linalg.norm(d, axis=1)[:, None] * step[:, None]
-        wps.append(np.vstack([p, p + np.cumsum(d, axis=0)]))
-        T.append(step * rng.uniform(0.8, 1.25, size=M))
-    bc = np.zeros((n, 2, r - 1, 3))
-    bc[:, 0, 0] = rng.uniform(-0.5, 0.5, size=(n, 3))
-    return dict(r=r, n=n, so=so, wp=np.vstack(wps), T=np.concatenate(T), bc=bc, uni=4 if uniform else 0, mmax=int(Ms.max()))
-
-
 class Flight:
     """one batch solved on the device, and the clearance penalty through the device-pointer entry"""
 
@@ -274,6 +215,22 @@ KEYS = ("phi", "grad_coeff", "grad_times", "min_dist", "outside")
 PENALTY_CASES = [(3, True, 31), (4, True, 32), (3, False, 33), (4, False, 34)]
 
 
+def penalty_errors(f, got, ref):
+    """-> dict output -> the largest error relative to the per-trajectory largest magnitude of that output"""
+    nc3 = 3 * 2 * f.r
+    worst = {}
+    for t in range(f.n):
+        s0, s1 = int(f.so[t]), int(f.so[t + 1])
+        for key, sl in (("phi", slice(t, t + 1)), ("grad_coeff", slice(nc3 * s0, nc3 * s1)), ("grad_times", slice(s0, s1)),
+                        ("min_dist", slice(t, t + 1))):
+            want = ref[key][sl]
+            have = got[key][sl].astype(LD)
+            scale = np.max(np.abs(want))
+            err = float(np.max(np.abs(have - want)) / scale) if scale > 0 else float(np.max(np.abs(have)))
+            worst[key] = max(worst.get(key, 0.0), err)
+    return worst
+
+
 @pytest.mark.parametrize("r,uniform,seed", PENALTY_CASES, ids=[f"r{r}-{'uniform' if u else 'ragged'}" for r, u, _ in PENALTY_CASES])
 def test_clearance_penalty_against_the_reference(gpu_ctx, scene, r, uniform, seed):
     m, ref_dist = scene
@@ -288,16 +245,7 @@ def test_clearance_penalty_against_the_reference(gpu_ctx, scene, r, uniform, see
     got = dict(zip(KEYS, (x.cpu().numpy() for x in out)))
     assert np.array_equal(got["outside"].astype(np.int64), ref["outside"])
     nc3 = 3 * 2 * r
-    worst = {}
-    for t in range(f.n):
-        s0, s1 = int(f.so[t]), int(f.so[t + 1])
-        for key, sl in (("phi", slice(t, t + 1)), ("grad_coeff", slice(nc3 * s0, nc3 * s1)), ("grad_times", slice(s0, s1)),
-                        ("min_dist", slice(t, t + 1))):
-            want = ref[key][sl]
-            have = got[key][sl].astype(LD)
-            scale = np.max(np.abs(want))
-            err = float(np.max(np.abs(have - want)) / scale) if scale > 0 else float(np.max(np.abs(have)))
-            worst[key] = max(worst.get(key, 0.0), err)
+    worst = penalty_errors(f, got, ref)
     print(f"r={r} uniform={uniform}: {np.count_nonzero(ref['phi'] > 0)} penalised, {np.count_nonzero(ref['outside'] > 0)} leave the map; max error "
           "relative to the per-trajectory largest magnitude: " + ", ".join(f"{k} {v:.3e}" for k, v in worst.items()))
     for k, v in worst.items():
@@ -334,6 +282,34 @@ def test_clearance_penalty_against_the_reference(gpu_ctx, scene, r, uniform, see
         assert h.tobytes() == got[k].tobytes(), k
 
 
+@pytest.mark.parametrize("r", [3, 4])
+def test_clearance_penalty_second_segment_of_a_sub_lane_and_a_ragged_tail(gpu_ctx, scene, r):
+    """13 trajectories, M from {1, 9, 11, 16, 17}: sub-lane j owns segments j, j + 8, j + 16, and the last lane group sits in a partly
+    filled wave.  The conditions are counted against the 13 (tests/test_esdf_contract.py checks the seeds on the CPU solve)."""
+    m, ref_dist = scene
+    b = S.long_flight_batch(r)
+    f = Flight(gpu_ctx, b)
+    c = f.coeff.cpu().numpy()
+    ref = E.penalty(r, f.so, b["T"], c, ref_dist, ORIGIN, MRES, MMAX, **PARAMS)
+    assert S.long_batch_qualifies(b, ref) == []
+    out = f.penalty(m)
+    got = dict(zip(KEYS, (x.cpu().numpy() for x in out)))
+    assert np.array_equal(got["outside"].astype(np.int64), ref["outside"])
+    worst = penalty_errors(f, got, ref)
+    print(f"r={r} M in {S.LONG_MS}: {np.count_nonzero(ref['phi'] > 0)} penalised, {np.count_nonzero(ref['outside'] > 0)} leave the map; max "
+          "error relative to the per-trajectory largest magnitude: " + ", ".join(f"{k} {v:.3e}" for k, v in worst.items()))
+    for k, v in worst.items():
+        assert v <= PARITY, f"{k}: {v:.3e}"
+    # a segment nobody penalises holds zeros, not the sentinel: every element of both gradients was written
+    assert not np.any(np.isnan(got["grad_coeff"])) and not np.any(np.isnan(got["grad_times"]))
+    # run to run, and through the host entry: the same bytes
+    for p, full in zip(f.penalty(m), out):
+        assert p.cpu().numpy().tobytes() == full.cpu().numpy().tobytes()
+    host = gpu_ctx.clearance_penalty_host(r, f.so, b["T"], c, m, uniform_segments=0, status=f.status.cpu().numpy(), **PARAMS)
+    for h, k in zip(host, KEYS):
+        assert h.tobytes() == got[k].tobytes(), k
+
+
 def test_clearance_penalty_of_empty_trajectories_is_zero(gpu_ctx, scene):
     """M = 0 among valid neighbours: zeros, min_dist = max_dist, outside = 0, every element written"""
     torch, d = dev()
@@ -356,29 +332,49 @@ def test_clearance_penalty_of_empty_trajectories_is_zero(gpu_ctx, scene):
     assert pen[keep].tobytes() == full[0].tobytes() and md[keep].tobytes() == full[3].tobytes() and outs[keep].tobytes() == full[4].tobytes()
 
 
+def guard_bands_of(gpu_ctx, m, b, penalised):
+    """one batch solved and penalised inside the arena, grad_coeff misaligned by 8 bytes; the query on its waypoints"""
+    from test_gpu_guard_bands import _both_fills
+    r = b["r"]
+    tot = int(b["so"][-1])
+
+    def run_clearance(ar):
+        d_so, wp, T, bc = ar.put(b["so"]), ar.put(b["wp"]), ar.put(b["T"]), ar.put(b["bc"])
+        co, st = ar.out(tot * 6 * r), ar.out(b["n"], np.int32)
+        gpu_ctx.solve_batch_device(r, b["n"], b["uni"], b["mmax"], d_so, wp, T, bc, co, st)
+        pen, g_c, g_t = ar.out(b["n"]), ar.out(tot * 6 * r, misalign=8), ar.out(tot)
+        md, outs = ar.out(b["n"]), ar.out(b["n"], np.int32)
+        gpu_ctx.clearance_penalty_device(r, b["n"], b["uni"], d_so, T, co, m, status=st, penalty=pen, grad_coeff=g_c, grad_times=g_t,
+                                         min_dist=md, outside=outs, **PARAMS)
+        pts, q_d, q_g, q_in = ar.put(b["wp"]), ar.out(b["wp"].shape[0]), ar.out(b["wp"].shape), ar.out(b["wp"].shape[0], np.uint8)
+        _lib.check(_lib.lib().uavqp_esdf_query_device(gpu_ctx._h, m.handle, b["wp"].shape[0], pts.data_ptr(), q_d.data_ptr(), q_g.data_ptr(),
+                                                      q_in.data_ptr()), "uavqp_esdf_query_device")
+        return {"pen": pen, "g_c": g_c, "g_t": g_t, "md": md, "outs": outs, "q_d": q_d, "q_g": q_g, "q_in": q_in}
+    got = _both_fills(run_clearance)
+    assert np.count_nonzero(got["pen"] > 0) >= penalised
+    return got
+
+
 def test_clearance_penalty_guard_bands(gpu_ctx, scene):
     """every input and output between sentinel bands, ragged and uniform, one output misaligned to 8 bytes: bands intact, results
     independent of what lies outside the buffers (the arena of tests/test_gpu_guard_bands.py)"""
-    from test_gpu_guard_bands import _both_fills
     m, _ = scene
     for r, uniform, seed in ((4, False, 34), (3, True, 31)):
-        b = flight_batch(r, uniform, seed)
-        tot = int(b["so"][-1])
+        guard_bands_of(gpu_ctx, m, flight_batch(r, uniform, seed), penalised=8)
 
-        def run_clearance(ar):
-            d_so, wp, T, bc = ar.put(b["so"]), ar.put(b["wp"]), ar.put(b["T"]), ar.put(b["bc"])
-            co, st = ar.out(tot * 6 * r), ar.out(b["n"], np.int32)
-            gpu_ctx.solve_batch_device(r, b["n"], b["uni"], b["mmax"], d_so, wp, T, bc, co, st)
-            pen, g_c, g_t = ar.out(b["n"]), ar.out(tot * 6 * r, misalign=8), ar.out(tot)
-            md, outs = ar.out(b["n"]), ar.out(b["n"], np.int32)
-            gpu_ctx.clearance_penalty_device(r, b["n"], b["uni"], d_so, T, co, m, status=st, penalty=pen, grad_coeff=g_c, grad_times=g_t,
-                                             min_dist=md, outside=outs, **PARAMS)
-            pts, q_d, q_g, q_in = ar.put(b["wp"]), ar.out(b["wp"].shape[0]), ar.out(b["wp"].shape), ar.out(b["wp"].shape[0], np.uint8)
-            _lib.check(_lib.lib().uavqp_esdf_query_device(gpu_ctx._h, m.handle, b["wp"].shape[0], pts.data_ptr(), q_d.data_ptr(), q_g.data_ptr(),
-                                                          q_in.data_ptr()), "uavqp_esdf_query_device")
-            return {"pen": pen, "g_c": g_c, "g_t": g_t, "md": md, "outs": outs, "q_d": q_d, "q_g": q_g, "q_in": q_in}
-        got = _both_fills(run_clearance)
-        assert np.count_nonzero(got["pen"] > 0) >= 8
+
+@pytest.mark.parametrize("r", [3, 4])
+def test_clearance_penalty_guard_bands_with_a_second_segment_per_sub_lane(gpu_ctx, scene, r):
+    """the same on the 13 trajectories of M from {1, 9, 11, 16, 17}: the unaligned stores of grad_coeff for segments j + 8, j + 16.  The
+    arena's outputs start as zeros, so what the 8-byte path stored is also compared with the 16-byte path's bytes of a plain call (the
+    two differ in the width of the loads and stores, not in the arithmetic)."""
+    m, _ = scene
+    b = S.long_flight_batch(r)
+    got = guard_bands_of(gpu_ctx, m, b, penalised=4)
+    plain = [x.cpu().numpy() for x in Flight(gpu_ctx, b).penalty(m)]
+    for k, want in zip(("pen", "g_c", "g_t", "md", "outs"), plain):
+        assert got[k].tobytes() == want.tobytes(), k
+    assert np.count_nonzero(got["g_c"].reshape(-1, 2 * r)[np.concatenate([np.tile(np.arange(M) >= 8, 3) for M in np.diff(b["so"])])]) > 0
 
 
 # ---------------------------------------------------------------------------------------------------------------- autograd
