@@ -719,7 +719,8 @@ int uavqp_flight_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_seg
  * uavqp_time_optimize_limits_device with uavqp_waypoint_optimize_device, which re-scales at every call, ended lower with the same number of
  * solves; a second call of this entry re-scales too.  The hard tests remain uavqp_time_reallocate_device (limits: it
  * then has far less to stretch) and uavqp_ellipsoid_check_* (collisions).
- * Out of scope: corridor and general-rows solves, capture into a graph, multi-GPU (shard the batch as for the solve), quasi-Newton directions. */
+ * Out of scope: corridor and general-rows solves, capture into a graph, multi-GPU (shard the batch as for the solve).  Quasi-Newton
+ * directions: uavqp_spacetime_lbfgs_device below. */
 typedef struct uavqp_spacetime_params {
     int32_t struct_size;
     int32_t max_iters;          /* trials per trajectory (default 32) */ 
@@ -747,6 +748,77 @@ int uavqp_spacetime_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform
                                   const uavqp_clearance_params* clearance, const uavqp_spacetime_params* params, double* coeff_out,
                                   int32_t* status_out, double* objective_out, int32_t* accepted_out, double* peak_out, double* min_dist_out,
                                   int32_t* outside_out);
+
+/* The same joint optimisation with LIMITED-MEMORY BFGS directions, kept per trajectory on the device: the objective f, the variables, the
+ * bounds, the gradients, every argument and output, the projection of the durations before the first solve, the treatment of trajectories
+ * that are not UAVQP_SOLVED at the start or have M = 1, the meaning of d_objective_out / d_accepted_out / d_peak_out / d_min_dist_out /
+ * d_outside_out and the rule "d_coeff_out is bit for bit the plain solve at what is handed back" are those of
+ * uavqp_spacetime_optimize_device above.  Only the direction of a trial differs.  Per trajectory:
+ * Variables.  x = (p_k[axis] / initial_step_move for the interior knots k, log T_i / initial_step_log): the units in which the first step
+ * of either block has length one.  g = (initial_step_move df/dp_k[axis], initial_step_log T_i df/dT_i), df/dp and df/dT as above.  lo, hi:
+ * the box and [log t_min, log t_max] in these units.  The device keeps p and T themselves: a trial is formed as
+ *       p_t = clamp(p + alpha initial_step_move d^p),  T_t = clamp(T exp(alpha initial_step_log d^u))            (d in x)
+ * and x_t - x = ((p_t - p) / initial_step_move, log(T_t / T) / initial_step_log), so a component whose d is zero keeps its bytes.
+ * Free set at the best point: component i is BLOCKED when x_i <= lo_i and g_i > 0, or x_i >= hi_i and g_i < 0.
+ * Gradient mode (at the start, and after every reset).  The direction of uavqp_spacetime_optimize_device: d^p_k = (df/dp_k) / s_k, d^u_i =
+ * T_i df/dT_i, blocked components zero; sigma_p = initial_step_move / max |d^p|, sigma_u = initial_step_log / max |d^u| (0 when the
+ * maximum is 0 or not finite), computed AT THE CURRENT BEST POINT EVERY TIME THE MODE IS ENTERED; alpha = 1 on entry (0 when both scales
+ * are 0).  Trial: p_t = clamp(p - alpha sigma_p d^p), T_t = clamp(T exp(-alpha sigma_u d^u)), the directions taken at the best point.
+ * Accepted: alpha *= grow, rejected: alpha *= shrink.  With max_iters = 1 every output is that of uavqp_spacetime_optimize_device.
+ * Quasi-Newton mode (whenever at least one pair is stored, after an accepted trial).  The two-loop recursion over the stored pairs (s_j,
+ * y_j), newest to oldest and back, started at q = g; the blocked components of g, s_j and y_j count as zero in every dot product and
+ * every update; a pair whose masked s_j . y_j is not positive is skipped; H0 = gamma I with gamma = s . y / y . y of the NEWEST pair,
+ * masked the same way.  d = minus the result, blocked components zero; alpha = 1 for every new direction.  If gamma is not positive and
+ * finite, or unless g_F . d < -1e-10 |g_F| |d| (g_F: g with its blocked components zero), the memory is cleared and gradient mode is
+ * entered at this point.
+ * Trial: accepted iff alpha > 0, its solve ends UAVQP_SOLVED and  f_t <= f - armijo_c * g . (x - x_t), i.e.
+ *       f_t <= f - armijo_c * [ sum_k (df/dp_k) . (p_k - p_t,k) + sum_i T_i (df/dT_i) log(T_i / T_t,i) ]
+ * (the rule of uavqp_spacetime_optimize_device in these units).  ONE accept / reject per trajectory and trial; f never increases.
+ * Accepted: s = x_t - x, y = g_t - g (NOT masked); the pair is stored iff s . y > curvature_eps |s| |y|; the memory holds the `memory`
+ * newest pairs.  The next direction is quasi-Newton if the memory is not empty; otherwise gradient mode goes on (alpha *= grow, the
+ * scales stay).
+ * Rejected: alpha *= shrink, the direction stays.  In quasi-Newton mode, after max_backtracks consecutive rejections the memory is cleared
+ * and gradient mode is entered at the best point.
+ * Sequencing, cost per trial (four launches), determinism and asynchrony as above; the history (memory + 1 slots of s and y per
+ * trajectory) lives in the workspace the first call of a given size allocates.
+ *   params   uavqp_default_spacetime_lbfgs_params fills the defaults: max_iters 32, memory 8, max_backtracks 6, curvature_eps 1e-10
+ *            (DESIGN.md section 5.21), every other field as uavqp_default_spacetime_params.  UAVQP_ERR_INVALID_ARG for a wrong
+ *            struct_size, whatever uavqp_spacetime_optimize_device refuses in a field of the same name, memory outside 1 .. 16,
+ *            max_backtracks outside 1 .. 64, curvature_eps outside [0, 1) or not a number.
+ * WHAT THE RESULT IS: as above, a local minimum of a piecewise smooth f with soft penalties.  On the test batches 32 trials leave 1e-3 of
+ * the decrease scipy's L-BFGS-B reaches, against 2e-2 for uavqp_spacetime_optimize_device.
+ * Out of scope: a Wolfe line search (one trial per iteration keeps the launch count fixed), corridor and general-rows solves, capture into
+ * a graph, multi-GPU (shard the batch as for the solve). */
+typedef struct uavqp_spacetime_lbfgs_params {
+    int32_t struct_size;
+    int32_t max_iters;          /* trials per trajectory (default 32) */
+    int32_t memory;             /* stored pairs per trajectory, 1 .. 16 (default 8) */
+    int32_t max_backtracks;     /* consecutive rejections of a quasi-Newton direction before the memory is cleared, 1 .. 64 (default 6) */
+    double smooth_weight;       /* the fields of uavqp_spacetime_params, same meaning, defaults and validity */
+    double time_weight;
+    double t_min;
+    double t_max;
+    double max_move;
+    double initial_step_move;   /* also the unit of the waypoint variables */
+    double initial_step_log;    /* also the unit of the log-duration variables */
+    double armijo_c;
+    double shrink;
+    double grow;                /* (gradient mode only) */
+    double curvature_eps;       /* a pair is stored iff s . y > curvature_eps |s| |y|, in [0, 1) (default 1e-10) */
+} uavqp_spacetime_lbfgs_params;
+void uavqp_default_spacetime_lbfgs_params(uavqp_spacetime_lbfgs_params* out);   /* callable without a device */
+int uavqp_spacetime_lbfgs_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                                 const int32_t* d_seg_offsets, double* d_waypoints, double* d_times, const double* d_bc,
+                                 const uavqp_esdf* esdf, const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
+                                 const uavqp_spacetime_lbfgs_params* params, double* d_coeff_out, int32_t* d_status_out,
+                                 double* d_objective_out, int32_t* d_accepted_out, double* d_peak_out, double* d_min_dist_out,
+                                 int32_t* d_outside_out);
+/* The same from HOST pointers, as uavqp_spacetime_optimize_host. */
+int uavqp_spacetime_lbfgs_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                               double* waypoints, double* times, const double* bc, const uavqp_esdf* esdf, const uavqp_limit_params* limits,
+                               const uavqp_clearance_params* clearance, const uavqp_spacetime_lbfgs_params* params, double* coeff_out,
+                               int32_t* status_out, double* objective_out, int32_t* accepted_out, double* peak_out, double* min_dist_out,
+                               int32_t* outside_out);
 
 /* Batched evaluation of solved trajectories on a uniform time grid.
  * Replaces, for a whole batch, PolyTraj::evaluatePos / evaluateVel / evaluateAcc

@@ -10,6 +10,11 @@
 2. Device time of one fused penalty launch beside the two separate penalty launches: `--launches` launches between two events after a
    warm-up, inputs and outputs rotating through enough sets of buffers to exceed the 256 MB last-level cache where one set is smaller.
 
+3. `--method lbfgs` (instead of 1 and 2): uavqp_spacetime_lbfgs_device beside uavqp_spacetime_optimize_device from the
+   same start, alternating in the same run, at 32 and at 256 trials: wall time per call of both and the median final joint objective of
+   both, next to the hand alternation's at 34 solves (as in 1) -- the comparison recorded in DESIGN.md section 5.20 as 4264 / 832 and
+   1062 / 696.  Under `rocprofv3 --kernel-trace --stats` the same run gives the time of spacetime_lbfgs_step_kernel.
+
 Shapes: 4096 x 8 segments, r = 4 (config 2) in the 200 x 200 x 50 map of tools/waypoint_opt_bench.py, and the ragged 14-trajectory batch of
 tests/test_gpu_spacetime.py (r = 4) in its own scene.  Limits: 0.7 x the batch's sampled peak at the start for config 2, the test's own for
 the test batch.  One JSON line per shape and measurement.  Needs the GPU: there is no CPU path."""
@@ -43,6 +48,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--shape", default=None)
+    ap.add_argument("--method", choices=("gd", "lbfgs"), default="gd", help="lbfgs: measurement 3 alone")
+    ap.add_argument("--trials", type=int, nargs="+", default=[32, 256], help="max_iters of measurement 3")
     args = ap.parse_args()
     import torch
     import spacetime_reference as R
@@ -123,6 +130,50 @@ def main():
                 ctx.synchronize()
                 return time.perf_counter() - t0, s
 
+            if args.method == "lbfgs":
+                # ---- measurement 3: the two joint entries from the same start, alternating; the hand alternation once for its objective
+                def entry(lbfgs, k, max_iters):
+                    s = sets[k % ROT]
+                    s["T"].copy_(d_T0)
+                    s["wp"].copy_(d_wp0)
+                    torch.cuda.synchronize()
+                    fn = ctx.spacetime_lbfgs_device if lbfgs else ctx.spacetime_optimize_device
+                    t0 = time.perf_counter()
+                    fn(r, n, uni, mmax, total, d_so, s["wp"], s["T"], d_bc, m, s["coeff"], s["status"], s["obj"], s["acc"], s["peak"], s["md"],
+                       s["out"], limits=lim, max_iters=max_iters, max_move=move)
+                    ctx.synchronize()
+                    return time.perf_counter() - t0, s
+                _, s_alt = call(False, 0)
+                joint(s_alt, 0)                               # the joint objective at the alternation's result
+                ctx.synchronize()
+                f_alt = s_alt["obj"].cpu().numpy().copy()
+                for trials in args.trials:
+                    reps = args.reps if trials <= 64 else max(3, args.reps // 3)
+                    for k in range(args.warmup):
+                        entry(False, k, trials)
+                        entry(True, k, trials)
+                    t_gd, t_qn = [], []
+                    for k in range(reps):
+                        dt, s_gd = entry(False, 2 * k, trials)
+                        t_gd.append(dt)
+                        f_gd, acc_gd = s_gd["obj"].cpu().numpy().copy(), s_gd["acc"].cpu().numpy().copy()
+                        dt, s_qn = entry(True, 2 * k + 1, trials)
+                        t_qn.append(dt)
+                    f_qn, acc_qn = s_qn["obj"].cpu().numpy().copy(), s_qn["acc"].cpu().numpy().copy()
+                    ok = np.isfinite(f_gd[:, 0]) & np.isfinite(f_qn[:, 0]) & np.isfinite(f_alt[:, 0])
+                    print(json.dumps(dict(measurement=3, shape=name, n_traj=n, segments=total, max_iters=trials, reps=reps, taking_part=int(ok.sum()),
+                                          lbfgs_ms=1e3 * statistics.median(t_qn), lbfgs_ms_min=1e3 * min(t_qn), lbfgs_ms_max=1e3 * max(t_qn),
+                                          gradient_ms=1e3 * statistics.median(t_gd), gradient_ms_min=1e3 * min(t_gd), gradient_ms_max=1e3 * max(t_gd),
+                                          ratio=statistics.median(t_qn) / statistics.median(t_gd),
+                                          median_f_start=float(np.median(f_qn[ok, 0])), median_f_lbfgs=float(np.median(f_qn[ok, 1])),
+                                          median_f_gradient=float(np.median(f_gd[ok, 1])),
+                                          median_f_alternating_34_solves=float(np.median(f_alt[ok, 0])),
+                                          lbfgs_lower_than_gradient_in=int(np.count_nonzero(f_qn[ok, 1] < f_gd[ok, 1])),
+                                          lbfgs_lower_than_alternating_in=int(np.count_nonzero(f_qn[ok, 1] < f_alt[ok, 0])),
+                                          median_accepted_lbfgs=float(np.median(acc_qn[ok])), median_accepted_gradient=float(np.median(acc_gd[ok])),
+                                          lbfgs_peak_v_a_max=[float(x) for x in s_qn["peak"].cpu().numpy()[ok].max(axis=0)],
+                                          lbfgs_min_dist_min=float(s_qn["md"].cpu().numpy()[ok].min()))))
+                continue
             for k in range(args.warmup):
                 call(False, k)
                 call(True, k)

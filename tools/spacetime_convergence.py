@@ -10,6 +10,10 @@ tests/spacetime_reference.py).
     python tools/spacetime_convergence.py --write-golden  the same, and f_start / f_scipy of every trajectory into tests/golden/spacetime_scipy.json
     python tools/spacetime_convergence.py --limits        sampled peaks at scipy's optimum with weight_v = weight_a = 0: the medians are LIMITS_OF[r]
     python tools/spacetime_convergence.py --seed-search   the first seed from 1 per r whose ragged and uniform batches meet the preconditions
+    python tools/spacetime_convergence.py --method lbfgs  the same table for the limited-memory BFGS entry (tests/spacetime_lbfgs_reference.py) after
+                                                          16, 32, 64 and 128 trials against the RECORDED scipy optima, GAP_LBFGS_AT_DEFAULT and its
+                                                          trajectory, the settings memory 4 and max_backtracks 3, and the three feasibility
+                                                          comparisons of the GPU test at 64 trials
 No GPU.
 """
 import argparse
@@ -25,6 +29,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import spacetime_reference as R   # noqa: E402
+import spacetime_lbfgs_reference as Q   # noqa: E402
 from oracle import oracle         # noqa: E402
 
 NO_LIMITS = dict(weight_v=0.0, weight_a=0.0)
@@ -130,8 +135,56 @@ def batches(r):
     return (("ragged", R.cases(r)), ("uniform", R.uniform_cases(r)))
 
 
+def lbfgs_table(rs):
+    """The study of the limited-memory BFGS entry: gaps against the recorded scipy optima, and the feasibility comparisons at 64 trials."""
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "spacetime_scipy.json")))
+    settings = (("memory 8, max_backtracks 6", {}), ("memory 4", dict(memory=4)), ("max_backtracks 3", dict(max_backtracks=3)))
+    d_safe = R.CLEARANCE["d_safe"]
+    for name, kw in settings:
+        print(f"{name}: left after".ljust(44) + " ".join(f"{k:9d}" for k in Q.STEPS) + f"   gradient descent after {R.DEFAULT_MAX_ITERS}")
+        total, at = np.full(len(Q.STEPS), -np.inf), [None] * len(Q.STEPS)
+        for r in rs:
+            for kind, batch in batches(r):
+                n = batch["seg_offsets"].size - 1
+                worst, where, gd, met, n_over, n_close = np.full(len(Q.STEPS), -np.inf), np.zeros(len(Q.STEPS), dtype=int), -np.inf, 0, 0, 0
+                for t in range(n):
+                    rec = golden[f"r{r}-{kind}"][t]
+                    run = Q.iterate_lbfgs(problem(batch, t), Q.STEPS[-1], **kw)
+                    assert abs(run["f_start"] - rec["f_start"]) <= 1e-9 * rec["f_start"], "the recorded results belong to other cases"
+                    left = np.array([(run["history"][k - 1] - rec["f_scipy"]) / (run["f_start"] - rec["f_scipy"]) for k in Q.STEPS])
+                    where = np.where(left > worst, t, where)
+                    worst = np.maximum(worst, left)
+                    if kw:
+                        continue
+                    old = R.iterate(problem(batch, t), R.DEFAULT_MAX_ITERS)
+                    gd = max(gd, (old["f"] - rec["f_scipy"]) / (old["f_start"] - rec["f_scipy"]))
+                    # the three comparisons of the GPU test, all runs at FEASIBILITY_ITERS trials
+                    res = Q.iterate_lbfgs(problem(batch, t), Q.FEASIBILITY_ITERS)
+                    nolim = Q.iterate_lbfgs(problem(batch, t, limits=NO_LIMITS), Q.FEASIBILITY_ITERS)
+                    noclr = Q.iterate_lbfgs(problem(batch, t, clearance=dict(weight=0.0)), Q.FEASIBILITY_ITERS)
+                    over = nolim["peak"] > 1.0
+                    close = problem(batch, t).M > 1 and noclr["min_dist"] < d_safe
+                    fine = (np.all(res["peak"][over] < nolim["peak"][over]) and (not close or res["min_dist"] > noclr["min_dist"])
+                            and res["outside"] == 0 and nolim["outside"] == 0 and noclr["outside"] == 0)
+                    met, n_over, n_close = met + int(fine), n_over + int(over.any()), n_close + int(close)
+                    if not fine:
+                        print(f"  {kind} r={r} t={t}: A FEASIBILITY COMPARISON FAILS at {Q.FEASIBILITY_ITERS} trials: peaks {res['peak']} against "
+                              f"{nolim['peak']}, min_dist {res['min_dist']:.4f} against {noclr['min_dist']:.4f}")
+                print(f"{kind + f' r={r}':44s}" + " ".join(f"{x:9.2e}" for x in worst) + (f"   {gd:9.2e}" if not kw else "")
+                      + ("" if kw else f"   feasibility at {Q.FEASIBILITY_ITERS} trials: {met} of {n} meet all comparisons, {n_over} over a limit, "
+                                       f"{n_close} closer than d_safe without the penalties"))
+                for k in range(len(Q.STEPS)):
+                    if worst[k] > total[k]:
+                        total[k], at[k] = worst[k], (r, kind, int(where[k]))
+        print("worst of all".ljust(44) + " ".join(f"{x:9.2e}" for x in total))
+        if not kw:
+            k = Q.STEPS.index(Q.DEFAULT_MAX_ITERS)
+            print(f"default max_iters = {Q.DEFAULT_MAX_ITERS}: GAP_LBFGS_AT_DEFAULT = {total[k]:.3e} at GAP_LBFGS_CASE = {at[k]}")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--method", choices=("gd", "lbfgs"), default="gd", help="lbfgs: the table of the limited-memory BFGS entry")
     ap.add_argument("--limits", action="store_true")
     ap.add_argument("--seed-search", action="store_true")
     ap.add_argument("--write-golden", action="store_true")
@@ -140,6 +193,10 @@ def main():
     args = ap.parse_args()
     oracle.build()
     t0 = time.time()
+    if args.method == "lbfgs":
+        lbfgs_table(args.r)
+        print(f"({time.time() - t0:.0f} s)")
+        return
     if args.limits:
         for r in (3, 4):
             v, a = [], []

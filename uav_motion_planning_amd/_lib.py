@@ -78,6 +78,9 @@ SYMBOLS = (
     "uavqp_default_spacetime_params",
     "uavqp_spacetime_optimize_device",
     "uavqp_spacetime_optimize_host",
+    "uavqp_default_spacetime_lbfgs_params",
+    "uavqp_spacetime_lbfgs_device",
+    "uavqp_spacetime_lbfgs_host",
     "uavqp_eval_batch_device",
     "uavqp_traj_length_device",
     "uavqp_ellipsoid_check_device",
@@ -166,6 +169,14 @@ class SpacetimeParams(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_int32), ("max_iters", ctypes.c_int32), ("smooth_weight", ctypes.c_double), ("time_weight", ctypes.c_double),
                 ("t_min", ctypes.c_double), ("t_max", ctypes.c_double), ("max_move", ctypes.c_double), ("initial_step_move", ctypes.c_double),
                 ("initial_step_log", ctypes.c_double), ("armijo_c", ctypes.c_double), ("shrink", ctypes.c_double), ("grow", ctypes.c_double)]
+
+
+class SpacetimeLbfgsParams(ctypes.Structure):
+    """uavqp_spacetime_lbfgs_params of include/uavqp.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("max_iters", ctypes.c_int32), ("memory", ctypes.c_int32), ("max_backtracks", ctypes.c_int32),
+                ("smooth_weight", ctypes.c_double), ("time_weight", ctypes.c_double), ("t_min", ctypes.c_double), ("t_max", ctypes.c_double),
+                ("max_move", ctypes.c_double), ("initial_step_move", ctypes.c_double), ("initial_step_log", ctypes.c_double),
+                ("armijo_c", ctypes.c_double), ("shrink", ctypes.c_double), ("grow", ctypes.c_double), ("curvature_eps", ctypes.c_double)]
 
 
 def build(force=False):
@@ -265,6 +276,12 @@ def lib():
                                                   ctypes.POINTER(ClearanceParams), ctypes.POINTER(SpacetimeParams), dp, ip, dp, ip, dp, dp, ip]
     L.uavqp_spacetime_optimize_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(LimitParams),
                                                 ctypes.POINTER(ClearanceParams), ctypes.POINTER(SpacetimeParams), dp, ip, dp, ip, dp, dp, ip]
+    L.uavqp_default_spacetime_lbfgs_params.argtypes = [ctypes.POINTER(SpacetimeLbfgsParams)]
+    L.uavqp_default_spacetime_lbfgs_params.restype = None
+    L.uavqp_spacetime_lbfgs_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(LimitParams),
+                                               ctypes.POINTER(ClearanceParams), ctypes.POINTER(SpacetimeLbfgsParams), dp, ip, dp, ip, dp, dp, ip]
+    L.uavqp_spacetime_lbfgs_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(LimitParams),
+                                             ctypes.POINTER(ClearanceParams), ctypes.POINTER(SpacetimeLbfgsParams), dp, ip, dp, ip, dp, dp, ip]
     L.uavqp_eval_batch_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, i32, dp]
     L.uavqp_traj_length_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ctypes.c_double, dp, dp, ip]
     L.uavqp_ellipsoid_check_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, dp, i32,

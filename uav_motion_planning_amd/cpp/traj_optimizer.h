@@ -285,6 +285,39 @@ class TrajOptimizer {
         for (int32_t s : status_) if (s != UAVQP_SOLVED) return false;
         return true;
     }
+    // The same with limited-memory BFGS directions kept per trajectory on the device (include/uavqp.h uavqp_spacetime_lbfgs_host): the same
+    // objective and bounds, the same members filled, fewer trials to the same objective.  params: null =
+    // uavqp_default_spacetime_lbfgs_params.  (Its own name and not an overload: with both parameter pointers defaulted a call without one
+    // would be ambiguous.)
+    template <class Map>
+    bool optimizeTrajectoryLbfgs(const Map& map, const uavqp_limit_params& limits, const uavqp_clearance_params& clearance,
+                                 const uavqp_spacetime_lbfgs_params* params = nullptr) {
+        if (n_traj_ <= 0 || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_])) return false;
+        if (!lo_.empty() || rows_k_ > 0) {
+            std::cout << "solver solve failed! (optimizeTrajectoryLbfgs: corridor and general-rows problems are out of scope)" << std::endl;
+            return false;
+        }
+        if (!ensureContext()) return false;
+        if (bc_.empty()) bc_.assign(static_cast<size_t>(n_traj_) * 2 * (order_ - 1) * 3, 0.0);
+        uavqp_spacetime_lbfgs_params pp;
+        if (params) pp = *params; else uavqp_default_spacetime_lbfgs_params(&pp);
+        coef_.assign(static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_], 0.0);
+        status_.assign(n_traj_, 0);
+        objective_.assign(static_cast<size_t>(2) * n_traj_, 0.0);
+        accepted_.assign(n_traj_, 0);
+        peak_.assign(static_cast<size_t>(2) * n_traj_, 0.0);
+        min_dist_.assign(n_traj_, 0.0);
+        outside_.assign(n_traj_, 0);
+        const int rc = uavqp_spacetime_lbfgs_host(ctx_, order_, n_traj_, 0, 0, seg_offsets_.data(), wp_.data(), T_.data(), bc_.data(), map.handle(),
+                                                  &limits, &clearance, &pp, coef_.data(), status_.data(), objective_.data(), accepted_.data(),
+                                                  peak_.data(), min_dist_.data(), outside_.data());
+        if (rc != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            return false;
+        }
+        for (int32_t s : status_) if (s != UAVQP_SOLVED) return false;
+        return true;
+    }
     // Limit penalty + clearance penalty per trajectory of the stored coefficients at the stored durations, in one launch
     // (uavqp_flight_penalty_host).  A trajectory that did not solve carries zero.  Empty on failure.
     template <class Map>

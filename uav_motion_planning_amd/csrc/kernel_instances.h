@@ -128,3 +128,9 @@
     UAVQP_INST __global__ void uavqp::spacetime_step_kernel<R_, true>(uavqp::SpacetimeArgs);       \
     UAVQP_INST __global__ void uavqp::spacetime_step_kernel<R_, false>(uavqp::SpacetimeArgs);
 #define UAVQP_INSTANCES_SPACETIME UAVQP_SPACETIME_R(3) UAVQP_SPACETIME_R(4)
+
+// ---- qp_spacetime_lbfgs.h: the step of the joint optimiser with limited-memory BFGS directions
+#define UAVQP_SPACETIME_LBFGS_R(R_)                                                                        \
+    UAVQP_INST __global__ void uavqp::spacetime_lbfgs_step_kernel<R_, true>(uavqp::SpacetimeLbfgsArgs);       \
+    UAVQP_INST __global__ void uavqp::spacetime_lbfgs_step_kernel<R_, false>(uavqp::SpacetimeLbfgsArgs);
+#define UAVQP_INSTANCES_SPACETIME_LBFGS UAVQP_SPACETIME_LBFGS_R(3) UAVQP_SPACETIME_LBFGS_R(4)

@@ -37,6 +37,7 @@
 #include "qp_esdf.h"
 #include "qp_waypoint_opt.h"
 #include "qp_spacetime.h"
+#include "qp_spacetime_lbfgs.h"
 // Measured-slower alternatives kept as bit-identical cross-checks: `make experiments` (-DUAVQP_EXPERIMENTS) only
 #ifdef UAVQP_EXPERIMENTS
 #include "cloud_grid2d.h"
@@ -66,6 +67,7 @@ UAVQP_INSTANCES_LIMITS
 UAVQP_INSTANCES_ESDF
 UAVQP_INSTANCES_WPOPT
 UAVQP_INSTANCES_SPACETIME
+UAVQP_INSTANCES_SPACETIME_LBFGS
 #endif
 
 namespace uavqp {
@@ -1946,6 +1948,7 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
 // Fused flight penalty (limits + clearance) and the joint optimiser of waypoints and durations
 // ===================================================================================================
 #include "uavqp_spacetime.h"
+#include "uavqp_spacetime_lbfgs.h"
 
 // ===================================================================================================
 // N3: quadrotor_msgs/PolynomialTrajectory packer (host only)

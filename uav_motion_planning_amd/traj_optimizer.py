@@ -395,6 +395,56 @@ class Context:
         _lib.check(rc, "uavqp_spacetime_optimize_host")
         return waypoints, times, coeff, status, objective, accepted, peak, min_dist, outside
 
+    @staticmethod
+    def _spacetime_lbfgs_params(params):
+        pp = _lib.SpacetimeLbfgsParams()
+        _lib.lib().uavqp_default_spacetime_lbfgs_params(ctypes.byref(pp))
+        for k, v in params.items():
+            if not hasattr(pp, k) or k == "struct_size":
+                raise ValueError(f"unknown uavqp_spacetime_lbfgs_params field {k!r}")
+            setattr(pp, k, v)
+        return pp
+
+    def spacetime_lbfgs_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc, esdf,
+                               coeff_out, status_out, objective_out, accepted_out=None, peak_out=None, min_dist_out=None, outside_out=None,
+                               limits=None, clearance=None, **params):
+        """uavqp_spacetime_lbfgs_device on device buffers: spacetime_optimize_device with limited-memory BFGS directions kept per
+        trajectory on the device -- the same objective, bounds, arguments and outputs, fewer trials to the same objective.  params: fields
+        of uavqp_spacetime_lbfgs_params that differ from the defaults (memory, max_backtracks and curvature_eps besides those of
+        uavqp_spacetime_params).  Asynchronous."""
+        pp = self._spacetime_lbfgs_params(params)
+        lp, cp = self._limit_params(limits or {}), self._clearance_params(clearance or {})
+        rc = _lib.lib().uavqp_spacetime_lbfgs_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), _ptr(seg_offsets),
+                                                     _ptr(waypoints), _ptr(times), _ptr(bc), getattr(esdf, "handle", esdf), ctypes.byref(lp),
+                                                     ctypes.byref(cp), ctypes.byref(pp), _ptr(coeff_out), _ptr(status_out), _ptr(objective_out),
+                                                     _ptr(accepted_out), _ptr(peak_out), _ptr(min_dist_out), _ptr(outside_out))
+        _lib.check(rc, "uavqp_spacetime_lbfgs_device")
+
+    def spacetime_lbfgs_host(self, r, seg_offsets, waypoints, times, bc, esdf, uniform_segments=0, limits=None, clearance=None, **params):
+        """numpy in / numpy out (synchronous; the map stays on the device).  Returns what spacetime_optimize_host returns."""
+        waypoints = np.array(waypoints, dtype=np.float64).reshape(-1, 3)   # copies: the call updates both in place
+        times = np.array(times, dtype=np.float64).ravel()
+        bc = np.ascontiguousarray(bc, dtype=np.float64)
+        so, n_traj, total, mmax = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total
+        assert waypoints.size == 3 * (total + n_traj), "waypoints must hold sum(M_b + 1) xyz rows"
+        assert bc.size == n_traj * 2 * (r - 1) * 3
+        pp = self._spacetime_lbfgs_params(params)
+        lp, cp = self._limit_params(limits or {}), self._clearance_params(clearance or {})
+        coeff = np.zeros(3 * 2 * r * total, dtype=np.float64)
+        status = np.zeros(n_traj, dtype=np.int32)
+        objective = np.zeros((n_traj, 2), dtype=np.float64)
+        accepted = np.zeros(n_traj, dtype=np.int32)
+        peak = np.zeros((n_traj, 2), dtype=np.float64)
+        min_dist = np.zeros(n_traj, dtype=np.float64)
+        outside = np.zeros(n_traj, dtype=np.int32)
+        rc = _lib.lib().uavqp_spacetime_lbfgs_host(self._h, r, n_traj, uniform_segments, max(mmax, 1), _ptr(so), _ptr(waypoints), _ptr(times),
+                                                   _ptr(bc), getattr(esdf, "handle", esdf), ctypes.byref(lp), ctypes.byref(cp), ctypes.byref(pp),
+                                                   _ptr(coeff), _ptr(status), _ptr(objective), _ptr(accepted), _ptr(peak), _ptr(min_dist),
+                                                   _ptr(outside))
+        _lib.check(rc, "uavqp_spacetime_lbfgs_host")
+        return waypoints, times, coeff, status, objective, accepted, peak, min_dist, outside
+
     def time_optimize_limits_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc,
                                     coeff_out, status_out, objective_out, accepted_out=None, peak_out=None, limits=None, **params):
         """uavqp_time_optimize_limits_device on device buffers: time_optimize_device with the limit penalty inside the objective
@@ -770,6 +820,7 @@ class TrajOptimizer:
                                      minimise smooth_weight * cost + time_weight * sum T + limit penalty + clearance penalty
                                      (uavqp_spacetime_optimize_host); stores waypoints, durations and coefficients; .objective,
                                      .iterations, .peak, .min_dist, .outside as above
+    optimizeTrajectoryLbfgs(esdf, ...)   the same with limited-memory BFGS directions kept on the device (uavqp_spacetime_lbfgs_host)
     getFlightPenalty(esdf, ...)      [n_traj] limit + clearance penalty of the stored coefficients in one launch
     getCostWaypointGradient()        [sum (M_b + 1)][3] gradient of getCost() in the waypoints, both ends of every trajectory included
     backward(grad_coeff)             equality-constrained problems only, after solve(): (grad_times, grad_waypoints, grad_bc) of a loss
@@ -920,6 +971,24 @@ class TrajOptimizer:
         ctx = self.context()
         (self._wp, self._T, self._coef, self.status, self.objective, self.iterations, self.peak, self.min_dist,
          self.outside) = ctx.spacetime_optimize_host(self._r, self._so, self._wp, self._T, bc, esdf, limits=limits, clearance=clearance, **params)
+        return bool(np.all(self.status == _lib.UAVQP_SOLVED))
+
+    def optimizeTrajectoryLbfgs(self, esdf, limits=None, clearance=None, **params):
+        """optimizeTrajectory with limited-memory BFGS directions (uavqp_spacetime_lbfgs_host): the same objective, bounds and members
+        filled, fewer trials to the same objective.  params: fields of uavqp_spacetime_lbfgs_params that differ from the defaults (an
+        unknown field raises ValueError)."""
+        if self._lo is not None or self._rows is not None:
+            raise ValueError("optimizeTrajectoryLbfgs: corridor and general-rows problems are out of scope (include/uavqp.h)")
+        Context._spacetime_lbfgs_params(params)   # (an unknown field is refused before anything runs)
+        if self._wp is None or self._T is None:
+            return False
+        n_traj = self._so.size - 1
+        if self._T.size != int(self._so[-1]):
+            return False
+        bc = self._bc if self._bc is not None else np.zeros((n_traj, 2, self._r - 1, 3))
+        ctx = self.context()
+        (self._wp, self._T, self._coef, self.status, self.objective, self.iterations, self.peak, self.min_dist,
+         self.outside) = ctx.spacetime_lbfgs_host(self._r, self._so, self._wp, self._T, bc, esdf, limits=limits, clearance=clearance, **params)
         return bool(np.all(self.status == _lib.UAVQP_SOLVED))
 
     def getFlightPenalty(self, esdf, limits=None, clearance=None):
