@@ -820,6 +820,72 @@ int uavqp_spacetime_lbfgs_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_se
                                int32_t* status_out, double* objective_out, int32_t* accepted_out, double* peak_out, double* min_dist_out,
                                int32_t* outside_out);
 
+/* Swarm separation penalty: reciprocal avoidance between the vehicles of one swarm, compared at the same instant on a clock the swarm
+ * shares, with its gradients in the coefficients, the durations and the departure times (no reference counterpart: its multi_agents.launch
+ * is namespacing only; the term is that of EGO-Swarm / MINCO-swarm).  It is the one penalty here that couples trajectories.
+ * The batch is described as everywhere else (r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff, d_status), and in addition
+ *   n_groups, d_group_offsets [n_groups + 1] int32, ascending from 0 to n_traj: swarm g is the trajectories b in [go[g], go[g+1]).
+ *                 d_group_offsets NULL with n_groups == 1: the whole batch is one swarm.  The offsets are trusted on the device, as
+ *                 d_seg_offsets is; the _host entry validates them.  A swarm has at most UAVQP_SWARM_MAX_VEHICLES vehicles: the _host
+ *                 entry refuses a larger one, the _device entry (which cannot see the offsets) gives such a swarm Phi = NaN and zeros.
+ *   d_start       [n_traj]: the departure time of each trajectory on its swarm's clock; NULL: all zero.
+ * Clock samples.  t_k = clock_start + k dt (the nearest double), k = 0..N, N = n_samples; trapezoid weights om_0 = om_N = 1/2, om_k = 1
+ * otherwise.  The grid does not depend on the durations: Phi is a smooth function of them, and the two vehicles of a pair are always
+ * compared at the same instant.
+ * Position of vehicle b at clock time t.  u = t - start_b.  u < 0: the vehicle WAITS, segment 0 at local time 0.  Otherwise segment and
+ * local time come from the segment rule of uavqp_eval_batch_device at u; if the rule says past the end, or the segment is the last one
+ * and the local time is at or beyond T_{M-1}, the vehicle HAS ARRIVED: last segment, local time T_{M-1} (the cap on the last segment is
+ * what makes the hold continuous: the bare rule would jump by 1e-4 |v_end| there).  Held positions are evaluated from the coefficients.
+ * Pair term and penalty.  delta = q_i - q_j, rho2 = (dx^2 + dy^2 + (dz / downwash)^2) / d_safe^2, x = max(0, 1 - rho2) (dimensionless,
+ * smooth at delta = 0),
+ *       Phi_g = dt sum_k om_k sum_{i < j in g} weight x_ijk^3
+ * each unordered pair once; twice continuously differentiable.
+ *   d_penalty     [n_groups] Phi_g
+ *   d_grad_coeff  layout of coeff: dPhi/dc at FIXED durations.  With e_ijk = -6 weight x^2 / d_safe^2 D delta, D = diag(1, 1, 1 / downwash^2),
+ *                 and G_ik = sum_{j != i} e_ijk the force on vehicle i at sample k:
+ *                 grad_coeff[i][axis][m][n] = dt sum_{k in segment m} om_k G_ik[axis] t_loc^n
+ *                 (a waiting sample adds to segment 0 with t_loc = 0, an arrived one to the last segment with t_loc = T_{M-1})
+ *   d_grad_times  [sum_b M_b]: the EXPLICIT dPhi/dT at FIXED coefficients.  W_m = sum over the moving samples of segment m of
+ *                 om_k G_ik . v_i(t_loc), P the same sum over the arrived samples with v_i = v_{M-1}(T_{M-1}):
+ *                 grad_times[i][l] = -dt sum_{m > l} W_m + [l == M-1] dt P
+ *                 (a moving sample's local time falls with every earlier duration; an arrived sample depends on the last duration alone)
+ *   d_grad_start  [n_traj]: -dt sum_m W_m (held samples do not move with the start)
+ *   d_min_sep     [n_traj]: d_safe sqrt(min rho2) over the vehicle's samples and partners; INFINITY for a vehicle without a partner
+ * Each output may be NULL (all NULL: UAVQP_OK, nothing done).  As with the other penalties the TOTAL gradient in the durations is
+ *       d_grad_times + uavqp_solve_backward_device(g = d_grad_coeff).grad_times
+ * and the gradients in the waypoints and boundary conditions come out of that same backward call.
+ * A vehicle that is not UAVQP_SOLVED (d_status NULL: all are), or has M < 1, is left out of every pair: it exerts nothing and receives
+ * nothing, its own outputs are zeros and min_sep = INFINITY.  A swarm of fewer than two such vehicles has Phi = 0.  weight == 0: zeros,
+ * min_sep still reported.
+ * Every output element is written exactly once, zeros included: no memset is needed.  The additions are in an order fixed by indices
+ * WITHIN the swarm alone: the same bytes run to run, for any grid, and for a swarm computed alone or in the middle of a batch.  No
+ * floating-point atomics.  One launch, asynchronous on the ctx stream, no allocation, no read-back.
+ * UAVQP_ERR_INVALID_ARG: r not 3 / 4, a negative count, a wrong struct_size, n_samples < 1, dt or d_safe not finite or <= 0, downwash not
+ * finite or < 1, weight not finite or < 0, clock_start not finite, NULL times / coeff, ragged without offsets, n_groups < 0, NULL group
+ * offsets with n_groups != 1; from the _host entry also group offsets that do not ascend from 0 to n_traj or a swarm larger than
+ * UAVQP_SWARM_MAX_VEHICLES.
+ * Out of scope: an optimiser that uses the penalty, moving or non-cooperative obstacles, a swarm sharded over several GPUs. */
+#define UAVQP_SWARM_MAX_VEHICLES 128
+typedef struct uavqp_swarm_params {
+    int32_t struct_size;
+    int32_t n_samples;     /* N: N + 1 clock samples (default 64) */
+    double clock_start;    /* s, on the swarm's clock (default 0) */
+    double dt;             /* s between clock samples (default 0.1) */
+    double d_safe;         /* m: separation below which a pair is penalised (default 1.0) */
+    double downwash;       /* >= 1: vertical separations count divided by this (default 1.0) */
+    double weight;         /* >= 0 (default 1e3) */
+} uavqp_swarm_params;
+void uavqp_default_swarm_params(uavqp_swarm_params* out);   /* callable without a device */
+int uavqp_swarm_penalty_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
+                               const double* d_coeff, const int32_t* d_status, int n_groups, const int32_t* d_group_offsets,
+                               const double* d_start, const uavqp_swarm_params* params, double* d_penalty, double* d_grad_coeff,
+                               double* d_grad_times, double* d_grad_start, double* d_min_sep);
+/* The same from HOST pointers (H2D copy, run, D2H copy, synchronous). */
+int uavqp_swarm_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
+                             const double* coeff, const int32_t* status, int n_groups, const int32_t* group_offsets, const double* start,
+                             const uavqp_swarm_params* params, double* penalty, double* grad_coeff, double* grad_times, double* grad_start,
+                             double* min_sep);
+
 /* Batched evaluation of solved trajectories on a uniform time grid.
  * Replaces, for a whole batch, PolyTraj::evaluatePos / evaluateVel / evaluateAcc
  * (src/planner/traj_utils/include/traj_utils/poly_traj.hpp:74-168) as driven by poly_traj_server's

@@ -81,6 +81,9 @@ SYMBOLS = (
     "uavqp_default_spacetime_lbfgs_params",
     "uavqp_spacetime_lbfgs_device",
     "uavqp_spacetime_lbfgs_host",
+    "uavqp_default_swarm_params",
+    "uavqp_swarm_penalty_device",
+    "uavqp_swarm_penalty_host",
     "uavqp_eval_batch_device",
     "uavqp_traj_length_device",
     "uavqp_ellipsoid_check_device",
@@ -177,6 +180,16 @@ class SpacetimeLbfgsParams(ctypes.Structure):
                 ("smooth_weight", ctypes.c_double), ("time_weight", ctypes.c_double), ("t_min", ctypes.c_double), ("t_max", ctypes.c_double),
                 ("max_move", ctypes.c_double), ("initial_step_move", ctypes.c_double), ("initial_step_log", ctypes.c_double),
                 ("armijo_c", ctypes.c_double), ("shrink", ctypes.c_double), ("grow", ctypes.c_double), ("curvature_eps", ctypes.c_double)]
+
+
+class SwarmParams(ctypes.Structure):
+    """uavqp_swarm_params of include/uavqp.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("n_samples", ctypes.c_int32), ("clock_start", ctypes.c_double), ("dt", ctypes.c_double),
+                ("d_safe", ctypes.c_double), ("downwash", ctypes.c_double), ("weight", ctypes.c_double)]
+
+
+# largest swarm of uavqp_swarm_penalty_* (UAVQP_SWARM_MAX_VEHICLES of include/uavqp.h)
+UAVQP_SWARM_MAX_VEHICLES = 128
 
 
 def build(force=False):
@@ -282,6 +295,10 @@ def lib():
                                                ctypes.POINTER(ClearanceParams), ctypes.POINTER(SpacetimeLbfgsParams), dp, ip, dp, ip, dp, dp, ip]
     L.uavqp_spacetime_lbfgs_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(LimitParams),
                                              ctypes.POINTER(ClearanceParams), ctypes.POINTER(SpacetimeLbfgsParams), dp, ip, dp, ip, dp, dp, ip]
+    L.uavqp_default_swarm_params.argtypes = [ctypes.POINTER(SwarmParams)]
+    L.uavqp_default_swarm_params.restype = None
+    L.uavqp_swarm_penalty_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, i32, ip, dp, ctypes.POINTER(SwarmParams), dp, dp, dp, dp, dp]
+    L.uavqp_swarm_penalty_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, i32, ip, dp, ctypes.POINTER(SwarmParams), dp, dp, dp, dp, dp]
     L.uavqp_eval_batch_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, i32, dp]
     L.uavqp_traj_length_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ctypes.c_double, dp, dp, ip]
     L.uavqp_ellipsoid_check_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, dp, i32,

@@ -209,6 +209,63 @@ def _flight_function():
     return _Flight
 
 
+_Swarm = None
+
+
+def _swarm_function():
+    global _Swarm
+    if _Swarm is not None:
+        return _Swarm
+    import torch
+
+    class SwarmPenalty(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, coeff, times, start, ctx, r, group_offsets, seg_offsets, uniform_segments, status, params):
+            for name, t in (("coeff", coeff), ("times", times), ("start", start)):
+                if t is not None and (t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous()):
+                    raise ValueError(f"swarm_penalty: {name} must be a contiguous float64 tensor on the GPU")
+            total = times.numel()
+            n_traj = total // uniform_segments if uniform_segments > 0 else seg_offsets.numel() - 1
+            if coeff.numel() != 3 * 2 * r * total:
+                raise ValueError("swarm_penalty: coeff must hold 3 * 2r doubles per segment")
+            if start is not None and start.numel() != n_traj:
+                raise ValueError("swarm_penalty: start must hold one departure time per trajectory")
+            n_groups = 1 if group_offsets is None else group_offsets.numel() - 1
+            phi = torch.empty(n_groups, dtype=torch.float64, device=times.device)
+            g_c = torch.empty_like(coeff)
+            g_t = torch.empty_like(times)
+            g_s = torch.empty(n_traj, dtype=torch.float64, device=times.device)
+            ctx.set_stream(torch.cuda.current_stream(times.device).cuda_stream)
+            ctx.swarm_penalty_device(r, n_traj, uniform_segments, seg_offsets, times.detach(), coeff.detach(), n_groups=n_groups,
+                                     group_offsets=group_offsets, start=None if start is None else start.detach(), status=status,
+                                     penalty=phi, grad_coeff=g_c, grad_times=g_t, grad_start=g_s, **params)
+            if uniform_segments > 0:
+                counts = torch.full((n_traj,), uniform_segments, dtype=torch.int64, device=times.device)
+            else:
+                counts = (seg_offsets[1:] - seg_offsets[:-1]).to(torch.int64)
+            if group_offsets is None:
+                sizes = torch.full((1,), n_traj, dtype=torch.int64, device=times.device)
+            else:
+                sizes = (group_offsets[1:] - group_offsets[:-1]).to(torch.int64)
+            fctx.save_for_backward(g_c, g_t, g_s, counts, sizes)
+            fctx.nc = 3 * 2 * r
+            return phi
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable   # the gradients come from a raw kernel: no second derivative through them
+        def backward(fctx, grad_phi):
+            g_c, g_t, g_s, counts, sizes = fctx.saved_tensors
+            need_c, need_t, need_s = fctx.needs_input_grad[:3]
+            per_traj = torch.repeat_interleave(grad_phi, sizes)                    # the swarm's weight on each of its vehicles
+            out_c = g_c * torch.repeat_interleave(per_traj, counts * fctx.nc) if need_c else None
+            out_t = g_t * torch.repeat_interleave(per_traj, counts) if need_t else None
+            out_s = g_s * per_traj if need_s else None
+            return out_c, out_t, out_s, None, None, None, None, None, None, None
+
+    _Swarm = SwarmPenalty
+    return _Swarm
+
+
 def solve_batch(ctx, r, waypoints, times, bc, seg_offsets=None, uniform_segments=0, max_segments=0, check_status=False, return_status=False):
     """Differentiable uavqp_solve_batch_device.  ctx: a Context on the tensors' device.  waypoints [sum (M_b + 1)][3], times [sum M_b],
     bc [n_traj][2][r-1][3]; seg_offsets: int32 device tensor [n_traj + 1] (ragged; max_segments = the longest trajectory, read back from
@@ -246,6 +303,21 @@ def clearance_penalty(ctx, r, coeff, times, esdf, seg_offsets=None, uniform_segm
     if uniform_segments <= 0 and seg_offsets is None:
         raise ValueError("clearance_penalty: ragged batches need seg_offsets")
     return _clearance_function().apply(coeff, times, ctx, int(r), esdf, seg_offsets, int(uniform_segments), status, dict(params))
+
+
+def swarm_penalty(ctx, r, coeff, times, group_offsets=None, start=None, seg_offsets=None, uniform_segments=0, status=None, **params):
+    """Differentiable uavqp_swarm_penalty_device: the separation penalty [n_groups] between the vehicles of each swarm (trajectories
+    group_offsets[g] .. group_offsets[g + 1], an int32 device tensor; None: the whole batch is one swarm) of coeff (layout of
+    solve_batch's result) at the durations `times` [sum M_b] and the departure times `start` [n_traj] (None: all zero, not
+    differentiated).  params: fields of uavqp_swarm_params that differ from the defaults (n_samples, clock_start, dt, d_safe, downwash,
+    weight).  status: optional int32 status tensor of the solve.  Differentiable in coeff, times and start; an upstream weight per swarm
+    scales that swarm's gradients.  The gradient in `times` is the explicit part; with coeff = solve_batch(..., times, ...) torch adds
+    the part through the solve, and waypoints.grad / bc.grad come from the same backward pass."""
+    if uniform_segments <= 0 and seg_offsets is None:
+        raise ValueError("swarm_penalty: ragged batches need seg_offsets")
+    from .traj_optimizer import Context
+    Context._swarm_params(params)   # (an unknown field is refused before anything runs)
+    return _swarm_function().apply(coeff, times, start, ctx, int(r), group_offsets, seg_offsets, int(uniform_segments), status, dict(params))
 
 
 def flight_penalty(ctx, r, coeff, times, esdf, seg_offsets=None, uniform_segments=0, status=None, limits=None, clearance=None):

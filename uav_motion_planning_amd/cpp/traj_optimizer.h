@@ -192,6 +192,34 @@ class TrajOptimizer {
         }
         return phi;
     }
+    // Which trajectories fly together: swarm g is the trajectories group_offsets[g] .. group_offsets[g + 1] (null: the whole batch is one
+    // swarm); start_times [n_traj]: when each departs on its swarm's clock (null: all at 0).  After setWaypoints (sizes).
+    void setSwarm(const int32_t* group_offsets, int n_groups, const double* start_times) {
+        groups_.clear();
+        start_.clear();
+        if (group_offsets && n_groups >= 0) groups_.assign(group_offsets, group_offsets + n_groups + 1);
+        if (start_times) start_.assign(start_times, start_times + n_traj_);
+    }
+    // Separation penalty per swarm between the vehicles set with setSwarm, at the stored coefficients and durations (after solve() or
+    // optimizeTime(); uavqp_swarm_penalty_host).  min_sep, when given, receives the smallest sampled separation per trajectory.  A
+    // trajectory that did not solve is left out of every pair.  Empty on failure.
+    std::vector<double> getSwarmPenalty(const uavqp_swarm_params& params, std::vector<double>* min_sep = nullptr) {
+        std::vector<double> phi;
+        if (n_traj_ <= 0 || !ctx_ || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_]) ||
+            coef_.size() != static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_] || status_.size() != static_cast<size_t>(n_traj_) ||
+            (!start_.empty() && start_.size() != static_cast<size_t>(n_traj_)))
+            return phi;
+        const int n_groups = groups_.empty() ? 1 : static_cast<int>(groups_.size()) - 1;
+        phi.assign(n_groups, 0.0);
+        if (min_sep) min_sep->assign(n_traj_, 0.0);
+        if (uavqp_swarm_penalty_host(ctx_, order_, n_traj_, 0, seg_offsets_.data(), T_.data(), coef_.data(), status_.data(), n_groups,
+                                     groups_.empty() ? nullptr : groups_.data(), start_.empty() ? nullptr : start_.data(), &params, phi.data(),
+                                     nullptr, nullptr, nullptr, min_sep ? min_sep->data() : nullptr) != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            phi.clear();
+        }
+        return phi;
+    }
     // Clearance penalty per trajectory of the stored coefficients at the stored durations against a distance field (uavqp::EsdfMap of
     // cpp/esdf_map.h, built on context() and updated; uavqp_clearance_penalty_host).  min_dist / outside, when given, receive the smallest
     // sampled distance and the count of samples outside the map per trajectory.  A trajectory that did not solve carries zero.  Empty on failure.
@@ -581,6 +609,8 @@ class TrajOptimizer {
     std::vector<double> objective_, peak_, min_dist_;
     std::vector<int32_t> outside_;
     std::vector<int32_t> accepted_;
+    std::vector<int32_t> groups_;   // setSwarm: empty = the whole batch is one swarm
+    std::vector<double> start_;     // setSwarm: empty = every vehicle departs at 0
     int rows_k_ = 0;
     uavqp_pipeline_result pipe_result_{};
 };

@@ -134,3 +134,7 @@
     UAVQP_INST __global__ void uavqp::spacetime_lbfgs_step_kernel<R_, true>(uavqp::SpacetimeLbfgsArgs);       \
     UAVQP_INST __global__ void uavqp::spacetime_lbfgs_step_kernel<R_, false>(uavqp::SpacetimeLbfgsArgs);
 #define UAVQP_INSTANCES_SPACETIME_LBFGS UAVQP_SPACETIME_LBFGS_R(3) UAVQP_SPACETIME_LBFGS_R(4)
+
+// ---- qp_swarm.h: the separation penalty between the vehicles of a swarm on a shared clock
+#define UAVQP_SWARM_R(R_) UAVQP_INST __global__ void uavqp::swarm_penalty_kernel<R_>(uavqp::SwarmArgs);
+#define UAVQP_INSTANCES_SWARM UAVQP_SWARM_R(3) UAVQP_SWARM_R(4)

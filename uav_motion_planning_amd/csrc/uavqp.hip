@@ -38,6 +38,7 @@
 #include "qp_waypoint_opt.h"
 #include "qp_spacetime.h"
 #include "qp_spacetime_lbfgs.h"
+#include "qp_swarm.h"
 // Measured-slower alternatives kept as bit-identical cross-checks: `make experiments` (-DUAVQP_EXPERIMENTS) only
 #ifdef UAVQP_EXPERIMENTS
 #include "cloud_grid2d.h"
@@ -68,6 +69,7 @@ UAVQP_INSTANCES_ESDF
 UAVQP_INSTANCES_WPOPT
 UAVQP_INSTANCES_SPACETIME
 UAVQP_INSTANCES_SPACETIME_LBFGS
+UAVQP_INSTANCES_SWARM
 #endif
 
 namespace uavqp {
@@ -1949,6 +1951,11 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
 // ===================================================================================================
 #include "uavqp_spacetime.h"
 #include "uavqp_spacetime_lbfgs.h"
+
+// ===================================================================================================
+// Separation penalty between the vehicles of a swarm on a shared clock
+// ===================================================================================================
+#include "uavqp_swarm.h"
 
 // ===================================================================================================
 // N3: quadrotor_msgs/PolynomialTrajectory packer (host only)

@@ -192,6 +192,55 @@ class Context:
         return penalty, g_c, g_t, peak
 
     @staticmethod
+    def _swarm_params(params):
+        sp = _lib.SwarmParams()
+        _lib.lib().uavqp_default_swarm_params(ctypes.byref(sp))
+        for k, v in params.items():
+            if not hasattr(sp, k) or k == "struct_size":
+                raise ValueError(f"unknown uavqp_swarm_params field {k!r}")
+            setattr(sp, k, v)
+        return sp
+
+    def swarm_penalty_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, n_groups=1, group_offsets=None, start=None,
+                             status=None, penalty=None, grad_coeff=None, grad_times=None, grad_start=None, min_sep=None, **params):
+        """uavqp_swarm_penalty_device on device buffers: the separation penalty [n_groups] between the vehicles of each swarm (trajectories
+        group_offsets[g] .. group_offsets[g + 1]; None with n_groups = 1: the whole batch) compared at the same instants of a shared
+        clock, its gradient in the coefficients at fixed durations (layout of coeff), its EXPLICIT gradients in the durations [sum M]
+        and in the departure times `start` [n_traj] (None: all zero), and the smallest sampled separation [n_traj]; each output may be
+        None.  status (the solve's, optional): vehicles that are not SOLVED are left out of every pair.  params: fields of
+        uavqp_swarm_params that differ from uavqp_default_swarm_params (n_samples, clock_start, dt, d_safe, downwash, weight).
+        Asynchronous."""
+        sp = self._swarm_params(params)
+        rc = _lib.lib().uavqp_swarm_penalty_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff), _ptr(status),
+                                                   int(n_groups), _ptr(group_offsets), _ptr(start), ctypes.byref(sp), _ptr(penalty),
+                                                   _ptr(grad_coeff), _ptr(grad_times), _ptr(grad_start), _ptr(min_sep))
+        _lib.check(rc, "uavqp_swarm_penalty_device")
+
+    def swarm_penalty_host(self, r, seg_offsets, times, coeff, group_offsets=None, start=None, uniform_segments=0, status=None, **params):
+        """numpy in / numpy out (synchronous).  group_offsets None: the whole batch is one swarm.  Returns (penalty [n_groups], grad_coeff,
+        grad_times [sum M], grad_start [n_traj], min_sep [n_traj])."""
+        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
+        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total and coeff.size == 3 * 2 * r * total
+        go = None if group_offsets is None else np.ascontiguousarray(group_offsets, dtype=np.int32)
+        n_groups = 1 if go is None else go.size - 1
+        start = None if start is None else np.ascontiguousarray(start, dtype=np.float64).ravel()
+        assert start is None or start.size == n_traj
+        sp = self._swarm_params(params)
+        penalty = np.zeros(n_groups, dtype=np.float64)
+        g_c = np.zeros_like(coeff)
+        g_t = np.zeros(total, dtype=np.float64)
+        g_s = np.zeros(n_traj, dtype=np.float64)
+        min_sep = np.zeros(n_traj, dtype=np.float64)
+        rc = _lib.lib().uavqp_swarm_penalty_host(self._h, r, n_traj, uniform_segments, _ptr(so), _ptr(times), _ptr(coeff), _ptr(status),
+                                                 n_groups, _ptr(go), _ptr(start), ctypes.byref(sp), _ptr(penalty), _ptr(g_c), _ptr(g_t),
+                                                 _ptr(g_s), _ptr(min_sep))
+        _lib.check(rc, "uavqp_swarm_penalty_host")
+        return penalty, g_c, g_t, g_s, min_sep
+
+    @staticmethod
     def _clearance_params(params):
         cp = _lib.ClearanceParams()
         _lib.lib().uavqp_default_clearance_params(ctypes.byref(cp))
@@ -822,6 +871,9 @@ class TrajOptimizer:
                                      .iterations, .peak, .min_dist, .outside as above
     optimizeTrajectoryLbfgs(esdf, ...)   the same with limited-memory BFGS directions kept on the device (uavqp_spacetime_lbfgs_host)
     getFlightPenalty(esdf, ...)      [n_traj] limit + clearance penalty of the stored coefficients in one launch
+    setSwarm(group_offsets, start_times)   which trajectories fly together (swarm g = trajectories group_offsets[g] .. group_offsets[g + 1];
+                                     None: the whole batch is one swarm) and when each departs on its swarm's clock (None: all at 0)
+    getSwarmPenalty(...)             [n_groups] separation penalty between the vehicles of each swarm at the stored coefficients
     getCostWaypointGradient()        [sum (M_b + 1)][3] gradient of getCost() in the waypoints, both ends of every trajectory included
     backward(grad_coeff)             equality-constrained problems only, after solve(): (grad_times, grad_waypoints, grad_bc) of a loss
                                      with d loss / d getPolyCoeff() = grad_coeff, through the solve
@@ -837,6 +889,7 @@ class TrajOptimizer:
         self._wp = self._T = self._bc = self._so = None
         self._lo = self._hi = None
         self._rows = None
+        self._groups = self._start = None
         self._coef = np.zeros(0)
         self.status = np.zeros(0, dtype=np.int32)
         self.iterations = np.zeros(0, dtype=np.int32)
@@ -1026,6 +1079,21 @@ class TrajOptimizer:
         return self._ctx.clearance_penalty_host(self._r, self._so, self._T, self._coef, esdf, status=self.status, **params)[0]
 
     get_clearance_penalty = getClearancePenalty
+
+    def setSwarm(self, group_offsets=None, start_times=None):
+        """Which trajectories fly together: swarm g is the trajectories group_offsets[g] .. group_offsets[g + 1] (None: the whole batch is
+        one swarm); start_times [n_traj]: when each departs on its swarm's clock (None: all at 0)."""
+        self._groups = None if group_offsets is None else np.ascontiguousarray(group_offsets, dtype=np.int32).ravel()
+        self._start = None if start_times is None else np.ascontiguousarray(start_times, dtype=np.float64).ravel()
+
+    def getSwarmPenalty(self, **params):
+        """[n_groups] separation penalty between the vehicles of each swarm set with setSwarm(), at the stored coefficients and durations
+        (uavqp_swarm_penalty_host); params: fields of uavqp_swarm_params that differ from the defaults.  Vehicles that did not solve are
+        left out of every pair."""
+        if self._ctx is None or self._coef.size != 3 * 2 * self._r * int(self._so[-1]) or self.status.size != self._so.size - 1:
+            raise _lib.UavqpError("getSwarmPenalty: no solved coefficients (call solve() or optimizeTime() first)")
+        return self._ctx.swarm_penalty_host(self._r, self._so, self._T, self._coef, group_offsets=self._groups, start=self._start,
+                                            status=self.status, **params)[0]
 
     def context(self):
         """The Context this optimiser solves on (created on first use): what an esdf.EsdfMap for getClearancePenalty is built on."""
