@@ -864,7 +864,8 @@ int uavqp_spacetime_lbfgs_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_se
  * finite or < 1, weight not finite or < 0, clock_start not finite, NULL times / coeff, ragged without offsets, n_groups < 0, NULL group
  * offsets with n_groups != 1; from the _host entry also group offsets that do not ascend from 0 to n_traj or a swarm larger than
  * UAVQP_SWARM_MAX_VEHICLES.
- * Out of scope: an optimiser that uses the penalty, moving or non-cooperative obstacles, a swarm sharded over several GPUs. */
+ * The optimiser that uses the penalty (one accept / reject per SWARM): uavqp_swarm_optimize_device below.
+ * Out of scope: moving or non-cooperative obstacles, a swarm sharded over several GPUs. */
 #define UAVQP_SWARM_MAX_VEHICLES 128
 typedef struct uavqp_swarm_params {
     int32_t struct_size;
@@ -885,6 +886,105 @@ int uavqp_swarm_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segm
                              const double* coeff, const int32_t* status, int n_groups, const int32_t* group_offsets, const double* start,
                              const uavqp_swarm_params* params, double* penalty, double* grad_coeff, double* grad_times, double* grad_start,
                              double* min_sep);
+
+/* Swarm optimiser: the joint optimisation of uavqp_spacetime_optimize_device with the swarm separation penalty above in the objective and
+ * ONE accept / reject per SWARM (no reference counterpart; what an EGO-Swarm / MINCO-swarm back-end gives, for a batch of swarms).  For
+ * each swarm g, described by n_groups / d_group_offsets exactly as for uavqp_swarm_penalty_device, with the boundary derivatives and both
+ * end waypoints of every vehicle fixed,
+ *       minimise over the interior waypoints and durations of every vehicle b in g, and (start_window > 0) the departures start_b
+ *           f_g = sum_{b in g} [ smooth_weight J_b + time_weight sum_i T_{b,i} + Phi_flight,b ] + Phi_swarm,g
+ *       subject to   |p - p^start| <= max_move,   t_min <= T <= t_max,   |start_b - start_b^0| <= start_window
+ * J_b and Phi_flight,b as in uavqp_spacetime_optimize_device, Phi_swarm,g the penalty of uavqp_swarm_penalty_device with `swarm` at the
+ * departures start_b.  The swarm term couples the vehicles: a vehicle's trial means something only together with its partners' trials,
+ * which is why the per-trajectory accept / reject of the single-vehicle optimisers cannot be used.
+ * Gradients.  g = dPhi_flight/dc + dPhi_swarm/dc goes through ONE uavqp_solve_backward_device call per trial;
+ *       df/dp_k = smooth_weight dJ/dp_k + backward(g).grad_waypoints_k
+ *       df/dT_i = -smooth_weight H_i + time_weight + (explicit dPhi_flight/dT_i + explicit dPhi_swarm/dT_i) + backward(g).grad_times_i
+ *       df/dstart_b = dPhi_swarm/dstart_b =: d^s_b   (already the total gradient: the coefficients do not depend on the departure)
+ * Method: that of uavqp_spacetime_optimize_device -- projected gradient descent with Armijo backtracking along the projection arc, in p and
+ * in u = log T -- with every quantity that is per trajectory there per SWARM here.  Directions d^p, d^u per vehicle as there; d^s_b zero
+ * where the window blocks it (start_b at start_b^0 - start_window and d^s_b > 0, or at the upper end and d^s_b < 0).  One alpha and three
+ * scales per swarm, fixed at the first gradient: sigma_p = initial_step_move / max |d^p|, sigma_u = initial_step_log / max |d^u|, sigma_s =
+ * initial_step_start / max |d^s|, each maximum over ALL vehicles of the swarm that take part (a scale is 0 when its maximum is 0 or not
+ * finite); alpha starts at 1, or at 0 if all three scales are 0.
+ * Trial, every vehicle of the swarm at once: p_t = clamp(p - alpha sigma_p d^p), T_t = clamp(T exp(-alpha sigma_u d^u)), start_t =
+ * clamp(start - alpha sigma_s d^s).  With need_b = sum_k (df/dp_k) . (p_k - p_t,k) + sum_i d^u_i log(T_i / T_t,i) of vehicle b,
+ *       need_g = armijo_c * [ sum_b need_b + sum_b d^s_b (start_b - start_t,b) ]
+ * the trial is accepted iff alpha > 0, EVERY vehicle that takes part solved at its trial point, and f_g,trial <= f_g - need_g.  Accepted:
+ * every vehicle of the swarm takes its trial point, alpha *= grow; rejected: none does, alpha *= shrink.  f_g never increases.
+ * Participation.  A vehicle that is not UAVQP_SOLVED at the start keeps its waypoints, durations and departure byte for byte (apart from
+ * the projection of all-positive durations, as in uavqp_spacetime_optimize_device) and takes no part; the swarm penalty leaves it out of
+ * every pair, and the rest of its swarm optimises without it.  A swarm with no participating vehicle, or whose f_g is not finite at the
+ * start, reports (NaN, NaN) and moves nothing.
+ * Host-side C++ sequencing of
+ *       anchor copies, clamp, solve, flight penalty, swarm penalty, backward, step,
+ *       max_iters x { solve at the trial point, flight penalty, swarm penalty at the trial departures, backward, step },
+ *       solve, diagnostics
+ * five launches per trial, every decision ON THE DEVICE, nothing read back, the number of launches depends on max_iters alone.  Every sum
+ * is taken in an order fixed by indices inside the swarm alone: the same bytes run to run, for any grid, and for a swarm alone or in the
+ * middle of a batch.  A swarm of ONE vehicle with start_window = 0 gives, byte for byte, what uavqp_spacetime_optimize_device gives for that
+ * trajectory.  Asynchronous on the ctx stream (a first call of a given size allocates the workspace).
+ *   d_waypoints, d_times, d_bc, d_seg_offsets, max_segments, total_segments   as for uavqp_spacetime_optimize_device (waypoints and times IN / OUT)
+ *   n_groups, d_group_offsets   as for uavqp_swarm_penalty_device; trusted on the device.  A swarm of more than UAVQP_SWARM_MAX_VEHICLES takes
+ *                    no part on the _device entry (objective NaN, NaN; its bytes are kept); the _host entry validates the offsets and
+ *                    refuses such a swarm.
+ *   d_start          [n_traj] IN: the departures, OUT: the accepted departures.  May be NULL (all zero) when start_window == 0.
+ *   esdf, limits, clearance     as for uavqp_spacetime_optimize_device;  swarm: the clock, d_safe, downwash and weight, as for
+ *                    uavqp_swarm_penalty_device
+ *   d_coeff_out      the solve AT what is handed back: bit for bit what uavqp_solve_batch_device writes for it; d_status_out [n_traj] its
+ *                    status (may be NULL)
+ *   d_objective_out  [n_groups][2]: f_g at the start (after the projection of the durations), f_g at the result (NaN, NaN: took no part)
+ *   d_accepted_out   [n_groups] int32 accepted trials (may be NULL)
+ *   d_peak_out [n_traj][2], d_min_dist_out [n_traj], d_outside_out [n_traj] int32: the flight penalty's diagnostics at the result;
+ *   d_min_sep_out [n_traj]: the swarm penalty's min_sep at the result (each may be NULL)
+ *   params           uavqp_default_swarm_opt_params fills the defaults: the fields of uavqp_spacetime_params with the same names, defaults and
+ *                    validity, start_window 0 (>= 0, finite), initial_step_start 0.1 s (> 0, finite).  max_iters = 0: the plain solve
+ *                    after the projection of the durations, both objective columns equal.
+ * UAVQP_ERR_INVALID_ARG: a wrong struct_size or an invalid field of params / swarm / limits / clearance, whatever
+ * uavqp_spacetime_optimize_device refuses in the batch arguments, n_groups < 0, NULL group offsets with n_groups != 1, start_window > 0 with
+ * NULL d_start; from the _host entry also group offsets that do not ascend from 0 to n_traj or a swarm larger than
+ * UAVQP_SWARM_MAX_VEHICLES.
+ * WHAT THE RESULT IS.  All penalties are SOFT: at finite weights two vehicles may end closer than d_safe, a limit may be exceeded by a
+ * few per cent, an obstacle approached closer than the clearance asks.  The result is a LOCAL minimum of a piecewise smooth f_g: two
+ * vehicles that meet head-on exactly on one line are on a saddle and do not move sideways; give them different departures or waypoints.
+ * The step is the swarm's: ONE slow vehicle (a trial that does not solve, a large gradient that fixes a small scale, a rejected
+ * trial) holds back the step of every vehicle of its swarm, and the scales are fixed at the FIRST gradient, as in
+ * uavqp_spacetime_optimize_device; a second call re-scales.  The hard tests remain uavqp_time_reallocate_device (limits) and
+ * uavqp_ellipsoid_check_* (collisions); separation is reported by d_min_sep_out on the swarm's clock samples only.
+ * Out of scope: quasi-Newton directions per swarm, capture into a graph, corridor and general-rows solves, a swarm sharded over several
+ * GPUs. */
+typedef struct uavqp_swarm_opt_params {
+    int32_t struct_size;
+    int32_t max_iters;          /* trials per swarm (default 32) */
+    double smooth_weight;       /* the fields of uavqp_spacetime_params, same meaning, defaults and validity */
+    double time_weight;
+    double t_min;
+    double t_max;
+    double max_move;
+    double initial_step_move;
+    double initial_step_log;
+    double armijo_c;
+    double shrink;
+    double grow;
+    double start_window;        /* half width of the window around every start departure, s, >= 0, finite (default 0: departures fixed) */
+    double initial_step_start;  /* largest move of a departure in the first trial, s, > 0 (default 0.1) */
+} uavqp_swarm_opt_params;
+void uavqp_default_swarm_opt_params(uavqp_swarm_opt_params* out);   /* callable without a device */
+int uavqp_swarm_optimize_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                                const int32_t* d_seg_offsets, double* d_waypoints, double* d_times, const double* d_bc, int n_groups,
+                                const int32_t* d_group_offsets, double* d_start, const uavqp_esdf* esdf, const uavqp_limit_params* limits,
+                                const uavqp_clearance_params* clearance, const uavqp_swarm_params* swarm,
+                                const uavqp_swarm_opt_params* params, double* d_coeff_out, int32_t* d_status_out, double* d_objective_out,
+                                int32_t* d_accepted_out, double* d_peak_out, double* d_min_dist_out, int32_t* d_outside_out,
+                                double* d_min_sep_out);
+/* The same from HOST pointers (H2D copy, run, D2H copy, synchronous; waypoints, times and start are updated in place; the map stays a
+ * device object). */
+int uavqp_swarm_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                              double* waypoints, double* times, const double* bc, int n_groups, const int32_t* group_offsets, double* start,
+                              const uavqp_esdf* esdf, const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
+                              const uavqp_swarm_params* swarm, const uavqp_swarm_opt_params* params, double* coeff_out, int32_t* status_out,
+                              double* objective_out, int32_t* accepted_out, double* peak_out, double* min_dist_out, int32_t* outside_out,
+                              double* min_sep_out);
 
 /* Batched evaluation of solved trajectories on a uniform time grid.
  * Replaces, for a whole batch, PolyTraj::evaluatePos / evaluateVel / evaluateAcc

@@ -84,6 +84,9 @@ SYMBOLS = (
     "uavqp_default_swarm_params",
     "uavqp_swarm_penalty_device",
     "uavqp_swarm_penalty_host",
+    "uavqp_default_swarm_opt_params",
+    "uavqp_swarm_optimize_device",
+    "uavqp_swarm_optimize_host",
     "uavqp_eval_batch_device",
     "uavqp_traj_length_device",
     "uavqp_ellipsoid_check_device",
@@ -186,6 +189,15 @@ class SwarmParams(ctypes.Structure):
     """uavqp_swarm_params of include/uavqp.h."""
     _fields_ = [("struct_size", ctypes.c_int32), ("n_samples", ctypes.c_int32), ("clock_start", ctypes.c_double), ("dt", ctypes.c_double),
                 ("d_safe", ctypes.c_double), ("downwash", ctypes.c_double), ("weight", ctypes.c_double)]
+
+
+class SwarmOptParams(ctypes.Structure):
+    """uavqp_swarm_opt_params of include/uavqp.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("max_iters", ctypes.c_int32), ("smooth_weight", ctypes.c_double),
+                ("time_weight", ctypes.c_double), ("t_min", ctypes.c_double), ("t_max", ctypes.c_double), ("max_move", ctypes.c_double),
+                ("initial_step_move", ctypes.c_double), ("initial_step_log", ctypes.c_double), ("armijo_c", ctypes.c_double),
+                ("shrink", ctypes.c_double), ("grow", ctypes.c_double), ("start_window", ctypes.c_double),
+                ("initial_step_start", ctypes.c_double)]
 
 
 # largest swarm of uavqp_swarm_penalty_* (UAVQP_SWARM_MAX_VEHICLES of include/uavqp.h)
@@ -299,6 +311,14 @@ def lib():
     L.uavqp_default_swarm_params.restype = None
     L.uavqp_swarm_penalty_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, i32, ip, dp, ctypes.POINTER(SwarmParams), dp, dp, dp, dp, dp]
     L.uavqp_swarm_penalty_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, i32, ip, dp, ctypes.POINTER(SwarmParams), dp, dp, dp, dp, dp]
+    L.uavqp_default_swarm_opt_params.argtypes = [ctypes.POINTER(SwarmOptParams)]
+    L.uavqp_default_swarm_opt_params.restype = None
+    L.uavqp_swarm_optimize_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, i32, ip, dp, vp, ctypes.POINTER(LimitParams),
+                                              ctypes.POINTER(ClearanceParams), ctypes.POINTER(SwarmParams), ctypes.POINTER(SwarmOptParams),
+                                              dp, ip, dp, ip, dp, dp, ip, dp]
+    L.uavqp_swarm_optimize_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, i32, ip, dp, vp, ctypes.POINTER(LimitParams),
+                                            ctypes.POINTER(ClearanceParams), ctypes.POINTER(SwarmParams), ctypes.POINTER(SwarmOptParams),
+                                            dp, ip, dp, ip, dp, dp, ip, dp]
     L.uavqp_eval_batch_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, i32, dp]
     L.uavqp_traj_length_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ctypes.c_double, dp, dp, ip]
     L.uavqp_ellipsoid_check_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, i32, ctypes.c_double, ctypes.c_double, dp, i32,

@@ -346,6 +346,48 @@ class TrajOptimizer {
         for (int32_t s : status_) if (s != UAVQP_SOLVED) return false;
         return true;
     }
+    // optimizeTrajectory for the swarms set with setSwarm (include/uavqp.h uavqp_swarm_optimize_host; the reference's equality rows only:
+    // false when a corridor or rows are set): the separation penalty `swarm` between the vehicles of each swarm joins the objective and
+    // every trial is accepted or rejected per SWARM.  With params->start_window > 0 the departures of setSwarm are optimised too and the
+    // new ones stored (swarmStart()).  Fills the members optimizeTrajectory fills -- objective() [n_groups][2] and acceptedTrials()
+    // [n_groups] are per swarm -- and minSep() per trajectory.  params: null = uavqp_default_swarm_opt_params.  All penalties are soft and
+    // the result a local minimum: uavqp_time_reallocate_device and uavqp_ellipsoid_check_* afterwards remain the hard tests.
+    template <class Map>
+    bool optimizeSwarm(const Map& map, const uavqp_limit_params& limits, const uavqp_clearance_params& clearance, const uavqp_swarm_params& swarm,
+                       const uavqp_swarm_opt_params* params = nullptr) {
+        if (n_traj_ <= 0 || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_])) return false;
+        if (!lo_.empty() || rows_k_ > 0) {
+            std::cout << "solver solve failed! (optimizeSwarm: corridor and general-rows problems are out of scope)" << std::endl;
+            return false;
+        }
+        if (!start_.empty() && start_.size() != static_cast<size_t>(n_traj_)) return false;
+        if (!ensureContext()) return false;
+        if (bc_.empty()) bc_.assign(static_cast<size_t>(n_traj_) * 2 * (order_ - 1) * 3, 0.0);
+        uavqp_swarm_opt_params pp;
+        if (params) pp = *params; else uavqp_default_swarm_opt_params(&pp);
+        if (start_.empty() && pp.start_window > 0.0) start_.assign(n_traj_, 0.0);
+        const int n_groups = groups_.empty() ? 1 : static_cast<int>(groups_.size()) - 1;
+        coef_.assign(static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_], 0.0);
+        status_.assign(n_traj_, 0);
+        objective_.assign(static_cast<size_t>(2) * n_groups, 0.0);
+        accepted_.assign(n_groups, 0);
+        peak_.assign(static_cast<size_t>(2) * n_traj_, 0.0);
+        min_dist_.assign(n_traj_, 0.0);
+        outside_.assign(n_traj_, 0);
+        min_sep_.assign(n_traj_, 0.0);
+        const int rc = uavqp_swarm_optimize_host(ctx_, order_, n_traj_, 0, 0, seg_offsets_.data(), wp_.data(), T_.data(), bc_.data(), n_groups,
+                                                 groups_.empty() ? nullptr : groups_.data(), start_.empty() ? nullptr : start_.data(),
+                                                 map.handle(), &limits, &clearance, &swarm, &pp, coef_.data(), status_.data(), objective_.data(),
+                                                 accepted_.data(), peak_.data(), min_dist_.data(), outside_.data(), min_sep_.data());
+        if (rc != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            return false;
+        }
+        for (int32_t s : status_) if (s != UAVQP_SOLVED) return false;
+        return true;
+    }
+    const std::vector<double>& minSep() const { return min_sep_; }
+    const std::vector<double>& swarmStart() const { return start_; }   // (empty: every vehicle departs at 0)
     // Limit penalty + clearance penalty per trajectory of the stored coefficients at the stored durations, in one launch
     // (uavqp_flight_penalty_host).  A trajectory that did not solve carries zero.  Empty on failure.
     template <class Map>
@@ -606,7 +648,7 @@ class TrajOptimizer {
     std::vector<double> wp_, T_, bc_, coef_, lo_, hi_, pipe_lo_, pipe_hi_, row_tau_, row_lo_, row_hi_;
     std::vector<int32_t> row_deriv_, first_hit_, repair_deriv_;
     std::vector<double> repair_tau_, repair_lo_, repair_hi_;
-    std::vector<double> objective_, peak_, min_dist_;
+    std::vector<double> objective_, peak_, min_dist_, min_sep_;
     std::vector<int32_t> outside_;
     std::vector<int32_t> accepted_;
     std::vector<int32_t> groups_;   // setSwarm: empty = the whole batch is one swarm

@@ -138,3 +138,10 @@
 // ---- qp_swarm.h: the separation penalty between the vehicles of a swarm on a shared clock
 #define UAVQP_SWARM_R(R_) UAVQP_INST __global__ void uavqp::swarm_penalty_kernel<R_>(uavqp::SwarmArgs);
 #define UAVQP_INSTANCES_SWARM UAVQP_SWARM_R(3) UAVQP_SWARM_R(4)
+
+// ---- qp_swarm_opt.h: the per-swarm step of the swarm optimiser, and the swarm penalty that ADDS its gradients to the flight penalty's
+#define UAVQP_SWARM_OPT_R(R_)                                                                  \
+    UAVQP_INST __global__ void uavqp::swarm_penalty_kernel<R_, true>(uavqp::SwarmArgs);           \
+    UAVQP_INST __global__ void uavqp::swarm_step_kernel<R_, true>(uavqp::SwarmOptArgs);           \
+    UAVQP_INST __global__ void uavqp::swarm_step_kernel<R_, false>(uavqp::SwarmOptArgs);
+#define UAVQP_INSTANCES_SWARM_OPT UAVQP_SWARM_OPT_R(3) UAVQP_SWARM_OPT_R(4)

@@ -65,18 +65,33 @@ struct SwarmArgs {
 enum : int { SWARM_MOVING = 0, SWARM_WAITING = 1, SWARM_ARRIVED = 2 };
 
 // grad_coeff and grad_times of segment l of a vehicle (gc, W: the sums of the samples it owns; tail = sum_{m > l} W_m; P: the arrived samples)
-template <int NC>
+// ACC (internal, the swarm optimiser of uavqp_swarm_opt.h): ADD to what another penalty has left in the two arrays.  Every element has this
+// one owning lane, so the sum is race-free and its order fixed.  `any`: a sample has added to gc -- most segments of a flight see no
+// partner, and adding their zeros would be a read and a write of 3 x 2r doubles for nothing (x + 0 is x: the bytes are the same).
+template <int NC, bool ACC>
 __device__ __forceinline__ void swarm_store_segment(const SwarmArgs& a, size_t base, size_t axs, int s0, int l, int M, const double (&gc)[3][NC],
-                                                    double tail, double P) {
-    if (a.grad_coeff)
+                                                    double tail, double P, bool any) {
+    if (a.grad_coeff && (!ACC || any)) {
+        double* at = a.grad_coeff + base + (size_t)l * NC;
+        double old[3][NC];
+        if (ACC)   // (all loads before the first store: the compiler cannot know that the two do not overlap)
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax)
+#pragma unroll
+                for (int n = 0; n < NC; ++n) old[ax][n] = at[(size_t)ax * axs + n];
 #pragma unroll
         for (int ax = 0; ax < 3; ++ax)
 #pragma unroll
-            for (int n = 0; n < NC; ++n) a.grad_coeff[base + (size_t)ax * axs + (size_t)l * NC + n] = a.dt * gc[ax][n];
-    if (a.grad_times) a.grad_times[s0 + l] = l == M - 1 ? fma(a.dt, P, 0.0 - a.dt * tail) : 0.0 - a.dt * tail;   // (0 - x: never -0.0)
+            for (int n = 0; n < NC; ++n) at[(size_t)ax * axs + n] = ACC ? old[ax][n] + a.dt * gc[ax][n] : a.dt * gc[ax][n];
+    }
+    if (a.grad_times) {
+        const double gt = l == M - 1 ? fma(a.dt, P, 0.0 - a.dt * tail) : 0.0 - a.dt * tail;   // (0 - x: never -0.0)
+        if (!ACC) a.grad_times[s0 + l] = gt;
+        else if (gt != 0.0) a.grad_times[s0 + l] += gt;
+    }
 }
 
-template <int R>
+template <int R, bool ACC = false>
 __global__ __launch_bounds__(SWARM_BLOCK) void swarm_penalty_kernel(SwarmArgs a) {
     constexpr int NC = 2 * R, E = SWARM_ENTRIES;
     __shared__ double sh_q[3][E], sh_v[3][E], sh_G[3][E], sh_t[E], sh_phi[E], sh_rho[E];
@@ -97,9 +112,9 @@ __global__ __launch_bounds__(SWARM_BLOCK) void swarm_penalty_kernel(SwarmArgs a)
                 const int b = b0 + i;
                 const auto [s0, M] = poly_span(a.uniform, a.seg_offsets, b);
                 const size_t n_c = (size_t)3 * NC * (M > 0 ? M : 0), base = (size_t)3 * NC * s0;
-                if (a.grad_coeff)
+                if (!ACC && a.grad_coeff)   // (ACC: adding zero leaves what is there)
                     for (size_t n = 0; n < n_c; ++n) a.grad_coeff[base + n] = 0.0;
-                if (a.grad_times)
+                if (!ACC && a.grad_times)
                     for (int l = 0; l < M; ++l) a.grad_times[s0 + l] = 0.0;
                 if (a.grad_start) a.grad_start[b] = 0.0;
                 if (a.min_sep) a.min_sep[b] = INFINITY;
@@ -125,6 +140,7 @@ __global__ __launch_bounds__(SWARM_BLOCK) void swarm_penalty_kernel(SwarmArgs a)
             for (int n = 0; n < NC; ++n) gc[ax][n] = 0.0;
         int cur = M - 1;                       // the segment whose sums the registers hold
         double W = 0.0, tail = 0.0, P = 0.0;   // W of cur, sum of W over the segments behind it, the arrived samples
+        bool any = false;                      // a sample has added to gc of cur
         double phi_i = 0.0, rho_i = INFINITY;
 
         const int TS = A > 0 ? E / A : E;      // samples per tile (A <= SWARM_MAX <= E: at least one)
@@ -201,9 +217,10 @@ __global__ __launch_bounds__(SWARM_BLOCK) void swarm_penalty_kernel(SwarmArgs a)
                     if (G[0] == 0.0 && G[1] == 0.0 && G[2] == 0.0) continue;
                     const int code = sh_seg[e], seg = code >> 2, state = code & 3;
                     while (cur > seg) {   // the vehicle has left segment cur (going back in time): its sums are complete
-                        swarm_store_segment<NC>(a, base, axs, s0, cur, M, gc, tail, P);
+                        swarm_store_segment<NC, ACC>(a, base, axs, s0, cur, M, gc, tail, P, any);
                         tail += W;
                         W = 0.0;
+                        any = false;
 #pragma unroll
                         for (int ax = 0; ax < 3; ++ax)
 #pragma unroll
@@ -214,6 +231,7 @@ __global__ __launch_bounds__(SWARM_BLOCK) void swarm_penalty_kernel(SwarmArgs a)
                     const double Gv = fma(G[0], sh_v[0][e], fma(G[1], sh_v[1][e], G[2] * sh_v[2][e]));
                     if (state == SWARM_MOVING) W += Gv;
                     if (state == SWARM_ARRIVED) P += Gv;
+                    any = true;
                     double p = 1.0;
 #pragma unroll
                     for (int n = 0; n < NC; ++n) {
@@ -229,9 +247,10 @@ __global__ __launch_bounds__(SWARM_BLOCK) void swarm_penalty_kernel(SwarmArgs a)
         if (mine) {
             if (!live) W = 0.0;
             while (cur >= 0) {
-                swarm_store_segment<NC>(a, base, axs, s0, cur, M, gc, tail, P);
+                swarm_store_segment<NC, ACC>(a, base, axs, s0, cur, M, gc, tail, P, any);
                 tail += W;
                 W = 0.0;
+                any = false;
 #pragma unroll
                 for (int ax = 0; ax < 3; ++ax)
 #pragma unroll

@@ -39,6 +39,7 @@
 #include "qp_spacetime.h"
 #include "qp_spacetime_lbfgs.h"
 #include "qp_swarm.h"
+#include "qp_swarm_opt.h"
 // Measured-slower alternatives kept as bit-identical cross-checks: `make experiments` (-DUAVQP_EXPERIMENTS) only
 #ifdef UAVQP_EXPERIMENTS
 #include "cloud_grid2d.h"
@@ -70,6 +71,7 @@ UAVQP_INSTANCES_WPOPT
 UAVQP_INSTANCES_SPACETIME
 UAVQP_INSTANCES_SPACETIME_LBFGS
 UAVQP_INSTANCES_SWARM
+UAVQP_INSTANCES_SWARM_OPT
 #endif
 
 namespace uavqp {
@@ -1956,6 +1958,7 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
 // Separation penalty between the vehicles of a swarm on a shared clock
 // ===================================================================================================
 #include "uavqp_swarm.h"
+#include "uavqp_swarm_opt.h"
 
 // ===================================================================================================
 // N3: quadrotor_msgs/PolynomialTrajectory packer (host only)

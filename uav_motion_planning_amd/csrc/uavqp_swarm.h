@@ -44,7 +44,7 @@ static int swarm_args_check(uavqp_ctx* ctx, int r, int n_traj, int uniform_segme
 static int swarm_penalty_enqueue(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
                                  const double* d_coeff, const int32_t* d_status, int n_groups, const int32_t* d_group_offsets,
                                  const double* d_start, const uavqp_swarm_params& S, double* d_penalty, double* d_grad_coeff,
-                                 double* d_grad_times, double* d_grad_start, double* d_min_sep) {
+                                 double* d_grad_times, double* d_grad_start, double* d_min_sep, bool accumulate = false) {
     uavqp::SwarmArgs a;
     a.n_traj = n_traj; a.uniform = uniform_segments; a.n_groups = n_groups; a.seg_offsets = d_seg_offsets; a.group_offsets = d_group_offsets;
     a.times = d_times; a.coeff = d_coeff; a.status = d_status; a.start = d_start;
@@ -55,7 +55,12 @@ static int swarm_penalty_enqueue(uavqp_ctx* ctx, int r, int n_traj, int uniform_
     // one workgroup per swarm, grid-stride past 5 resident workgroups per CU (the LDS of qp_swarm.h)
     const int cap = ctx->num_cus * 5;
     const int grid = n_groups < cap ? n_groups : cap;
-    if (r == 3)
+    // accumulate (uavqp_swarm_opt.h only, not in the C ABI): grad_coeff and grad_times are ADDED to what the arrays hold
+    if (accumulate && r == 3)
+        hipLaunchKernelGGL((uavqp::swarm_penalty_kernel<3, true>), dim3(grid), dim3(uavqp::SWARM_BLOCK), 0, ctx->stream, a);
+    else if (accumulate)
+        hipLaunchKernelGGL((uavqp::swarm_penalty_kernel<4, true>), dim3(grid), dim3(uavqp::SWARM_BLOCK), 0, ctx->stream, a);
+    else if (r == 3)
         hipLaunchKernelGGL(uavqp::swarm_penalty_kernel<3>, dim3(grid), dim3(uavqp::SWARM_BLOCK), 0, ctx->stream, a);
     else
         hipLaunchKernelGGL(uavqp::swarm_penalty_kernel<4>, dim3(grid), dim3(uavqp::SWARM_BLOCK), 0, ctx->stream, a);

@@ -445,6 +445,70 @@ class Context:
         return waypoints, times, coeff, status, objective, accepted, peak, min_dist, outside
 
     @staticmethod
+    def _swarm_opt_params(params):
+        pp = _lib.SwarmOptParams()
+        _lib.lib().uavqp_default_swarm_opt_params(ctypes.byref(pp))
+        for k, v in params.items():
+            if not hasattr(pp, k) or k == "struct_size":
+                raise ValueError(f"unknown uavqp_swarm_opt_params field {k!r}")
+            setattr(pp, k, v)
+        return pp
+
+    def swarm_optimize_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc, esdf,
+                              coeff_out, status_out, objective_out, n_groups=1, group_offsets=None, start=None, accepted_out=None,
+                              peak_out=None, min_dist_out=None, outside_out=None, min_sep_out=None, limits=None, clearance=None, swarm=None,
+                              **params):
+        """uavqp_swarm_optimize_device on device buffers: spacetime_optimize_device with the swarm separation penalty in the objective and
+        ONE accept / reject per swarm.  `waypoints`, `times` and (start_window > 0) `start` hold the start and receive the result;
+        objective_out [n_groups][2] and accepted_out [n_groups] are per SWARM (trajectories group_offsets[g] .. group_offsets[g + 1]; None
+        with n_groups = 1: the whole batch), the diagnostics peak_out / min_dist_out / outside_out / min_sep_out per vehicle.  limits /
+        clearance / swarm: dicts of uavqp_limit_params / uavqp_clearance_params / uavqp_swarm_params fields; params: fields of
+        uavqp_swarm_opt_params that differ from the defaults.  All penalties are soft and the result is a local minimum (include/uavqp.h).
+        Asynchronous."""
+        pp = self._swarm_opt_params(params)
+        lp, cp, sp = self._limit_params(limits or {}), self._clearance_params(clearance or {}), self._swarm_params(swarm or {})
+        rc = _lib.lib().uavqp_swarm_optimize_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), _ptr(seg_offsets),
+                                                    _ptr(waypoints), _ptr(times), _ptr(bc), int(n_groups), _ptr(group_offsets), _ptr(start),
+                                                    getattr(esdf, "handle", esdf), ctypes.byref(lp), ctypes.byref(cp), ctypes.byref(sp),
+                                                    ctypes.byref(pp), _ptr(coeff_out), _ptr(status_out), _ptr(objective_out),
+                                                    _ptr(accepted_out), _ptr(peak_out), _ptr(min_dist_out), _ptr(outside_out),
+                                                    _ptr(min_sep_out))
+        _lib.check(rc, "uavqp_swarm_optimize_device")
+
+    def swarm_optimize_host(self, r, seg_offsets, waypoints, times, bc, esdf, group_offsets=None, start=None, uniform_segments=0, limits=None,
+                            clearance=None, swarm=None, **params):
+        """numpy in / numpy out (synchronous; the map stays on the device).  group_offsets None: the whole batch is one swarm; start None:
+        all departures zero (and fixed).  Returns (waypoints [sum (M + 1)][3], times [sum M], start [n_traj] or None, coeff_flat, status,
+        objective [n_groups][2], accepted [n_groups], peak [n_traj][2], min_dist [n_traj], outside [n_traj] int32, min_sep [n_traj])."""
+        waypoints = np.array(waypoints, dtype=np.float64).reshape(-1, 3)   # copies: the call updates all three in place
+        times = np.array(times, dtype=np.float64).ravel()
+        bc = np.ascontiguousarray(bc, dtype=np.float64)
+        so, n_traj, total, mmax = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total
+        assert waypoints.size == 3 * (total + n_traj), "waypoints must hold sum(M_b + 1) xyz rows"
+        assert bc.size == n_traj * 2 * (r - 1) * 3
+        go = None if group_offsets is None else np.ascontiguousarray(group_offsets, dtype=np.int32)
+        n_groups = 1 if go is None else go.size - 1
+        start = None if start is None else np.array(start, dtype=np.float64).ravel()
+        assert start is None or start.size == n_traj
+        pp = self._swarm_opt_params(params)
+        lp, cp, sp = self._limit_params(limits or {}), self._clearance_params(clearance or {}), self._swarm_params(swarm or {})
+        coeff = np.zeros(3 * 2 * r * total, dtype=np.float64)
+        status = np.zeros(n_traj, dtype=np.int32)
+        objective = np.zeros((n_groups, 2), dtype=np.float64)
+        accepted = np.zeros(n_groups, dtype=np.int32)
+        peak = np.zeros((n_traj, 2), dtype=np.float64)
+        min_dist = np.zeros(n_traj, dtype=np.float64)
+        outside = np.zeros(n_traj, dtype=np.int32)
+        min_sep = np.zeros(n_traj, dtype=np.float64)
+        rc = _lib.lib().uavqp_swarm_optimize_host(self._h, r, n_traj, uniform_segments, max(mmax, 1), _ptr(so), _ptr(waypoints), _ptr(times),
+                                                  _ptr(bc), n_groups, _ptr(go), _ptr(start), getattr(esdf, "handle", esdf), ctypes.byref(lp),
+                                                  ctypes.byref(cp), ctypes.byref(sp), ctypes.byref(pp), _ptr(coeff), _ptr(status),
+                                                  _ptr(objective), _ptr(accepted), _ptr(peak), _ptr(min_dist), _ptr(outside), _ptr(min_sep))
+        _lib.check(rc, "uavqp_swarm_optimize_host")
+        return waypoints, times, start, coeff, status, objective, accepted, peak, min_dist, outside, min_sep
+
+    @staticmethod
     def _spacetime_lbfgs_params(params):
         pp = _lib.SpacetimeLbfgsParams()
         _lib.lib().uavqp_default_spacetime_lbfgs_params(ctypes.byref(pp))
@@ -874,6 +938,8 @@ class TrajOptimizer:
     setSwarm(group_offsets, start_times)   which trajectories fly together (swarm g = trajectories group_offsets[g] .. group_offsets[g + 1];
                                      None: the whole batch is one swarm) and when each departs on its swarm's clock (None: all at 0)
     getSwarmPenalty(...)             [n_groups] separation penalty between the vehicles of each swarm at the stored coefficients
+    optimizeSwarm(esdf, ...)         optimizeTrajectory with that penalty in the objective and one accept / reject per SWARM; with
+                                     start_window > 0 the departures are optimised too (getSwarmStart()); .min_sep per trajectory
     getCostWaypointGradient()        [sum (M_b + 1)][3] gradient of getCost() in the waypoints, both ends of every trajectory included
     backward(grad_coeff)             equality-constrained problems only, after solve(): (grad_times, grad_waypoints, grad_bc) of a loss
                                      with d loss / d getPolyCoeff() = grad_coeff, through the solve
@@ -1094,6 +1160,38 @@ class TrajOptimizer:
             raise _lib.UavqpError("getSwarmPenalty: no solved coefficients (call solve() or optimizeTime() first)")
         return self._ctx.swarm_penalty_host(self._r, self._so, self._T, self._coef, group_offsets=self._groups, start=self._start,
                                             status=self.status, **params)[0]
+
+    def optimizeSwarm(self, esdf, limits=None, clearance=None, swarm=None, **params):
+        """optimizeTrajectory for the swarms set with setSwarm() (uavqp_swarm_optimize_host): the separation penalty between the vehicles
+        of each swarm joins the objective and every trial is accepted or rejected per SWARM.  With start_window > 0 the departures of
+        setSwarm() are optimised too and the new ones stored (getSwarmStart()).  The reference's equality rows only: a corridor or rows
+        set raises ValueError.  True iff every trajectory is solved at the result.  limits / clearance / swarm: dicts of
+        uavqp_limit_params / uavqp_clearance_params / uavqp_swarm_params fields; params: fields of uavqp_swarm_opt_params that differ from
+        the defaults (an unknown field raises ValueError).  Fills the members optimizeTrajectory fills -- .objective [n_groups][2] and
+        .iterations [n_groups] per swarm -- and .min_sep [n_traj].  All penalties are soft (include/uavqp.h)."""
+        if self._lo is not None or self._rows is not None:
+            raise ValueError("optimizeSwarm: corridor and general-rows problems are out of scope (include/uavqp.h)")
+        pp = Context._swarm_opt_params(params)   # (an unknown field is refused before anything runs)
+        Context._swarm_params(swarm or {})
+        if self._wp is None or self._T is None:
+            return False
+        n_traj = self._so.size - 1
+        if self._T.size != int(self._so[-1]):
+            return False
+        bc = self._bc if self._bc is not None else np.zeros((n_traj, 2, self._r - 1, 3))
+        start = self._start
+        if start is None and pp.start_window > 0.0:
+            start = np.zeros(n_traj, dtype=np.float64)
+        ctx = self.context()
+        (self._wp, self._T, start, self._coef, self.status, self.objective, self.iterations, self.peak, self.min_dist, self.outside,
+         self.min_sep) = ctx.swarm_optimize_host(self._r, self._so, self._wp, self._T, bc, esdf, group_offsets=self._groups, start=start,
+                                                 limits=limits, clearance=clearance, swarm=swarm, **params)
+        self._start = start
+        return bool(np.all(self.status == _lib.UAVQP_SOLVED))
+
+    def getSwarmStart(self):
+        """[n_traj] the departures of setSwarm(), as optimizeSwarm() left them (None: all at 0)."""
+        return None if self._start is None else self._start.copy()
 
     def context(self):
         """The Context this optimiser solves on (created on first use): what an esdf.EsdfMap for getClearancePenalty is built on."""
