@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "qp_core_kernels.h"
+#include "qp_twisted_map.h"
 #include "qp_wave_utils.h"
 
 #ifndef UAVQP_STAMP   // (probe builds under tools/ubench define their own: per-wave timelines)
@@ -68,6 +69,8 @@ struct TwistedCfg {
 
 // ONE (latency shapes): the launch has exactly one WHOLE tile per wave (grid == n_tiles, n_traj % TILE == 0 -- the host checks both):
 // no shifted or guarded tile, no prefetch and no second input buffer, nothing that depends on the batch size; the tile loop makes one trip.
+// (It must stay that way: the ONE instantiation never reads n_traj, and tools/ubench/twisted_phases.hip passes the timeline slab of a
+// back-to-back launch in that argument.  Every use of a.n_traj below sits behind an `ONE ?` / `if constexpr (ONE)`.)
 //
 // Arguments: FLAT, one signature for every tile shape, the three arrays the LDS-DMA needs in front.  The translation units of this kernel
 // are compiled with the leading six arguments preloaded into SGPRs at wave launch (csrc/Makefile: TWISTED_FLAGS; a struct passed by
@@ -92,6 +95,11 @@ struct TwistedArgs {   // what the body reads: the kernel's own arguments under 
     long long* stamps;
 #endif
 };
+constexpr bool twmap_plain_rows() {   // qp_twisted_map.h with one lane pair per axis is the plain decode the 8-lane shape spells out
+    for (int rest = 0; rest < 16; ++rest)
+        if (twmap_rest_side<1>(rest) != (rest & 1) || twmap_rest_sub<1>(rest) != 0 || twmap_rest_traj<1>(rest) != rest >> 1) return false;
+    return true;
+}
 template <int R, int M, int TILE, int LPT = 2, bool ONE = false>
 __global__ __launch_bounds__(64, 1) void solve_twisted_kernel(const double* waypoints, const double* times, const double* bc, double* coeff,
                                                               int32_t* status, int n_traj UAVQP_TWISTED_STAMPS_PARAM) {
@@ -397,8 +405,15 @@ __global__ __launch_bounds__(64, 1) void solve_twisted_kernel(const double* wayp
                 }
             }
             // LPT == 16: two lane pairs per (trajectory, axis) repeat elimination and back-substitution and split the EMISSION --
-            // pair `sub` evaluates the own segments sub * H .. sub * H + H - 1 (selects between the two compile-time candidates, one
-            // instruction stream): 4 trajectories per wave, a 4096-trajectory batch fills all 1024 SIMDs.
+            // in step s pair `sub` evaluates the own segment s * NSUB + sub (selects between compile-time candidates, one instruction
+            // stream): 4 trajectories per wave, a 4096-trajectory batch fills all 1024 SIMDs.  The two pairs of a side emit ADJACENT
+            // segments in the same step, and the staging rows of a trajectory are ordered by address (side 0 sub 0, side 0 sub 1,
+            // side 1 sub 1, side 1 sub 0: the reversed lanes' segments descend), so that for r = 4 and even M a step's copy-out writes
+            // whole 128-byte lines, each from eight adjacent lanes (M = 8: 16 lines per instruction, no partial line; odd mL leaves the
+            // two halves of the middle line to the last step), and for r = 3 96-byte runs.  Before, pair `sub` emitted sub * H + s:
+            // every store wrote 64-byte halves of 32 different lines, the other half a step later, and write-through halves are not
+            // merged in L2 (tools/ubench/write_patterns.hip patterns 9 / 8).  The map -- (lane, step) -> trajectory, side, segment,
+            // column, keep or drop -- is qp_twisted_map.h, shared with tests/cpp/test_twisted_map.cpp.
             //
             // Copy-out, software-pipelined (what the per-wave timelines of tools/ubench/tw asked for: a vector-memory store costs the
             // wave ~100 cycles of issue, sixteen scattered quarter-chunk stores per lane were 1100 of the emission's 3400 cycles and left
@@ -427,20 +442,34 @@ __global__ __launch_bounds__(64, 1) void solve_twisted_kernel(const double* wayp
             typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
             // the piece this lane copies (the same row slot for the three axes)
             const int c_rest = lane >> 2, c_col = lane & 3;
-            const int c_R = c_rest & 1, c_sub = NSUB == 2 ? (c_rest >> 1) & 1 : 0, c_tl = c_rest >> NSUB;
+            // (NSUB == 1: the map's decode written out -- the 8-lane shape's instruction stream is left exactly as it was)
+            static_assert(twmap_plain_rows(), "one lane pair per axis: rest = trajectory * 2 + side");
+            const int c_R = NSUB == 2 ? twmap_rest_side<NSUB>(c_rest) : c_rest & 1, c_sub = NSUB == 2 ? twmap_rest_sub<NSUB>(c_rest) : 0,
+                      c_tl = NSUB == 2 ? twmap_rest_traj<NSUB>(c_rest) : c_rest >> 1;
+            static_assert(twmap_side_segments(M, 0) == mL && twmap_side_segments(M, 1) == mR, "the map's sides are the kernel's");
             const int c_m = c_R ? mR : mL;
             const bool c_keep = (c_col < NC / 2) && ((okmask >> (LPT * c_tl)) & 1ull);
             const unsigned c_off = (unsigned)(((c_tl * 3 * M) * NC + 2 * c_col) * 8);   // + axis * M * NC * 8 + segment * NC * 8
             const int c_lds = c_rest * RS + 2 * c_col;
-            const int my_rest = NSUB == 2 ? tlc * 4 + sub * 2 + isR : tlc * 2 + isR;
+            const int my_rest = twmap_rest<NSUB>(tlc, sub, isR);
             const int my_lds = axl < 3 ? row_addr(axl, my_rest) : 48 * RS + 16 + (lane & 15) * RS;
             auto flush = [&](int sp) {   // copy-out of step sp: NIT LDS reads, NIT stores
                 double2 v[NIT];
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) v[it] = *reinterpret_cast<const double2*>(s_out + row_addr(it, 0) + c_lds);
-                const int jv = c_sub * H + sp;                                    // own segment of the producing lane
-                const int cseg = c_R ? (M - 1 - jv) : jv;
-                const unsigned off0 = (c_keep && jv < c_m) ? c_off + (unsigned)(cseg * NC * 8) : 0xFFFFFFF0u;
+                const int jv = twmap_own_segment<NSUB>(sp, c_sub);               // own segment of the producing lane
+                const int cseg = twmap_global_segment(M, c_R, jv);
+#if defined(UAVQP_TW_DROP_STORES) && !defined(UAVQP_TIMING_BUILD)
+#error "UAVQP_TW_DROP_STORES produces WRONG results: timing harness only (tools/ubench/twisted_phases4_one_nostores, built with -DUAVQP_TIMING_BUILD), never libuavqp.so"
+#endif
+                unsigned off0 = (c_keep && jv < c_m) ? c_off + (unsigned)(cseg * NC * 8) : 0xFFFFFFF0u;
+#ifdef UAVQP_TW_DROP_STORES   // timing-only build: EVERY piece gets the out-of-range offset (offsets are multiples of 16: or-ing the mask in gives exactly
+                // 0xFFFFFFF0) -- the same instructions plus one v_or, the hardware drops all stores.  Against the product this bounds what any change
+                // to the store path can return; no coefficient is written
+                unsigned tw_drop = 0xFFFFFFF0u;
+                asm volatile("" : "+s"(tw_drop));   // (opaque: the address arithmetic stays)
+                off0 |= tw_drop;
+#endif
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) {
                     u32x4 w;
@@ -454,7 +483,7 @@ __global__ __launch_bounds__(64, 1) void solve_twisted_kernel(const double* wayp
 #pragma unroll
             for (int s = 0; s < H; ++s) {
                 if (s > 0) flush(s - 1);
-                const int j = s + sub * H;
+                const int j = twmap_own_segment<NSUB>(s, sub);
                 const bool act = (j < m);
                 const int jc = act ? j : (m > 0 ? m - 1 : 0);
                 const double pj = pos(jc, 0), pj1 = pos(jc + 1, 0);
@@ -463,18 +492,18 @@ __global__ __launch_bounds__(64, 1) void solve_twisted_kernel(const double* wayp
                 for (int d = 0; d < ND; ++d) {
                     const double fs = ((d & 1) == 0) ? -1.0 : 1.0;
                     auto Y = [&](int q) -> double { return (q >= mL || q == m) ? ynext[d][0] : h[q < mL ? q : mL - 1][d][0]; };
-                    double yj = h[s][d][0], yj1 = Y(s + 1);
+                    double yj = h[NSUB * s][d][0], yj1 = Y(NSUB * s + 1);
                     if constexpr (NSUB == 2) {
-                        const int jb = (H + s < mL) ? H + s : mL - 1;
+                        // pair 1 emits the segment behind pair 0's: its start is pair 0's end -- Y(2 s + 1) is h[2 s + 1] wherever pair 1 has
+                        // a segment (2 s + 1 < m), and where it has none its chunk is dropped -- so three candidates serve the two selects
                         // (the candidates are pinned as VALUES first: left alone, the optimiser turns a select between two elements of h
                         // into ONE load through a selected pointer before the loops are unrolled -- and h, indexed at run time, goes to
                         // scratch: 32-48 bytes per lane in the M = 3, 4, 5 shapes)
-                        double alt = h[jb][d][0], alt1 = Y(H + s + 1);
-                        asm("" : "+v"(alt));
+                        double alt1 = Y(2 * s + 2);
                         asm("" : "+v"(yj));
                         asm("" : "+v"(alt1));
                         asm("" : "+v"(yj1));
-                        yj = sub ? alt : yj;
+                        yj = sub ? yj1 : yj;
                         yj1 = sub ? alt1 : yj1;
                     }
                     ys[d] = isR ? fs * yj1 : yj;
