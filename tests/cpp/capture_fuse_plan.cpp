@@ -1,0 +1,53 @@
+// What uavqp_capture_end makes of a capture, from the host rules alone (uav_motion_planning_amd/csrc/uavqp_capture.h: lay_out, fuse_groups;
+// kernel_instances.h: which shapes have a group kernel), without the HIP runtime: tests/test_gpu_capture_fuse.py hands this program the
+// solves it captured and reads back which of them share a launch.
+// stdin:  "lanes nodes_per_lane F num_cus count", then per solve "r M tile n_traj waypoints times bc coeff status" (addresses, 0 = none)
+// stdout: one line per launch of the replay, "stage lane node node ..."
+#include <cstdint>
+#include <cstdio>
+#include <vector>
+
+#include "kernel_instances.h"
+#include "uavqp_capture.h"
+
+using namespace uavqp_capture;
+
+int main() {
+    int lanes = 0, per_lane = 0, F = 0, num_cus = 0, count = 0;
+    if (std::scanf("%d %d %d %d %d", &lanes, &per_lane, &F, &num_cus, &count) != 5 || count < 0 || count > (int)NODES_MAX) return 2;
+    std::vector<Record> rec;
+    std::vector<Shape> shape;
+    for (int k = 0; k < count; ++k) {
+        int r = 0, M = 0, tile = 0, n_traj = 0;
+        unsigned long long p[5];
+        if (std::scanf("%d %d %d %d %llu %llu %llu %llu %llu", &r, &M, &tile, &n_traj, &p[0], &p[1], &p[2], &p[3], &p[4]) != 9) return 2;
+        if (tile < 1 || n_traj < 1 || M < 1 || r < 1) return 2;
+        // the extents and the launch shape of uavqp_solve_batch_device (uavqp.hip: capture_note, the tile rule)
+        const size_t n = (size_t)n_traj, tot = n * (size_t)M;
+        Record x;
+        x.read[0] = range_of((const void*)(uintptr_t)p[0], sizeof(double) * 3 * (tot + n));
+        x.read[1] = range_of((const void*)(uintptr_t)p[1], sizeof(double) * tot);
+        x.read[2] = range_of((const void*)(uintptr_t)p[2], sizeof(double) * n * 2 * (size_t)(r - 1) * 3);
+        x.coeff = range_of((const void*)(uintptr_t)p[3], sizeof(double) * 3 * 2 * (size_t)r * tot);
+        x.status = range_of((const void*)(uintptr_t)p[4], sizeof(int32_t) * n);
+        rec.push_back(x);
+        const int n_tiles = (n_traj + tile - 1) / tile, max_wg = num_cus * 4;
+        Shape s;
+        s.fn = (const void*)(uintptr_t)(r * 10000 + M * 100 + tile);   // one kernel function per (r, M, tile)
+        s.grid = (unsigned)(n_tiles < max_wg ? n_tiles : max_wg);
+        s.block = 64;
+        s.n_traj = n_traj;
+        s.one = (int)s.grid == n_tiles && n_traj % tile == 0 && uavqp_twisted_group_exists(r, M, tile);
+        shape.push_back(s);
+    }
+    const std::vector<char> dead = dead_status_stores(rec);
+    const Fused f = fuse_groups(rec, dead, lay_out(rec, dead, lanes), shape, F, lanes, per_lane);
+    for (size_t s = 0; s < f.group.size(); ++s)
+        for (size_t l = 0; l < f.group[s].size(); ++l)
+            for (const std::vector<int>& g : f.group[s][l]) {
+                std::printf("%d %d", (int)s, (int)l);
+                for (int k : g) std::printf(" %d", k);
+                std::printf("\n");
+            }
+    return 0;
+}

@@ -33,6 +33,27 @@
     UAVQP_INST __global__ void uavqp::solve_twisted_kernel<R_, M_, 8, 8, true>(UAVQP_TWISTED_SIG);
 #define UAVQP_INSTANCES_TWISTED3_ONE UAVQP_TWISTED_PAIRS3(UAVQP_TWISTED_SHAPES_ONE)
 #define UAVQP_INSTANCES_TWISTED4_ONE UAVQP_TWISTED_PAIRS4(UAVQP_TWISTED_SHAPES_ONE)
+// and the group kernel, several one-tile-per-wave solves in one launch (k_twisted3_group.hip / k_twisted4_group.hip), for those of the
+// latency shapes whose wave fits THREE to a SIMD: at most 168 VGPRs, no scratch (the group kernel has the register count of the
+// one-tile-per-wave kernel of its shape: both are qp_twisted_body.h; tests/test_capture_fuse.py reads the counts from a cross-compile).
+// The others -- 16 lanes: (4, 7) 182, (4, 9) 210, (4, 10) 182, (4, 12) 216;  8 lanes: (4, 5) 190, (4, 7) 228, (4, 8) 200, (4, 9) 264, (4, 10) 240,
+// (4, 12) 266, (3, 12) 184, (3, 16) 234 -- have no group kernel and are replayed one launch per solve.
+#define UAVQP_GROUP_PAIRS4_T4(X) X(4, 2) X(4, 3) X(4, 4) X(4, 5) X(4, 6) X(4, 8)
+#define UAVQP_GROUP_PAIRS4_T8(X) X(4, 2) X(4, 3) X(4, 4) X(4, 6)
+#define UAVQP_GROUP_PAIRS3_T4(X) UAVQP_TWISTED_PAIRS3(X)
+#define UAVQP_GROUP_PAIRS3_T8(X) X(3, 2) X(3, 3) X(3, 4) X(3, 5) X(3, 6) X(3, 7) X(3, 8) X(3, 10)
+#define UAVQP_TWISTED_GROUP_T4(R_, M_) UAVQP_INST __global__ void uavqp::solve_twisted_group_kernel<R_, M_, 4, 16>(UAVQP_TWISTED_GROUP_SIG);
+#define UAVQP_TWISTED_GROUP_T8(R_, M_) UAVQP_INST __global__ void uavqp::solve_twisted_group_kernel<R_, M_, 8, 8>(UAVQP_TWISTED_GROUP_SIG);
+#define UAVQP_INSTANCES_TWISTED3_GROUP UAVQP_GROUP_PAIRS3_T4(UAVQP_TWISTED_GROUP_T4) UAVQP_GROUP_PAIRS3_T8(UAVQP_TWISTED_GROUP_T8)
+#define UAVQP_INSTANCES_TWISTED4_GROUP UAVQP_GROUP_PAIRS4_T4(UAVQP_TWISTED_GROUP_T4) UAVQP_GROUP_PAIRS4_T8(UAVQP_TWISTED_GROUP_T8)
+// the same lists for host code without the HIP runtime (tests): is there a group kernel for (r, M) at this tile?
+static inline bool uavqp_twisted_group_exists(int r, int M, int tile) {
+#define UAVQP_GROUP_HAS(R_, M_) if (r == R_ && M == M_) return true;
+    if (tile == 4) { UAVQP_GROUP_PAIRS4_T4(UAVQP_GROUP_HAS) UAVQP_GROUP_PAIRS3_T4(UAVQP_GROUP_HAS) }
+    if (tile == 8) { UAVQP_GROUP_PAIRS4_T8(UAVQP_GROUP_HAS) UAVQP_GROUP_PAIRS3_T8(UAVQP_GROUP_HAS) }
+#undef UAVQP_GROUP_HAS
+    return false;
+}
 
 // ---- qp_core_kernels.h / qp_generic2.h: the ragged solvers
 #define UAVQP_GENERIC_R(R_)                                                                \

@@ -47,13 +47,16 @@
 #endif
 
 // the solver families are compiled as their own translation units (k_*.hip): here their instantiations are only DECLARED
-// (-DUAVQP_SINGLE_TU: a build that includes this file whole -- tools/ubench/twisted_phases.hip -- instantiates everything itself)
-#ifndef UAVQP_SINGLE_TU
+// (-DUAVQP_SINGLE_TU: a build that includes this file whole -- tools/ubench/twisted_phases.hip -- instantiates everything itself; the
+//  lists are read in either build: find_twisted_group goes by them)
 #include "kernel_instances.h"
+#ifndef UAVQP_SINGLE_TU
 UAVQP_INSTANCES_TWISTED3
 UAVQP_INSTANCES_TWISTED4
 UAVQP_INSTANCES_TWISTED3_ONE
 UAVQP_INSTANCES_TWISTED4_ONE
+UAVQP_INSTANCES_TWISTED3_GROUP
+UAVQP_INSTANCES_TWISTED4_GROUP
 UAVQP_INSTANCES_GENERIC
 UAVQP_INSTANCES_CORRIDOR
 UAVQP_INSTANCES_CORRIDOR_DUAL
@@ -118,6 +121,17 @@ static twisted_fn find_twisted(int r, int M, int tile, bool one) {
     UAVQP_CASE(3, 2) UAVQP_CASE(3, 3) UAVQP_CASE(3, 4) UAVQP_CASE(3, 5) UAVQP_CASE(3, 6) UAVQP_CASE(3, 7)
     UAVQP_CASE(3, 8) UAVQP_CASE(3, 10) UAVQP_CASE(3, 12) UAVQP_CASE(3, 16)
 #undef UAVQP_CASE
+    return nullptr;
+}
+// The group kernel of a launch that takes the one-tile-per-wave instantiation of (r, M) at this tile, or null where the shape has none
+// (kernel_instances.h: the lists): what uavqp_capture_end replays several independent solves of one shape with.
+static const void* find_twisted_group(int r, int M, int tile) {
+#define UAVQP_CASE4(RR, MM) if (tile == 4 && r == RR && M == MM) return (const void*)&solve_twisted_group_kernel<RR, MM, 4, 16>;
+#define UAVQP_CASE8(RR, MM) if (tile == 8 && r == RR && M == MM) return (const void*)&solve_twisted_group_kernel<RR, MM, 8, 8>;
+    UAVQP_GROUP_PAIRS4_T4(UAVQP_CASE4) UAVQP_GROUP_PAIRS3_T4(UAVQP_CASE4)
+    UAVQP_GROUP_PAIRS4_T8(UAVQP_CASE8) UAVQP_GROUP_PAIRS3_T8(UAVQP_CASE8)
+#undef UAVQP_CASE4
+#undef UAVQP_CASE8
     return nullptr;
 }
 }  // namespace uavqp
@@ -201,6 +215,7 @@ struct CapturedLaunch {
     dim3 grid, block;
     unsigned int lds_bytes = 0;
     BatchArgs args{};  // fn != null: a solve_twisted_kernel launch, re-added through TwistedParams (a barrier launch is re-added with the parameters of its captured node)
+    const void* group_fn = nullptr;   // the launch took the one-tile-per-wave instantiation and its shape has a group kernel: that kernel
 };
 
 struct uavqp_ctx {
@@ -248,7 +263,7 @@ struct uavqp_ctx {
 };
 
 // (capture only) remember a launch just made on the ctx stream; `a` null = a launch that cannot be analysed (a barrier)
-static void capture_note(uavqp_ctx* ctx, const void* fn, dim3 grid, dim3 block, size_t lds_bytes, const BatchArgs* a, int r) {
+static void capture_note(uavqp_ctx* ctx, const void* fn, dim3 grid, dim3 block, size_t lds_bytes, const BatchArgs* a, int r, const void* group_fn = nullptr) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusActive) {   // the capture ended behind the library's back
         ctx->capturing = false;
@@ -258,6 +273,7 @@ static void capture_note(uavqp_ctx* ctx, const void* fn, dim3 grid, dim3 block, 
     }
     CapturedLaunch l;
     l.fn = fn; l.grid = grid; l.block = block; l.lds_bytes = (unsigned int)lds_bytes;
+    l.group_fn = a ? group_fn : nullptr;
     uavqp_capture::Record rec;
     rec.barrier = a == nullptr;
     if (a) {
@@ -508,7 +524,8 @@ extern "C" int uavqp_solve_batch_device(uavqp_ctx* ctx, int r, int n_traj, int u
             a.ws = nullptr;
             uavqp::TwistedParams tp(a);
             UAVQP_HIP(hipLaunchKernel((const void*)fn, dim3(g), dim3(64), tp.ptr, 0, ctx->stream));
-            if (ctx->capturing) capture_note(ctx, (const void*)fn, dim3(g), dim3(64), 0, &a, r);   // no workspace of the ctx: the one analysable launch
+            if (ctx->capturing)   // no workspace of the ctx: the one analysable launch
+                capture_note(ctx, (const void*)fn, dim3(g), dim3(64), 0, &a, r, one ? uavqp::find_twisted_group(r, uniform_segments, tile) : nullptr);
             return UAVQP_OK;
         }
         if (ctx->variant == 2) {
@@ -744,45 +761,66 @@ struct CapturedGraph {
 // The same launches as `captured`, ordered by what they touch instead of by when they were enqueued (uavqp_capture.h): independent solves
 // go to different lanes, at most `lanes` of them, and a solve that conflicts with an earlier one follows it in that one's lane.  False when the capture is not exactly the recorded launches of
 // uavqp_solve_batch_device, when nothing in it is independent, or when the runtime refuses a step: the caller keeps the captured graph.
+// Within a lane, up to `fuse` solves of one shape that follow each other and touch disjoint buffers become ONE launch of the group kernel
+// (uavqp_capture.h: fuse_groups; qp_twisted.h: solve_twisted_group_kernel) -- also where the replay stays on one lane.
 // (Measured: ONE graph with parallel branches replays slower than the captured chain -- the runtime leaves its single-queue fast path --
 //  so every lane of a stage is a chain graph of its own: docs/measurement_log.md.)
-static bool rebuild_captured(uavqp_ctx* ctx, hipGraph_t captured, int lanes, int nodes_per_lane, CapturedGraph& out) {
+static bool rebuild_captured(uavqp_ctx* ctx, hipGraph_t captured, int lanes, int nodes_per_lane, int fuse, CapturedGraph& out) {
+    static_assert(uavqp::GROUP_MAX == uavqp_capture::FUSE_MAX, "a group's pointer sets travel in one kernarg struct");
     const size_t n = ctx->cap_launch.size();
-    if (lanes <= 1 || n < 2 || n != ctx->cap_rec.size()) return false;
+    if (lanes < 1) lanes = 1;
+    if ((lanes == 1 && fuse <= 1) || n < 2 || n != ctx->cap_rec.size()) return false;
     std::vector<hipGraphNode_t> order;
     if (!captured_chain(captured, order) || order.size() != n) return false;
     std::vector<hipKernelNodeParams> params(n);
+    std::vector<uavqp_capture::Shape> shape(n);
     for (size_t k = 0; k < n; ++k) {
         const CapturedLaunch& l = ctx->cap_launch[k];
         hipKernelNodeParams& p = params[k];
         if (hipGraphKernelNodeGetParams(order[k], &p) != hipSuccess) return false;
         if ((l.fn && p.func != l.fn) || p.gridDim.x != l.grid.x || p.gridDim.y != l.grid.y || p.gridDim.z != l.grid.z) return false;
+        uavqp_capture::Shape& sh = shape[k];
+        sh.fn = l.fn; sh.grid = l.grid.x; sh.block = l.block.x; sh.lds_bytes = l.lds_bytes; sh.n_traj = l.args.n_traj;
+        sh.one = l.fn && l.group_fn && l.grid.y == 1 && l.grid.z == 1;   // (one kernel function: one group kernel)
     }
     if (n > uavqp_capture::NODES_MAX) return false;
     const std::vector<char> status_dead = uavqp_capture::dead_status_stores(ctx->cap_rec);
     const uavqp_capture::Layout lay = uavqp_capture::lay_out(ctx->cap_rec, status_dead, lanes);
-    if (!lay.parallel) return false;
-    std::vector<int> starts = lay.starts;
-    starts.push_back((int)n);
-    bool side_by_side = false;
     // (The width of a stage goes by its launches in all, not by how they are spread: a stage that is one long chain and a few single
     //  solves pays a fork / join for each of those.  A rotation, what the layout is for, deals its chains evenly.)
-    for (size_t s = 0; s + 1 < starts.size(); ++s) {
-        const int first = starts[s], width = uavqp_capture::lanes_that_pay(starts[s + 1] - first, lanes, nodes_per_lane);
+    const uavqp_capture::Fused plan = uavqp_capture::fuse_groups(ctx->cap_rec, status_dead, lay, shape, fuse, lanes, nodes_per_lane);
+    if (!plan.side_by_side && !plan.fused) return false;   // one lane, one launch per solve: the captured chain
+    for (size_t s = 0; s < plan.group.size(); ++s) {
         out.stage.emplace_back();
-        for (int lane = 0; lane < width; ++lane) {   // node k of the stage: chain lay.lane[k] % width, in capture order
+        for (const std::vector<std::vector<int>>& chain : plan.group[s]) {   // one lane of the stage: its groups in capture order, one launch each
+            if (chain.empty()) continue;   // the lanes of a stage fill from 0 up: a stage with fewer busy lanes than its width has them in front
             hipGraph_t graph = nullptr;
+            if (hipGraphCreate(&graph, 0) != hipSuccess) return false;
             hipGraphNode_t prev = nullptr;
             bool ok = true;
-            for (int k = first; ok && k < starts[s + 1]; ++k) {
-                if (lay.lane[k] % width != lane) continue;
-                if (!graph && hipGraphCreate(&graph, 0) != hipSuccess) return false;
+            for (size_t g = 0; ok && g < chain.size(); ++g) {
+                const std::vector<int>& members = chain[g];
+                const int k = members[0];
                 const CapturedLaunch& l = ctx->cap_launch[k];
                 BatchArgs a = l.args;
                 if (status_dead[k]) a.status = nullptr;        // a later solve overwrites every one of them before anything reads one
                 uavqp::TwistedParams tp(a);                    // (every analysable launch is a solve_twisted_kernel: capture_note)
+                uavqp::TwistedGroupArgs sets{};
+                void* group_ptr[1] = {&sets};
                 hipKernelNodeParams p = params[k];             // a barrier: as captured
-                if (l.fn) {
+                if (members.size() > 1) {                      // independent solves of one shape: one launch of the group kernel, grid (n_tiles, members)
+                    for (size_t m = 0; m < members.size(); ++m) {
+                        const int km = members[m];
+                        const BatchArgs& am = ctx->cap_launch[km].args;
+                        sets.set[m] = uavqp::TwistedGroupSet{am.waypoints, am.times, am.bc, am.coeff, status_dead[km] ? nullptr : am.status};
+                    }
+                    p = hipKernelNodeParams{};
+                    p.func = const_cast<void*>(l.group_fn);
+                    p.gridDim = dim3(l.grid.x, (unsigned int)members.size());
+                    p.blockDim = l.block;
+                    p.sharedMemBytes = l.lds_bytes;
+                    p.kernelParams = group_ptr;
+                } else if (l.fn) {
                     p = hipKernelNodeParams{};
                     p.func = const_cast<void*>(l.fn);
                     p.gridDim = l.grid;
@@ -794,16 +832,13 @@ static bool rebuild_captured(uavqp_ctx* ctx, hipGraph_t captured, int lanes, int
                 ok = hipGraphAddKernelNode(&node, graph, prev ? &prev : nullptr, prev ? 1 : 0, &p) == hipSuccess;   // (the arguments are copied into the node)
                 prev = node;
             }
-            if (!graph) continue;   // the lanes of a stage fill from 0 up: a stage with fewer busy lanes than `width` has them in front
             hipGraphExec_t exec = nullptr;
             ok = ok && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
             (void)hipGraphDestroy(graph);
             if (!ok) return false;
             out.stage.back().push_back(exec);
         }
-        side_by_side |= out.stage.back().size() > 1;
     }
-    if (!side_by_side) return false;
     // the streams and events the replay forks to and joins through
     if (!ctx->ev_fork && hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess) return false;
     for (int lane = 1; lane < lanes; ++lane) {
@@ -824,11 +859,12 @@ extern "C" int uavqp_capture_end(uavqp_ctx* ctx, void** out_graph_exec) {
     UAVQP_HIP(hipStreamEndCapture(ctx->stream, &graph));
     // UAVQP_CAPTURE_LANES = 1..8 (A/B runs; 1 = replay the chain as captured; not set: 2, uavqp_capture.h: REPLAY_LANES_DEFAULT).  GPU_MAX_HW_QUEUES is only read: a process given fewer
     // than 4 hardware queues keeps the chain.  UAVQP_CAPTURE_LANE_NODES: the launches a stage must have per lane (default 16).
+    // UAVQP_CAPTURE_FUSE = 1..8: the most independent solves of one shape a launch of the replay carries (1 = one launch per solve; uavqp_capture.h: fuse_groups).
     const uavqp_capture::Knobs knobs = uavqp_capture::knobs_from_environment();
     const int lanes = ctx->capturing ? knobs.lanes : 1;
     CapturedGraph* cg = new (std::nothrow) CapturedGraph();
     if (!cg) { (void)hipGraphDestroy(graph); return UAVQP_ERR_ALLOC; }
-    if (!rebuild_captured(ctx, graph, lanes, knobs.nodes_per_lane, *cg)) {
+    if (!rebuild_captured(ctx, graph, lanes, knobs.nodes_per_lane, ctx->capturing ? knobs.fuse : 1, *cg)) {
         (void)hipGetLastError();
         delete cg;
         cg = new (std::nothrow) CapturedGraph();

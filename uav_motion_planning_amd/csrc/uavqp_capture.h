@@ -4,7 +4,9 @@
 // boundary (docs/measurement_log.md 5.1, 6, 7).  The replay is laid out by lay_out: a solve follows the solve it conflicts with into that
 // solve's lane, so a rotation over any number of buffer sets is ONE stage of chains.  analyse / stage_starts are the layout before it
 // (lane of node k: k % lanes), kept with their results as the reference the conflict rules are pinned against.
-// Host-only: byte ranges and indices, no HIP type -- compiles without the runtime (tests/cpp/test_capture_deps.cpp, test_capture_lanes.cpp).
+// fuse_groups then cuts every lane into groups of independent solves of one shape, each replayed as ONE launch.
+// Host-only: byte ranges and indices, no HIP type -- compiles without the runtime (tests/cpp/test_capture_deps.cpp, test_capture_lanes.cpp,
+// test_capture_fuse.cpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -241,10 +243,90 @@ static inline int replay_lanes_from_env(const char* lanes_env, const char* hw_qu
     return lanes < REPLAY_LANES_DEFAULT ? lanes : REPLAY_LANES_DEFAULT;
 }
 
-// The two knobs as the process environment has them NOW: read when a capture ends (uavqp_capture_end), never on a launch path.
-struct Knobs { int lanes, nodes_per_lane; };
+// ---- Groups: independent solves of one shape that follow each other in a lane are replayed as ONE launch (qp_twisted.h:
+// solve_twisted_group_kernel, grid (n_tiles, members)).  A replayed small-batch solve is bound by its launch -- the kernel boundary and the
+// dispatch ramp of its grid cost more than its waves live (docs/measurement_log.md, 2026-10-20) -- so a lane pays one boundary per group
+// instead of one per solve, and the waves of up to three members share a SIMD.  fuse_groups runs AFTER lay_out and changes nothing of it.
+//
+// What a launch is, as far as grouping goes: two launches with equal keys run the same kernel over grids of the same shape.
+struct Shape {
+    const void* fn = nullptr;                  // the kernel function of the launch
+    unsigned grid = 0, block = 0, lds_bytes = 0;
+    int n_traj = 0;
+    bool one = false;                          // grid == n_tiles and n_traj % TILE == 0: the launch takes the one-tile-per-wave instantiation
+};
+static inline bool same_shape(const Shape& a, const Shape& b) {
+    return a.fn == b.fn && a.grid == b.grid && a.block == b.block && a.lds_bytes == b.lds_bytes && a.n_traj == b.n_traj && a.one == b.one;
+}
+// UAVQP_CAPTURE_FUSE (1..8, anything else: the default): the most solves one launch of a replay carries; 1 = every solve its own launch.
+// The default is 2, chosen by measurement on MI355X among 2 / 4 / 8 (docs/measurement_log.md, 2026-10-20; 4096 x 8-segment min-snap, us per step,
+// medians of six plain runs, one launch per solve first): replayed graph of 200 steps 3.15 -> 2.44 / 2.19 / 2.10, of 20 steps (one lane)
+// 5.95 -> 4.47 / 3.91 / 3.74, of 1500 steps 3.09 -> 2.60 / 2.68 / 2.71.  4 and 8 are faster at 200 and at 20 steps, but with them a
+// two-lane replay depends on which hardware queues the runtime gave the two streams: a process that initialised its communication
+// library first replays 4-5 % (F = 4) and 5-8 % (F = 8) faster than a plain one, at F = 2 0.5 % -- and a default whose speed depends on
+// what else the process did was ruled out when the lane count was chosen (REPLAY_LANES_DEFAULT; tests/test_gpu_bench_two_ranks.py holds
+// the two kinds of process within 6 % of each other).  UAVQP_CAPTURE_FUSE=8 is there for a caller that wants the fewest launches.
+static constexpr int FUSE_MAX = 8;             // == uavqp::GROUP_MAX (qp_twisted.h): the pointer sets one kernarg struct holds
+static constexpr int FUSE_DEFAULT = 2;
+static inline int fuse_from_env(const char* env) {
+    const int v = env && *env ? std::atoi(env) : 0;
+    return v >= 1 && v <= FUSE_MAX ? v : FUSE_DEFAULT;
+}
+// The replay as it is built: stage s runs on width[s] lanes (lanes_that_pay; node k in lane lay.lane[k] % width[s]), and
+// group[s][l] holds the nodes of lane l of stage s, in capture order, cut into groups -- one launch each.  In capture order a node joins the
+// OPEN (the last) group of its lane only if
+//   * it is no barrier and takes the one-tile-per-wave instantiation (Shape::one),
+//   * its shape key equals the group's,
+//   * it conflicts with NO member of the group (conflict(), with the dead-status flags lay_out was given),
+//   * the group has fewer than F members;
+// otherwise it opens a new group.  Hence
+//   * every node is in exactly one group;
+//   * the groups of a lane are in capture order: every node of a group comes before every node of the next one;
+//   * the members of a group are pairwise conflict-free, so their relative order is free -- they may run side by side;
+//   * two conflicting nodes are in different stages, or in one lane in different groups in capture order: ordered as before.
+// F <= 1 gives every node a group of its own: the chains of lay_out.  One comparison per member of the open group: at most F - 1 per node.
+struct Fused {
+    std::vector<int> width;                                            // per stage
+    std::vector<std::vector<std::vector<std::vector<int>>>> group;     // [stage][lane][group][member] -> node
+    bool side_by_side = false;                                         // some stage has two busy lanes
+    bool fused = false;                                                // some group has two members
+};
+static inline Fused fuse_groups(const std::vector<Record>& rec, const std::vector<char>& status_dead, const Layout& lay, const std::vector<Shape>& shape,
+                                int F, int lanes, int nodes_per_lane = NODES_PER_LANE_MIN) {
+    Fused out;
+    const int n = (int)rec.size();
+    if (n == 0 || lay.lane.size() != (size_t)n || lay.starts.empty() || shape.size() != (size_t)n) return out;
+    if (F > FUSE_MAX) F = FUSE_MAX;
+    if (lanes < 1) lanes = 1;
+    const bool have_dead = status_dead.size() == (size_t)n;
+    for (size_t s = 0; s < lay.starts.size(); ++s) {
+        const int first = lay.starts[s], last = s + 1 < lay.starts.size() ? lay.starts[s + 1] : n;
+        const int width = lanes_that_pay(last - first, lanes, nodes_per_lane);
+        out.width.push_back(width);
+        out.group.emplace_back((size_t)width);
+        for (int k = first; k < last; ++k) {
+            std::vector<std::vector<int>>& chain = out.group.back()[(size_t)(lay.lane[k] % width)];
+            const bool k_dead = have_dead && status_dead[k] != 0;
+            bool join = !chain.empty() && !rec[k].barrier && shape[k].one && (int)chain.back().size() < F && same_shape(shape[chain.back()[0]], shape[k]);
+            if (join)    // (the first member of a group that takes a second is no barrier and `one`: same_shape compares the flag)
+                for (int i : chain.back())
+                    if (rec[i].barrier || conflict(rec[i], have_dead && status_dead[i] != 0, rec[k], k_dead)) { join = false; break; }
+            if (!join) chain.emplace_back();
+            chain.back().push_back(k);
+            if (chain.back().size() > 1) out.fused = true;
+        }
+        int busy = 0;
+        for (const auto& chain : out.group.back()) busy += !chain.empty();
+        if (busy > 1) out.side_by_side = true;
+    }
+    return out;
+}
+
+// The knobs as the process environment has them NOW: read when a capture ends (uavqp_capture_end), never on a launch path.
+struct Knobs { int lanes, nodes_per_lane, fuse; };
 static inline Knobs knobs_from_environment() {
-    return Knobs{replay_lanes_from_env(std::getenv("UAVQP_CAPTURE_LANES"), std::getenv("GPU_MAX_HW_QUEUES")), lane_nodes_from_env(std::getenv("UAVQP_CAPTURE_LANE_NODES"))};
+    return Knobs{replay_lanes_from_env(std::getenv("UAVQP_CAPTURE_LANES"), std::getenv("GPU_MAX_HW_QUEUES")), lane_nodes_from_env(std::getenv("UAVQP_CAPTURE_LANE_NODES")),
+                 fuse_from_env(std::getenv("UAVQP_CAPTURE_FUSE"))};
 }
 
 }  // namespace uavqp_capture
