@@ -820,6 +820,97 @@ int uavqp_spacetime_lbfgs_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_se
                                int32_t* status_out, double* objective_out, int32_t* accepted_out, double* peak_out, double* min_dist_out,
                                int32_t* outside_out);
 
+/* Attitude penalty of solved trajectories with its gradients: what a multirotor must do to fly them -- how hard its rotors push, how far
+ * it tilts, how fast its body turns (no reference counterpart as a penalty: the reference's so3_control derives attitude and thrust from
+ * the commanded acceleration in the same way; the term is that of GCOPTER / MINCO, in a division-free form).  The shape of
+ * uavqp_limit_penalty_device.  Per sample at segment-local time t let a, j, s be the acceleration, jerk and snap of the three axes,
+ * z = a + gravity e_z the specific thrust vector (thrust per unit of mass, m/s^2), f2 = |z|^2.  With pos(x) = max(0, x) and
+ * kappa = tan^2(tilt_max):
+ *   u_hi   = f2 / f_max^2 - 1
+ *   u_lo   = 1 - f2 / f_min^2                                                    (absent when f_min = 0)
+ *   u_tilt = (z_x^2 + z_y^2 - kappa z_z |z_z|) / gravity^2
+ *   u_rate = (|z x j|^2 - rate_max^2 f2^2) / (rate_max^2 gravity^4),             |z x j|^2 = f2 |j|^2 - (z.j)^2
+ *   phi    = weight_thrust (pos(u_hi)^3 + pos(u_lo)^3) + weight_tilt pos(u_tilt)^3 + weight_rate pos(u_rate)^3
+ *   Phi    = sum_i (T_i / K) sum_{s=0..K} om_s phi(tau_s T_i)
+ * K = samples_per_seg, tau_s = s / K and the trapezoid weights om_s those of uavqp_limit_penalty_device.  The feasible sets are the
+ * physical ones: u_hi <= 0 and u_lo <= 0 mean f_min <= |z| <= f_max; u_tilt <= 0 means a tilt of at most tilt_max with upward thrust
+ * (thrust pointing below the horizon is penalised whatever tilt_max is); u_rate <= 0 means |b3 x db3/dt| = |z x j| / f2 <= rate_max, b3
+ * the thrust axis.  NO term divides by |z|: every output is finite for every finite input, free fall (z = 0) costs exactly weight_thrust
+ * per unit of weight (when f_min > 0) and has zero gradient.  Every u is dimensionless, so Phi has the unit of time_weight * T like the
+ * other penalties, and the cube makes it twice continuously differentiable.  The yaw rate is NOT part of the body rate: these
+ * trajectories carry no heading, the rate bounded is that of the thrust axis alone.
+ * Gradients, G_a and G_j the derivatives of phi in a and j:
+ *   G_a = 3 weight_thrust (pos(u_hi)^2 2 z / f_max^2 - pos(u_lo)^2 2 z / f_min^2)
+ *       + 3 weight_tilt pos(u_tilt)^2 (2 z_x, 2 z_y, -2 kappa |z_z|) / gravity^2
+ *       + 3 weight_rate pos(u_rate)^2 (2 |j|^2 z - 2 (z.j) j - 4 rate_max^2 f2 z) / (rate_max^2 gravity^4)
+ *   G_j = 3 weight_rate pos(u_rate)^2 (2 f2 j - 2 (z.j) z) / (rate_max^2 gravity^4)
+ *   d_penalty     [n_traj] Phi
+ *   d_grad_coeff  layout of coeff: dPhi/dc_{axis,k} = (T_i / K) sum_s om_s [G_a[axis] k(k-1) t^(k-2) + G_j[axis] k(k-1)(k-2) t^(k-3)], at FIXED
+ *                 durations
+ *   d_grad_times  [sum_b M_b]: the EXPLICIT dPhi/dT_i = Phi_i / T_i + (T_i / K) sum_s om_s tau_s [G_a . j + G_j . s], at FIXED coefficients
+ *   d_peak        [n_traj][4], in physical units, over the samples: the largest |z|, the smallest |z| (m/s^2), the largest tilt angle
+ *                 atan2(sqrt(z_x^2 + z_y^2), z_z) (rad), the largest body rate |z x j| / f2 (rad/s; a sample with f2 = 0 is left out).  A
+ *                 trajectory without a sample (not UAVQP_SOLVED, or M < 1) reports {0, +inf, 0, 0}.
+ * Each output may be NULL (all NULL: UAVQP_OK, nothing done).  The TOTAL gradients in durations, waypoints and boundary derivatives of
+ * coefficients that come from uavqp_solve_batch_device are d_grad_times + uavqp_solve_backward_device(g = d_grad_coeff), as for the other
+ * penalties.  d_status as for uavqp_limit_penalty_device: a trajectory that is not UAVQP_SOLVED, or with M < 1, gets zeros in the penalty
+ * and both gradients.  Every output element is written exactly once, zeros included; the additions are in a fixed order: the same bytes
+ * run to run and for any grid.  One launch, asynchronous on the ctx stream, no allocation, no read-back.
+ * WHAT THE RESULT IS: a SOFT penalty.  At finite weights a trajectory optimised against it may still exceed a limit that binds; d_peak is
+ * the check afterwards, in the units of the limits themselves.
+ * UAVQP_ERR_INVALID_ARG: r not 3 / 4, a negative count, a wrong struct_size, samples_per_seg < 1, gravity not positive and finite, not
+ * 0 <= f_min < f_max < inf, tilt_max outside (0, pi/2), rate_max not positive and finite, a weight that is negative or not finite, NULL
+ * times / coeff, ragged without offsets. */
+typedef struct uavqp_attitude_params {
+    int32_t struct_size;
+    int32_t samples_per_seg;   /* K: K + 1 sample points per segment (default 8) */
+    double gravity;            /* m/s^2, > 0 (default 9.81, the constant the collision check's body frame uses) */
+    double f_min;              /* smallest specific thrust, m/s^2, >= 0; 0: no lower limit (default 3) */
+    double f_max;              /* largest specific thrust, m/s^2, > f_min (default 20: about twice the weight) */
+    double tilt_max;           /* largest tilt of the thrust axis from vertical, rad, in (0, pi/2) (default 1.05) */
+    double rate_max;           /* largest rate of the thrust axis, rad/s, > 0 (default 2.1) */
+    double weight_thrust;      /* >= 0 (default 1e3) */
+    double weight_tilt;        /* >= 0 (default 1e3) */
+    double weight_rate;        /* >= 0 (default 1e3) */
+} uavqp_attitude_params;
+void uavqp_default_attitude_params(uavqp_attitude_params* out);   /* callable without a device */
+int uavqp_attitude_penalty_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
+                                  const double* d_times, const double* d_coeff, const int32_t* d_status,
+                                  const uavqp_attitude_params* params, double* d_penalty, double* d_grad_coeff, double* d_grad_times,
+                                  double* d_peak);
+/* The same from HOST pointers (H2D copy, run, D2H copy, synchronous). */
+int uavqp_attitude_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
+                                const double* coeff, const int32_t* status, const uavqp_attitude_params* params, double* penalty,
+                                double* grad_coeff, double* grad_times, double* peak);
+
+/* uavqp_spacetime_lbfgs_device with the attitude penalty inside the objective: per trajectory
+ *       minimise  f(p, T) = [the objective of uavqp_spacetime_lbfgs_device] + Phi_att(c*(p, T), T)
+ * Phi_att exactly the formula of uavqp_attitude_penalty_device with `attitude`.  Variables, bounds, directions, the ONE accept / reject per
+ * trajectory and trial, every argument, every output and the parameters are those of uavqp_spacetime_lbfgs_device; only f and its
+ * gradient differ.  Sequencing: that of uavqp_spacetime_lbfgs_device with one more launch after every flight penalty that feeds a step
+ * (the attitude penalty ADDS its value and both partial gradients to the flight penalty's before the one backward pass): five launches per
+ * trial, still none that depends on the data, nothing read back.  d_objective_out holds f INCLUDING Phi_att; d_coeff_out is bit for bit
+ * uavqp_solve_batch_device at what is handed back.  With all three attitude weights 0 that launch is skipped and every output equals that
+ * of uavqp_spacetime_lbfgs_device byte for byte.
+ *   attitude             validated as for uavqp_attitude_penalty_device
+ *   d_attitude_peak_out  [n_traj][4] (may be NULL): d_peak of uavqp_attitude_penalty_device at what is handed back
+ * WHAT THE RESULT IS: as for uavqp_spacetime_lbfgs_device, a local minimum of a piecewise smooth f with soft penalties: a limit that binds
+ * may still be exceeded, d_attitude_peak_out says by how much.
+ * Out of scope: as uavqp_spacetime_lbfgs_device. */
+int uavqp_attitude_optimize_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                                   const int32_t* d_seg_offsets, double* d_waypoints, double* d_times, const double* d_bc,
+                                   const uavqp_esdf* esdf, const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
+                                   const uavqp_attitude_params* attitude, const uavqp_spacetime_lbfgs_params* params, double* d_coeff_out,
+                                   int32_t* d_status_out, double* d_objective_out, int32_t* d_accepted_out, double* d_peak_out,
+                                   double* d_min_dist_out, int32_t* d_outside_out, double* d_attitude_peak_out);
+/* The same from HOST pointers, as uavqp_spacetime_lbfgs_host. */
+int uavqp_attitude_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                                 double* waypoints, double* times, const double* bc, const uavqp_esdf* esdf, const uavqp_limit_params* limits,
+                                 const uavqp_clearance_params* clearance, const uavqp_attitude_params* attitude,
+                                 const uavqp_spacetime_lbfgs_params* params, double* coeff_out, int32_t* status_out, double* objective_out,
+                                 int32_t* accepted_out, double* peak_out, double* min_dist_out, int32_t* outside_out,
+                                 double* attitude_peak_out);
+
 /* Swarm separation penalty: reciprocal avoidance between the vehicles of one swarm, compared at the same instant on a clock the swarm
  * shares, with its gradients in the coefficients, the durations and the departure times (no reference counterpart: its multi_agents.launch
  * is namespacing only; the term is that of EGO-Swarm / MINCO-swarm).  It is the one penalty here that couples trajectories.

@@ -81,6 +81,11 @@ SYMBOLS = (
     "uavqp_default_spacetime_lbfgs_params",
     "uavqp_spacetime_lbfgs_device",
     "uavqp_spacetime_lbfgs_host",
+    "uavqp_default_attitude_params",
+    "uavqp_attitude_penalty_device",
+    "uavqp_attitude_penalty_host",
+    "uavqp_attitude_optimize_device",
+    "uavqp_attitude_optimize_host",
     "uavqp_default_swarm_params",
     "uavqp_swarm_penalty_device",
     "uavqp_swarm_penalty_host",
@@ -183,6 +188,13 @@ class SpacetimeLbfgsParams(ctypes.Structure):
                 ("smooth_weight", ctypes.c_double), ("time_weight", ctypes.c_double), ("t_min", ctypes.c_double), ("t_max", ctypes.c_double),
                 ("max_move", ctypes.c_double), ("initial_step_move", ctypes.c_double), ("initial_step_log", ctypes.c_double),
                 ("armijo_c", ctypes.c_double), ("shrink", ctypes.c_double), ("grow", ctypes.c_double), ("curvature_eps", ctypes.c_double)]
+
+
+class AttitudeParams(ctypes.Structure):
+    """uavqp_attitude_params of include/uavqp.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("samples_per_seg", ctypes.c_int32), ("gravity", ctypes.c_double), ("f_min", ctypes.c_double),
+                ("f_max", ctypes.c_double), ("tilt_max", ctypes.c_double), ("rate_max", ctypes.c_double), ("weight_thrust", ctypes.c_double),
+                ("weight_tilt", ctypes.c_double), ("weight_rate", ctypes.c_double)]
 
 
 class SwarmParams(ctypes.Structure):
@@ -307,6 +319,16 @@ def lib():
                                                ctypes.POINTER(ClearanceParams), ctypes.POINTER(SpacetimeLbfgsParams), dp, ip, dp, ip, dp, dp, ip]
     L.uavqp_spacetime_lbfgs_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(LimitParams),
                                              ctypes.POINTER(ClearanceParams), ctypes.POINTER(SpacetimeLbfgsParams), dp, ip, dp, ip, dp, dp, ip]
+    L.uavqp_default_attitude_params.argtypes = [ctypes.POINTER(AttitudeParams)]
+    L.uavqp_default_attitude_params.restype = None
+    L.uavqp_attitude_penalty_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, ctypes.POINTER(AttitudeParams), dp, dp, dp, dp]
+    L.uavqp_attitude_penalty_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, ctypes.POINTER(AttitudeParams), dp, dp, dp, dp]
+    L.uavqp_attitude_optimize_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(LimitParams),
+                                                 ctypes.POINTER(ClearanceParams), ctypes.POINTER(AttitudeParams),
+                                                 ctypes.POINTER(SpacetimeLbfgsParams), dp, ip, dp, ip, dp, dp, ip, dp]
+    L.uavqp_attitude_optimize_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(LimitParams),
+                                               ctypes.POINTER(ClearanceParams), ctypes.POINTER(AttitudeParams),
+                                               ctypes.POINTER(SpacetimeLbfgsParams), dp, ip, dp, ip, dp, dp, ip, dp]
     L.uavqp_default_swarm_params.argtypes = [ctypes.POINTER(SwarmParams)]
     L.uavqp_default_swarm_params.restype = None
     L.uavqp_swarm_penalty_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, i32, ip, dp, ctypes.POINTER(SwarmParams), dp, dp, dp, dp, dp]

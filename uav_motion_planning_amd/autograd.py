@@ -16,6 +16,10 @@ forward = uavqp_limit_penalty_device, which also writes both gradients; backward
     phi = clearance_penalty(ctx, r, coeff, times, esdf, uniform_segments=8, d_safe=0.6)   # [n_traj], esdf: an updated esdf.EsdfMap
 
 the same for uavqp_clearance_penalty_device; behind solve_batch the gradients reach waypoints, times and bc through its backward pass.
+
+    phi = attitude_penalty(ctx, r, coeff, times, uniform_segments=8, tilt_max=0.5)        # [n_traj]
+
+the same for uavqp_attitude_penalty_device (specific thrust, tilt and body rate of the vehicle that flies the trajectory).
 """
 from . import _lib
 
@@ -115,6 +119,52 @@ def _penalty_function():
 
     _Penalty = LimitPenalty
     return _Penalty
+
+
+_Attitude = None
+
+
+def _attitude_function():
+    global _Attitude
+    if _Attitude is not None:
+        return _Attitude
+    import torch
+
+    class AttitudePenalty(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, coeff, times, ctx, r, seg_offsets, uniform_segments, status, params):
+            for name, t in (("coeff", coeff), ("times", times)):
+                if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+                    raise ValueError(f"attitude_penalty: {name} must be a contiguous float64 tensor on the GPU")
+            total = times.numel()
+            n_traj = total // uniform_segments if uniform_segments > 0 else seg_offsets.numel() - 1
+            if coeff.numel() != 3 * 2 * r * total:
+                raise ValueError("attitude_penalty: coeff must hold 3 * 2r doubles per segment")
+            phi = torch.empty(n_traj, dtype=torch.float64, device=times.device)
+            g_c = torch.empty_like(coeff)
+            g_t = torch.empty_like(times)
+            ctx.set_stream(torch.cuda.current_stream(times.device).cuda_stream)
+            ctx.attitude_penalty_device(r, n_traj, uniform_segments, seg_offsets, times.detach(), coeff.detach(), status=status, penalty=phi,
+                                        grad_coeff=g_c, grad_times=g_t, **params)
+            if uniform_segments > 0:
+                counts = torch.full((n_traj,), uniform_segments, dtype=torch.int64, device=times.device)
+            else:
+                counts = (seg_offsets[1:] - seg_offsets[:-1]).to(torch.int64)
+            fctx.save_for_backward(g_c, g_t, counts)
+            fctx.nc = 3 * 2 * r
+            return phi
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable   # the gradients come from a raw kernel: no second derivative through them
+        def backward(fctx, grad_phi):
+            g_c, g_t, counts = fctx.saved_tensors
+            need_c, need_t = fctx.needs_input_grad[:2]
+            out_c = g_c * torch.repeat_interleave(grad_phi, counts * fctx.nc) if need_c else None
+            out_t = g_t * torch.repeat_interleave(grad_phi, counts) if need_t else None
+            return out_c, out_t, None, None, None, None, None, None
+
+    _Attitude = AttitudePenalty
+    return _Attitude
 
 
 _Clearance = None
@@ -292,6 +342,19 @@ def limit_penalty(ctx, r, coeff, times, seg_offsets=None, uniform_segments=0, st
     if uniform_segments <= 0 and seg_offsets is None:
         raise ValueError("limit_penalty: ragged batches need seg_offsets")
     return _penalty_function().apply(coeff, times, ctx, int(r), seg_offsets, int(uniform_segments), status, dict(limits))
+
+
+def attitude_penalty(ctx, r, coeff, times, seg_offsets=None, uniform_segments=0, status=None, **params):
+    """Differentiable uavqp_attitude_penalty_device: the thrust / tilt / body-rate penalty [n_traj] of coeff (layout of solve_batch's
+    result) at the durations `times` [sum M_b].  params: fields of uavqp_attitude_params that differ from the defaults (gravity, f_min,
+    f_max, tilt_max, rate_max, weight_thrust, weight_tilt, weight_rate, samples_per_seg).  status: optional int32 status tensor of the
+    solve.  The gradient in `times` is the explicit part; with coeff = solve_batch(..., times, ...) torch adds the part through the solve,
+    and waypoints.grad / bc.grad come from the same backward pass."""
+    if uniform_segments <= 0 and seg_offsets is None:
+        raise ValueError("attitude_penalty: ragged batches need seg_offsets")
+    from .traj_optimizer import Context
+    Context._attitude_params(params)   # (an unknown field is refused before anything runs)
+    return _attitude_function().apply(coeff, times, ctx, int(r), seg_offsets, int(uniform_segments), status, dict(params))
 
 
 def clearance_penalty(ctx, r, coeff, times, esdf, seg_offsets=None, uniform_segments=0, status=None, **params):

@@ -346,6 +346,57 @@ class TrajOptimizer {
         for (int32_t s : status_) if (s != UAVQP_SOLVED) return false;
         return true;
     }
+    // optimizeTrajectoryLbfgs with the attitude penalty -- specific thrust, tilt and body rate of the vehicle -- inside the objective
+    // (include/uavqp.h uavqp_attitude_optimize_host): the same bounds, the same members filled, and attitudePeak() [n_traj][4] = largest and
+    // smallest specific thrust (m/s^2), largest tilt (rad), largest body rate (rad/s) sampled at the result.  The penalty is soft:
+    // attitudePeak() is the check afterwards.  params: null = uavqp_default_spacetime_lbfgs_params.
+    template <class Map>
+    bool optimizeTrajectoryAttitude(const Map& map, const uavqp_limit_params& limits, const uavqp_clearance_params& clearance,
+                                    const uavqp_attitude_params& attitude, const uavqp_spacetime_lbfgs_params* params = nullptr) {
+        if (n_traj_ <= 0 || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_])) return false;
+        if (!lo_.empty() || rows_k_ > 0) {
+            std::cout << "solver solve failed! (optimizeTrajectoryAttitude: corridor and general-rows problems are out of scope)" << std::endl;
+            return false;
+        }
+        if (!ensureContext()) return false;
+        if (bc_.empty()) bc_.assign(static_cast<size_t>(n_traj_) * 2 * (order_ - 1) * 3, 0.0);
+        uavqp_spacetime_lbfgs_params pp;
+        if (params) pp = *params; else uavqp_default_spacetime_lbfgs_params(&pp);
+        coef_.assign(static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_], 0.0);
+        status_.assign(n_traj_, 0);
+        objective_.assign(static_cast<size_t>(2) * n_traj_, 0.0);
+        accepted_.assign(n_traj_, 0);
+        peak_.assign(static_cast<size_t>(2) * n_traj_, 0.0);
+        min_dist_.assign(n_traj_, 0.0);
+        outside_.assign(n_traj_, 0);
+        attitude_peak_.assign(static_cast<size_t>(4) * n_traj_, 0.0);
+        const int rc = uavqp_attitude_optimize_host(ctx_, order_, n_traj_, 0, 0, seg_offsets_.data(), wp_.data(), T_.data(), bc_.data(), map.handle(),
+                                                    &limits, &clearance, &attitude, &pp, coef_.data(), status_.data(), objective_.data(),
+                                                    accepted_.data(), peak_.data(), min_dist_.data(), outside_.data(), attitude_peak_.data());
+        if (rc != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            return false;
+        }
+        for (int32_t s : status_) if (s != UAVQP_SOLVED) return false;
+        return true;
+    }
+    // Attitude penalty per trajectory of the stored coefficients at the stored durations (after solve() or an optimiser;
+    // uavqp_attitude_penalty_host); fills attitudePeak().  A trajectory that did not solve carries zero.  Empty on failure.
+    std::vector<double> getAttitudePenalty(const uavqp_attitude_params& attitude) {
+        std::vector<double> phi;
+        if (n_traj_ <= 0 || !ctx_ || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_]) ||
+            coef_.size() != static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_] || status_.size() != static_cast<size_t>(n_traj_))
+            return phi;
+        phi.assign(n_traj_, 0.0);
+        attitude_peak_.assign(static_cast<size_t>(4) * n_traj_, 0.0);
+        if (uavqp_attitude_penalty_host(ctx_, order_, n_traj_, 0, seg_offsets_.data(), T_.data(), coef_.data(), status_.data(), &attitude,
+                                        phi.data(), nullptr, nullptr, attitude_peak_.data()) != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            phi.clear();
+        }
+        return phi;
+    }
+    const std::vector<double>& attitudePeak() const { return attitude_peak_; }
     // optimizeTrajectory for the swarms set with setSwarm (include/uavqp.h uavqp_swarm_optimize_host; the reference's equality rows only:
     // false when a corridor or rows are set): the separation penalty `swarm` between the vehicles of each swarm joins the objective and
     // every trial is accepted or rejected per SWARM.  With params->start_window > 0 the departures of setSwarm are optimised too and the
@@ -648,7 +699,7 @@ class TrajOptimizer {
     std::vector<double> wp_, T_, bc_, coef_, lo_, hi_, pipe_lo_, pipe_hi_, row_tau_, row_lo_, row_hi_;
     std::vector<int32_t> row_deriv_, first_hit_, repair_deriv_;
     std::vector<double> repair_tau_, repair_lo_, repair_hi_;
-    std::vector<double> objective_, peak_, min_dist_, min_sep_;
+    std::vector<double> objective_, peak_, min_dist_, min_sep_, attitude_peak_;
     std::vector<int32_t> outside_;
     std::vector<int32_t> accepted_;
     std::vector<int32_t> groups_;   // setSwarm: empty = the whole batch is one swarm

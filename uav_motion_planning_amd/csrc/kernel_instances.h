@@ -166,3 +166,9 @@ static inline bool uavqp_twisted_group_exists(int r, int M, int tile) {
     UAVQP_INST __global__ void uavqp::swarm_step_kernel<R_, true>(uavqp::SwarmOptArgs);           \
     UAVQP_INST __global__ void uavqp::swarm_step_kernel<R_, false>(uavqp::SwarmOptArgs);
 #define UAVQP_INSTANCES_SWARM_OPT UAVQP_SWARM_OPT_R(3) UAVQP_SWARM_OPT_R(4)
+
+// ---- qp_attitude.h: thrust / tilt / body-rate penalty with its gradients, and the variant that ADDS them to the flight penalty's
+#define UAVQP_ATTITUDE_R(R_)                                                                     \
+    UAVQP_INST __global__ void uavqp::attitude_penalty_kernel<R_, false>(uavqp::AttitudeArgs);      \
+    UAVQP_INST __global__ void uavqp::attitude_penalty_kernel<R_, true>(uavqp::AttitudeArgs);
+#define UAVQP_INSTANCES_ATTITUDE UAVQP_ATTITUDE_R(3) UAVQP_ATTITUDE_R(4)

@@ -40,6 +40,7 @@
 #include "qp_spacetime_lbfgs.h"
 #include "qp_swarm.h"
 #include "qp_swarm_opt.h"
+#include "qp_attitude.h"
 // Measured-slower alternatives kept as bit-identical cross-checks: `make experiments` (-DUAVQP_EXPERIMENTS) only
 #ifdef UAVQP_EXPERIMENTS
 #include "cloud_grid2d.h"
@@ -75,6 +76,7 @@ UAVQP_INSTANCES_SPACETIME
 UAVQP_INSTANCES_SPACETIME_LBFGS
 UAVQP_INSTANCES_SWARM
 UAVQP_INSTANCES_SWARM_OPT
+UAVQP_INSTANCES_ATTITUDE
 #endif
 
 namespace uavqp {
@@ -1973,6 +1975,11 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
 // Velocity / acceleration limit penalty and the limit-aware duration optimiser
 // ===================================================================================================
 #include "uavqp_limits.h"
+
+// ===================================================================================================
+// Attitude penalty: specific thrust, tilt and body rate of the vehicle that flies the trajectory
+// ===================================================================================================
+#include "uavqp_attitude.h"
 
 // ===================================================================================================
 // Signed distance field of an occupancy grid and the clearance penalty

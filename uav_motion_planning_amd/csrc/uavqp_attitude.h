@@ -1,0 +1,108 @@
+// uavqp_attitude.h -- host side of uavqp_attitude_penalty_device / _host (include/uavqp.h): included by uavqp.hip behind uavqp_limits.h.
+// Kernel: qp_attitude.h (translation unit k_attitude.hip).  The penalty is one launch, nothing allocated, nothing read back.
+// uavqp_attitude_optimize_device (uavqp_spacetime_lbfgs.h) enqueues the accumulating variant through attitude_penalty_enqueue.
+#pragma once
+
+extern "C" void uavqp_default_attitude_params(uavqp_attitude_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(uavqp_attitude_params);
+    p->samples_per_seg = 8;     // as uavqp_default_limit_params
+    p->gravity = 9.81;          // the constant of poly_body_frame (qp_poly.h)
+    p->f_min = 3.0;             // a small racing-class multirotor: thrust between 0.3 and 2 times its weight,
+    p->f_max = 20.0;
+    p->tilt_max = 1.05;         // 60 degrees of tilt,
+    p->rate_max = 2.1;          // 120 degrees per second of body rate
+    p->weight_thrust = 1e3;     // comparable with the other penalties: the u inside the penalty are dimensionless
+    p->weight_tilt = 1e3;
+    p->weight_rate = 1e3;
+}
+
+static bool attitude_params_valid(const uavqp_attitude_params* p) {
+    if (!p || p->struct_size != (int32_t)sizeof(uavqp_attitude_params)) return false;
+    if (p->samples_per_seg < 1) return false;
+    if (!(p->gravity > 0.0 && p->gravity < INFINITY)) return false;
+    if (!(p->f_min >= 0.0 && p->f_min < p->f_max && p->f_max < INFINITY)) return false;
+    if (!(p->tilt_max > 0.0 && p->tilt_max < 1.5707963267948966)) return false;
+    if (!(p->rate_max > 0.0 && p->rate_max < INFINITY)) return false;
+    for (double w : {p->weight_thrust, p->weight_tilt, p->weight_rate})
+        if (!(w >= 0.0 && w < INFINITY)) return false;
+    return true;
+}
+
+static bool attitude_any_weight(const uavqp_attitude_params& A) { return A.weight_thrust > 0.0 || A.weight_tilt > 0.0 || A.weight_rate > 0.0; }
+
+// (arguments checked by the callers)  accumulate (uavqp_attitude_optimize_device only, not in the C ABI): penalty, grad_coeff and grad_times
+// are ADDED to what the arrays hold
+static int attitude_penalty_enqueue(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
+                                    const double* d_coeff, const int32_t* d_status, const uavqp_attitude_params& A, double* d_penalty,
+                                    double* d_grad_coeff, double* d_grad_times, double* d_peak, bool accumulate = false) {
+    uavqp::AttitudeArgs a;
+    a.n_traj = n_traj; a.uniform = uniform_segments; a.seg_offsets = d_seg_offsets; a.times = d_times; a.coeff = d_coeff; a.status = d_status;
+    a.penalty = d_penalty; a.grad_coeff = d_grad_coeff; a.grad_times = d_grad_times; a.peak = d_peak;
+    a.K = A.samples_per_seg;
+    a.al16 = ((((uintptr_t)d_coeff) | ((uintptr_t)d_grad_coeff)) & 15u) == 0 ? 1 : 0;
+    const double g2 = A.gravity * A.gravity, tn = std::tan(A.tilt_max);
+    a.gravity = A.gravity; a.inv_g2 = 1.0 / g2;
+    a.inv_fmax2 = 1.0 / (A.f_max * A.f_max);
+    a.lo_one = A.f_min > 0.0 ? 1.0 : 0.0;
+    a.inv_fmin2 = A.f_min > 0.0 ? 1.0 / (A.f_min * A.f_min) : 0.0;
+    a.kappa = tn * tn;
+    a.rate2 = A.rate_max * A.rate_max; a.inv_rg4 = 1.0 / (a.rate2 * g2 * g2);
+    a.w_thrust = A.weight_thrust; a.w_tilt = A.weight_tilt; a.w_rate = A.weight_rate;
+    const int grid = topt_grid(ctx, n_traj);
+    if (accumulate && r == 3)
+        hipLaunchKernelGGL((uavqp::attitude_penalty_kernel<3, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+    else if (accumulate)
+        hipLaunchKernelGGL((uavqp::attitude_penalty_kernel<4, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+    else if (r == 3)
+        hipLaunchKernelGGL((uavqp::attitude_penalty_kernel<3, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
+    else
+        hipLaunchKernelGGL((uavqp::attitude_penalty_kernel<4, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
+    UAVQP_HIP(hipGetLastError());
+    return UAVQP_OK;
+}
+
+extern "C" int uavqp_attitude_penalty_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
+                                             const double* d_times, const double* d_coeff, const int32_t* d_status,
+                                             const uavqp_attitude_params* params, double* d_penalty, double* d_grad_coeff,
+                                             double* d_grad_times, double* d_peak) {
+    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0) return UAVQP_ERR_INVALID_ARG;
+    if (!attitude_params_valid(params)) return UAVQP_ERR_INVALID_ARG;
+    if (n_traj == 0 || (!d_penalty && !d_grad_coeff && !d_grad_times && !d_peak)) return UAVQP_OK;
+    if (!d_times || !d_coeff || (uniform_segments == 0 && !d_seg_offsets)) return UAVQP_ERR_INVALID_ARG;
+    UAVQP_HIP(hipSetDevice(ctx->device));
+    return attitude_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff, d_status, *params, d_penalty,
+                                    d_grad_coeff, d_grad_times, d_peak);
+}
+
+extern "C" int uavqp_attitude_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets,
+                                           const double* times, const double* coeff, const int32_t* status,
+                                           const uavqp_attitude_params* params, double* penalty, double* grad_coeff, double* grad_times,
+                                           double* peak) {
+    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0) return UAVQP_ERR_INVALID_ARG;
+    if (!attitude_params_valid(params)) return UAVQP_ERR_INVALID_ARG;
+    if (n_traj == 0 || (!penalty && !grad_coeff && !grad_times && !peak)) return UAVQP_OK;
+    if (!times || !coeff || (uniform_segments == 0 && !seg_offsets)) return UAVQP_ERR_INVALID_ARG;
+    BatchShape sh;
+    int rc = batch_shape(n_traj, uniform_segments, 0, seg_offsets, &sh);
+    if (rc != UAVQP_OK) return rc;
+    UAVQP_HIP(hipSetDevice(ctx->device));
+    const size_t n = (size_t)n_traj, tot = (size_t)sh.total_seg;
+    Stage st;
+    const int i_off = uniform_segments > 0 ? -1 : st.in(seg_offsets, sizeof(int32_t) * (n + 1));
+    const int i_t = st.in(times, sizeof(double) * tot);
+    const int i_c = st.in(coeff, sizeof(double) * 3 * 2 * r * tot);
+    const int i_st = status ? st.in(status, sizeof(int32_t) * n) : -1;
+    const int i_p = penalty ? st.out(penalty, sizeof(double) * n) : -1;
+    const int i_g = grad_coeff ? st.out(grad_coeff, sizeof(double) * 3 * 2 * r * tot) : -1;
+    const int i_gt = grad_times ? st.out(grad_times, sizeof(double) * tot) : -1;
+    const int i_pk = peak ? st.out(peak, sizeof(double) * 4 * n) : -1;
+    rc = stage_begin(ctx, st);
+    if (rc != UAVQP_OK) return rc;
+    rc = attitude_penalty_enqueue(ctx, r, n_traj, uniform_segments, st.at<int32_t>(i_off), st.at<double>(i_t), st.at<double>(i_c),
+                                  st.at<int32_t>(i_st), *params, st.at<double>(i_p), st.at<double>(i_g), st.at<double>(i_gt),
+                                  st.at<double>(i_pk));
+    if (rc != UAVQP_OK) return rc;
+    return stage_end(ctx, st, "uavqp_attitude_penalty_host");
+}

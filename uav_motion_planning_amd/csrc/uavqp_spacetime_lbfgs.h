@@ -1,5 +1,5 @@
-// uavqp_spacetime_lbfgs.h -- host side of uavqp_spacetime_lbfgs_device / _host (include/uavqp.h): included by uavqp.hip behind
-// uavqp_spacetime.h, whose parameter checks, penalty launch and sequencing it shares.  Kernel: qp_spacetime_lbfgs.h (translation unit
+// uavqp_spacetime_lbfgs.h -- host side of uavqp_spacetime_lbfgs_device / _host and uavqp_attitude_optimize_device / _host (include/uavqp.h):
+// included by uavqp.hip behind uavqp_spacetime.h, whose parameter checks, penalty launch and sequencing it shares, and uavqp_attitude.h.  Kernel: qp_spacetime_lbfgs.h (translation unit
 // k_spacetime_lbfgs.hip).
 //
 // The launch sequence is that of uavqp_spacetime_optimize_device with the other step kernel: NO data-dependent control flow on the host, the
@@ -8,7 +8,7 @@
 //     anchor copy -> clamp -> solve(waypoints, times) -> flight penalty -> backward -> step<INIT>
 //       -> max_iters x { solve(trial waypoints, trial durations) -> flight penalty -> backward -> step<ITER> }
 //       -> solve(waypoints, times) -> flight penalty (peak / min_dist / outside only)
-// Four launches per iteration.
+// Four launches per iteration; with the attitude penalty (uavqp_attitude_optimize_device) one more after every flight penalty of the loop.
 #pragma once
 
 extern "C" void uavqp_default_spacetime_lbfgs_params(uavqp_spacetime_lbfgs_params* p) {
@@ -55,15 +55,20 @@ static bool spacetime_lbfgs_params_valid(const uavqp_spacetime_lbfgs_params* p) 
     return true;
 }
 
-extern "C" int uavqp_spacetime_lbfgs_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
-                                            const int32_t* d_seg_offsets, double* d_waypoints, double* d_times, const double* d_bc,
-                                            const uavqp_esdf* esdf, const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
-                                            const uavqp_spacetime_lbfgs_params* params, double* d_coeff_out, int32_t* d_status_out,
-                                            double* d_objective_out, int32_t* d_accepted_out, double* d_peak_out, double* d_min_dist_out,
-                                            int32_t* d_outside_out) {
+// The sequence above for both entries.  attitude null (uavqp_spacetime_lbfgs_device): exactly those launches.  attitude with a positive
+// weight (uavqp_attitude_optimize_device): the accumulating attitude penalty (qp_attitude.h) is enqueued between the flight penalty and the
+// backward pass, so the step kernel reads the summed phi and the summed partial gradients -- five launches per iteration.
+static int spacetime_lbfgs_run(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                               const int32_t* d_seg_offsets, double* d_waypoints, double* d_times, const double* d_bc, const uavqp_esdf* esdf,
+                               const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
+                               const uavqp_spacetime_lbfgs_params* params, double* d_coeff_out, int32_t* d_status_out, double* d_objective_out,
+                               int32_t* d_accepted_out, double* d_peak_out, double* d_min_dist_out, int32_t* d_outside_out,
+                               const uavqp_attitude_params* attitude, double* d_attitude_peak_out) {
     if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0 || total_segments < 0) return UAVQP_ERR_INVALID_ARG;
     if (!spacetime_lbfgs_params_valid(params) || !limit_params_valid(limits)) return UAVQP_ERR_INVALID_ARG;
     if (!esdf_usable(ctx, esdf) || !esdf->updated || !clearance_params_valid(clearance)) return UAVQP_ERR_INVALID_ARG;
+    if (attitude && !attitude_params_valid(attitude)) return UAVQP_ERR_INVALID_ARG;
+    const bool with_attitude = attitude && attitude_any_weight(*attitude);
     if (n_traj == 0) return UAVQP_OK;
     if (!d_waypoints || !d_times || !d_bc || !d_coeff_out || !d_objective_out) return UAVQP_ERR_INVALID_ARG;
     if (uniform_segments == 0 && (!d_seg_offsets || max_segments < 1)) return UAVQP_ERR_INVALID_ARG;
@@ -114,6 +119,11 @@ extern "C" int uavqp_spacetime_lbfgs_device(uavqp_ctx* ctx, int r, int n_traj, i
         int e = flight_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_T, d_coeff_out, d_st, esdf, *limits, *clearance,
                                        c.at<double>(i_ph), c.at<double>(i_g), c.at<double>(i_ex), nullptr, nullptr, nullptr);
         if (e != UAVQP_OK) return e;
+        if (with_attitude) {
+            e = attitude_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_T, d_coeff_out, d_st, *attitude, c.at<double>(i_ph),
+                                         c.at<double>(i_g), c.at<double>(i_ex), nullptr, true);
+            if (e != UAVQP_OK) return e;
+        }
         return uavqp_solve_backward_device(ctx, r, n_traj, uniform_segments, max_segments, total_segments, d_seg_offsets, d_wp, d_T, d_bc,
                                            d_coeff_out, d_st, c.at<double>(i_g), c.at<double>(i_tht), c.at<double>(i_thp), nullptr);
     };
@@ -167,17 +177,44 @@ extern "C" int uavqp_spacetime_lbfgs_device(uavqp_ctx* ctx, int r, int n_traj, i
     if (d_peak_out || d_min_dist_out || d_outside_out)   // the penalty's diagnostics of what is handed back
         rc = flight_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, d_st_final, esdf, *limits, *clearance,
                                     nullptr, nullptr, nullptr, d_peak_out, d_min_dist_out, d_outside_out);
+    if (rc == UAVQP_OK && attitude && d_attitude_peak_out)
+        rc = attitude_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, d_st_final, *attitude, nullptr,
+                                      nullptr, nullptr, d_attitude_peak_out);
     return rc;
 }
 
-extern "C" int uavqp_spacetime_lbfgs_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
-                                          double* waypoints, double* times, const double* bc, const uavqp_esdf* esdf,
-                                          const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
-                                          const uavqp_spacetime_lbfgs_params* params, double* coeff_out, int32_t* status_out, double* objective_out,
-                                          int32_t* accepted_out, double* peak_out, double* min_dist_out, int32_t* outside_out) {
+extern "C" int uavqp_spacetime_lbfgs_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                                            const int32_t* d_seg_offsets, double* d_waypoints, double* d_times, const double* d_bc,
+                                            const uavqp_esdf* esdf, const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
+                                            const uavqp_spacetime_lbfgs_params* params, double* d_coeff_out, int32_t* d_status_out,
+                                            double* d_objective_out, int32_t* d_accepted_out, double* d_peak_out, double* d_min_dist_out,
+                                            int32_t* d_outside_out) {
+    return spacetime_lbfgs_run(ctx, r, n_traj, uniform_segments, max_segments, total_segments, d_seg_offsets, d_waypoints, d_times, d_bc, esdf,
+                               limits, clearance, params, d_coeff_out, d_status_out, d_objective_out, d_accepted_out, d_peak_out, d_min_dist_out,
+                               d_outside_out, nullptr, nullptr);
+}
+
+extern "C" int uavqp_attitude_optimize_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                                              const int32_t* d_seg_offsets, double* d_waypoints, double* d_times, const double* d_bc,
+                                              const uavqp_esdf* esdf, const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
+                                              const uavqp_attitude_params* attitude, const uavqp_spacetime_lbfgs_params* params,
+                                              double* d_coeff_out, int32_t* d_status_out, double* d_objective_out, int32_t* d_accepted_out,
+                                              double* d_peak_out, double* d_min_dist_out, int32_t* d_outside_out, double* d_attitude_peak_out) {
+    if (!attitude_params_valid(attitude)) return UAVQP_ERR_INVALID_ARG;
+    return spacetime_lbfgs_run(ctx, r, n_traj, uniform_segments, max_segments, total_segments, d_seg_offsets, d_waypoints, d_times, d_bc, esdf,
+                               limits, clearance, params, d_coeff_out, d_status_out, d_objective_out, d_accepted_out, d_peak_out, d_min_dist_out,
+                               d_outside_out, attitude, d_attitude_peak_out);
+}
+
+static int spacetime_lbfgs_run_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                                    double* waypoints, double* times, const double* bc, const uavqp_esdf* esdf, const uavqp_limit_params* limits,
+                                    const uavqp_clearance_params* clearance, const uavqp_spacetime_lbfgs_params* params, double* coeff_out,
+                                    int32_t* status_out, double* objective_out, int32_t* accepted_out, double* peak_out, double* min_dist_out,
+                                    int32_t* outside_out, const uavqp_attitude_params* attitude, double* attitude_peak_out, const char* what) {
     if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0) return UAVQP_ERR_INVALID_ARG;
     if (!spacetime_lbfgs_params_valid(params) || !limit_params_valid(limits)) return UAVQP_ERR_INVALID_ARG;
     if (!esdf_usable(ctx, esdf) || !esdf->updated || !clearance_params_valid(clearance)) return UAVQP_ERR_INVALID_ARG;
+    if (attitude && !attitude_params_valid(attitude)) return UAVQP_ERR_INVALID_ARG;
     if (n_traj == 0) return UAVQP_OK;
     if (!waypoints || !times || !bc || !coeff_out || !objective_out) return UAVQP_ERR_INVALID_ARG;
     if (uniform_segments == 0 && !seg_offsets) return UAVQP_ERR_INVALID_ARG;
@@ -197,12 +234,35 @@ extern "C" int uavqp_spacetime_lbfgs_host(uavqp_ctx* ctx, int r, int n_traj, int
     const int i_pk = peak_out ? st.out(peak_out, sizeof(double) * 2 * n) : -1;
     const int i_md = min_dist_out ? st.out(min_dist_out, sizeof(double) * n) : -1;
     const int i_o = outside_out ? st.out(outside_out, sizeof(int32_t) * n) : -1;
+    const int i_apk = (attitude && attitude_peak_out) ? st.out(attitude_peak_out, sizeof(double) * 4 * n) : -1;
     rc = stage_begin(ctx, st);
     if (rc != UAVQP_OK) return rc;
-    rc = uavqp_spacetime_lbfgs_device(ctx, r, n_traj, uniform_segments, sh.Mmax, (int)sh.total_seg, st.at<int32_t>(i_off), st.at<double>(i_wp),
-                                      st.at<double>(i_t), st.at<double>(i_bc), esdf, limits, clearance, params, st.at<double>(i_out),
-                                      st.at<int32_t>(i_st), st.at<double>(i_obj), st.at<int32_t>(i_acc), st.at<double>(i_pk),
-                                      st.at<double>(i_md), st.at<int32_t>(i_o));
+    rc = spacetime_lbfgs_run(ctx, r, n_traj, uniform_segments, sh.Mmax, (int)sh.total_seg, st.at<int32_t>(i_off), st.at<double>(i_wp),
+                             st.at<double>(i_t), st.at<double>(i_bc), esdf, limits, clearance, params, st.at<double>(i_out),
+                             st.at<int32_t>(i_st), st.at<double>(i_obj), st.at<int32_t>(i_acc), st.at<double>(i_pk), st.at<double>(i_md),
+                             st.at<int32_t>(i_o), attitude, st.at<double>(i_apk));
     if (rc != UAVQP_OK) return rc;
-    return stage_end(ctx, st, "uavqp_spacetime_lbfgs_host");
+    return stage_end(ctx, st, what);
+}
+
+extern "C" int uavqp_spacetime_lbfgs_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                                          double* waypoints, double* times, const double* bc, const uavqp_esdf* esdf,
+                                          const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
+                                          const uavqp_spacetime_lbfgs_params* params, double* coeff_out, int32_t* status_out, double* objective_out,
+                                          int32_t* accepted_out, double* peak_out, double* min_dist_out, int32_t* outside_out) {
+    return spacetime_lbfgs_run_host(ctx, r, n_traj, uniform_segments, max_segments, seg_offsets, waypoints, times, bc, esdf, limits, clearance,
+                                    params, coeff_out, status_out, objective_out, accepted_out, peak_out, min_dist_out, outside_out, nullptr,
+                                    nullptr, "uavqp_spacetime_lbfgs_host");
+}
+
+extern "C" int uavqp_attitude_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                                            double* waypoints, double* times, const double* bc, const uavqp_esdf* esdf,
+                                            const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
+                                            const uavqp_attitude_params* attitude, const uavqp_spacetime_lbfgs_params* params, double* coeff_out,
+                                            int32_t* status_out, double* objective_out, int32_t* accepted_out, double* peak_out,
+                                            double* min_dist_out, int32_t* outside_out, double* attitude_peak_out) {
+    if (!attitude_params_valid(attitude)) return UAVQP_ERR_INVALID_ARG;
+    return spacetime_lbfgs_run_host(ctx, r, n_traj, uniform_segments, max_segments, seg_offsets, waypoints, times, bc, esdf, limits, clearance,
+                                    params, coeff_out, status_out, objective_out, accepted_out, peak_out, min_dist_out, outside_out, attitude,
+                                    attitude_peak_out, "uavqp_attitude_optimize_host");
 }

@@ -558,6 +558,89 @@ class Context:
         _lib.check(rc, "uavqp_spacetime_lbfgs_host")
         return waypoints, times, coeff, status, objective, accepted, peak, min_dist, outside
 
+    @staticmethod
+    def _attitude_params(params):
+        ap = _lib.AttitudeParams()
+        _lib.lib().uavqp_default_attitude_params(ctypes.byref(ap))
+        for k, v in params.items():
+            if not hasattr(ap, k) or k == "struct_size":
+                raise ValueError(f"unknown uavqp_attitude_params field {k!r}")
+            setattr(ap, k, v)
+        return ap
+
+    def attitude_penalty_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, status=None, penalty=None, grad_coeff=None,
+                                grad_times=None, peak=None, **params):
+        """uavqp_attitude_penalty_device on device buffers: the thrust / tilt / body-rate penalty [n_traj] of solved trajectories, its
+        gradient in the coefficients at fixed durations (layout of coeff), its EXPLICIT gradient in the durations at fixed coefficients
+        [sum M], and the sampled peaks [n_traj][4] (largest and smallest specific thrust in m/s^2, largest tilt in rad, largest body rate
+        in rad/s); each output may be None.  status (the solve's, optional): trajectories that are not SOLVED get zeros.  params: fields
+        of uavqp_attitude_params that differ from uavqp_default_attitude_params.  Asynchronous."""
+        ap = self._attitude_params(params)
+        rc = _lib.lib().uavqp_attitude_penalty_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff),
+                                                      _ptr(status), ctypes.byref(ap), _ptr(penalty), _ptr(grad_coeff), _ptr(grad_times),
+                                                      _ptr(peak))
+        _lib.check(rc, "uavqp_attitude_penalty_device")
+
+    def attitude_penalty_host(self, r, seg_offsets, times, coeff, uniform_segments=0, status=None, **params):
+        """numpy in / numpy out (synchronous).  Returns (penalty [n_traj], grad_coeff, grad_times [sum M], peak [n_traj][4])."""
+        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
+        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total and coeff.size == 3 * 2 * r * total
+        ap = self._attitude_params(params)
+        penalty = np.zeros(n_traj, dtype=np.float64)
+        g_c = np.zeros_like(coeff)
+        g_t = np.zeros(total, dtype=np.float64)
+        peak = np.zeros((n_traj, 4), dtype=np.float64)
+        rc = _lib.lib().uavqp_attitude_penalty_host(self._h, r, n_traj, uniform_segments, _ptr(so), _ptr(times), _ptr(coeff), _ptr(status),
+                                                    ctypes.byref(ap), _ptr(penalty), _ptr(g_c), _ptr(g_t), _ptr(peak))
+        _lib.check(rc, "uavqp_attitude_penalty_host")
+        return penalty, g_c, g_t, peak
+
+    def attitude_optimize_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc, esdf,
+                                 coeff_out, status_out, objective_out, accepted_out=None, peak_out=None, min_dist_out=None, outside_out=None,
+                                 attitude_peak_out=None, limits=None, clearance=None, attitude=None, **params):
+        """uavqp_attitude_optimize_device on device buffers: spacetime_lbfgs_device with the attitude penalty inside the objective
+        (objective_out includes it); attitude_peak_out [n_traj][4] receives attitude_penalty_device's peaks at the result.  attitude: dict
+        of uavqp_attitude_params fields; everything else as spacetime_lbfgs_device.  Asynchronous."""
+        pp = self._spacetime_lbfgs_params(params)
+        lp, cp, ap = self._limit_params(limits or {}), self._clearance_params(clearance or {}), self._attitude_params(attitude or {})
+        rc = _lib.lib().uavqp_attitude_optimize_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), _ptr(seg_offsets),
+                                                       _ptr(waypoints), _ptr(times), _ptr(bc), getattr(esdf, "handle", esdf), ctypes.byref(lp),
+                                                       ctypes.byref(cp), ctypes.byref(ap), ctypes.byref(pp), _ptr(coeff_out), _ptr(status_out),
+                                                       _ptr(objective_out), _ptr(accepted_out), _ptr(peak_out), _ptr(min_dist_out),
+                                                       _ptr(outside_out), _ptr(attitude_peak_out))
+        _lib.check(rc, "uavqp_attitude_optimize_device")
+
+    def attitude_optimize_host(self, r, seg_offsets, waypoints, times, bc, esdf, uniform_segments=0, limits=None, clearance=None, attitude=None,
+                               **params):
+        """numpy in / numpy out (synchronous; the map stays on the device).  Returns what spacetime_lbfgs_host returns, and the attitude
+        peaks [n_traj][4] after it."""
+        waypoints = np.array(waypoints, dtype=np.float64).reshape(-1, 3)   # copies: the call updates both in place
+        times = np.array(times, dtype=np.float64).ravel()
+        bc = np.ascontiguousarray(bc, dtype=np.float64)
+        so, n_traj, total, mmax = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total
+        assert waypoints.size == 3 * (total + n_traj), "waypoints must hold sum(M_b + 1) xyz rows"
+        assert bc.size == n_traj * 2 * (r - 1) * 3
+        pp = self._spacetime_lbfgs_params(params)
+        lp, cp, ap = self._limit_params(limits or {}), self._clearance_params(clearance or {}), self._attitude_params(attitude or {})
+        coeff = np.zeros(3 * 2 * r * total, dtype=np.float64)
+        status = np.zeros(n_traj, dtype=np.int32)
+        objective = np.zeros((n_traj, 2), dtype=np.float64)
+        accepted = np.zeros(n_traj, dtype=np.int32)
+        peak = np.zeros((n_traj, 2), dtype=np.float64)
+        min_dist = np.zeros(n_traj, dtype=np.float64)
+        outside = np.zeros(n_traj, dtype=np.int32)
+        attitude_peak = np.zeros((n_traj, 4), dtype=np.float64)
+        rc = _lib.lib().uavqp_attitude_optimize_host(self._h, r, n_traj, uniform_segments, max(mmax, 1), _ptr(so), _ptr(waypoints), _ptr(times),
+                                                     _ptr(bc), getattr(esdf, "handle", esdf), ctypes.byref(lp), ctypes.byref(cp), ctypes.byref(ap),
+                                                     ctypes.byref(pp), _ptr(coeff), _ptr(status), _ptr(objective), _ptr(accepted), _ptr(peak),
+                                                     _ptr(min_dist), _ptr(outside), _ptr(attitude_peak))
+        _lib.check(rc, "uavqp_attitude_optimize_host")
+        return waypoints, times, coeff, status, objective, accepted, peak, min_dist, outside, attitude_peak
+
     def time_optimize_limits_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc,
                                     coeff_out, status_out, objective_out, accepted_out=None, peak_out=None, limits=None, **params):
         """uavqp_time_optimize_limits_device on device buffers: time_optimize_device with the limit penalty inside the objective
@@ -934,6 +1017,9 @@ class TrajOptimizer:
                                      (uavqp_spacetime_optimize_host); stores waypoints, durations and coefficients; .objective,
                                      .iterations, .peak, .min_dist, .outside as above
     optimizeTrajectoryLbfgs(esdf, ...)   the same with limited-memory BFGS directions kept on the device (uavqp_spacetime_lbfgs_host)
+    optimizeTrajectoryAttitude(esdf, ...)   optimizeTrajectoryLbfgs with the attitude penalty (thrust, tilt, body rate) in the objective
+                                     (uavqp_attitude_optimize_host); .attitude_peak [n_traj][4] the sampled peaks at the result
+    getAttitudePenalty(...)          [n_traj] attitude penalty of the stored coefficients at the stored durations; fills .attitude_peak
     getFlightPenalty(esdf, ...)      [n_traj] limit + clearance penalty of the stored coefficients in one launch
     setSwarm(group_offsets, start_times)   which trajectories fly together (swarm g = trajectories group_offsets[g] .. group_offsets[g + 1];
                                      None: the whole batch is one swarm) and when each departs on its swarm's clock (None: all at 0)
@@ -961,6 +1047,7 @@ class TrajOptimizer:
         self.iterations = np.zeros(0, dtype=np.int32)
         self.objective = np.zeros((0, 2))
         self.peak = np.zeros((0, 2))
+        self.attitude_peak = np.zeros((0, 4))
         self.min_dist = np.zeros(0)
         self.outside = np.zeros(0, dtype=np.int32)
 
@@ -1109,6 +1196,37 @@ class TrajOptimizer:
         (self._wp, self._T, self._coef, self.status, self.objective, self.iterations, self.peak, self.min_dist,
          self.outside) = ctx.spacetime_lbfgs_host(self._r, self._so, self._wp, self._T, bc, esdf, limits=limits, clearance=clearance, **params)
         return bool(np.all(self.status == _lib.UAVQP_SOLVED))
+
+    def optimizeTrajectoryAttitude(self, esdf, limits=None, clearance=None, attitude=None, **params):
+        """optimizeTrajectoryLbfgs with the attitude penalty (thrust, tilt, body rate) inside the objective
+        (uavqp_attitude_optimize_host): the same bounds and members filled, and .attitude_peak [n_traj][4] = largest and smallest specific
+        thrust (m/s^2), largest tilt (rad), largest body rate (rad/s) sampled at the result.  attitude: dict of uavqp_attitude_params
+        fields ({} or None: the defaults); params: fields of uavqp_spacetime_lbfgs_params (an unknown field of either raises ValueError).
+        The penalty is soft: check .attitude_peak against the limits (include/uavqp.h)."""
+        if self._lo is not None or self._rows is not None:
+            raise ValueError("optimizeTrajectoryAttitude: corridor and general-rows problems are out of scope (include/uavqp.h)")
+        Context._spacetime_lbfgs_params(params)   # (an unknown field is refused before anything runs)
+        Context._attitude_params(attitude or {})
+        if self._wp is None or self._T is None:
+            return False
+        n_traj = self._so.size - 1
+        if self._T.size != int(self._so[-1]):
+            return False
+        bc = self._bc if self._bc is not None else np.zeros((n_traj, 2, self._r - 1, 3))
+        ctx = self.context()
+        (self._wp, self._T, self._coef, self.status, self.objective, self.iterations, self.peak, self.min_dist, self.outside,
+         self.attitude_peak) = ctx.attitude_optimize_host(self._r, self._so, self._wp, self._T, bc, esdf, limits=limits, clearance=clearance,
+                                                          attitude=attitude, **params)
+        return bool(np.all(self.status == _lib.UAVQP_SOLVED))
+
+    def getAttitudePenalty(self, **params):
+        """[n_traj] attitude penalty (thrust, tilt, body rate) of the stored coefficients at the stored durations (after solve() or an
+        optimiser); params: fields of uavqp_attitude_params that differ from the defaults.  Trajectories that did not solve carry zero.
+        .attitude_peak [n_traj][4] is filled with the sampled peaks."""
+        if self._ctx is None or self._coef.size != 3 * 2 * self._r * int(self._so[-1]) or self.status.size != self._so.size - 1:
+            raise _lib.UavqpError("getAttitudePenalty: no solved coefficients (call solve() or an optimiser first)")
+        phi, _, _, self.attitude_peak = self._ctx.attitude_penalty_host(self._r, self._so, self._T, self._coef, status=self.status, **params)
+        return phi
 
     def getFlightPenalty(self, esdf, limits=None, clearance=None):
         """[n_traj] limit penalty + clearance penalty of the stored coefficients at the stored durations against `esdf`, in one launch
