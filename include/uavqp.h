@@ -218,7 +218,8 @@ int uavqp_solve_axis_host(uavqp_ctx* ctx, int r, int n_seg, const double* pos_1d
  * stream synchronisation: workspaces are sized by the batch's total segment count) -- the host entries and the pipeline, which know
  * the total, do not.
  * Exact primal active-set solve in the Hermite variables; status UAVQP_MAX_ITER_REACHED
- * (uavqp_settings.max_iter, default 8 M + 20 iterations) leaves a feasible, smooth, possibly sub-optimal trajectory. */
+ * (uavqp_settings.max_iter, default 8 M + 20 iterations) leaves a feasible, smooth, possibly sub-optimal trajectory.
+ * M <= 63; a longer trajectory is flagged UAVQP_INVALID_INPUT (the working set is one 64-bit word per axis). */
 int uavqp_solve_corridor_batch_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments,
                                       const int32_t* d_seg_offsets, const double* d_waypoints, const double* d_times,
                                       const double* d_bc, const double* d_corr_lo, const double* d_corr_hi,
@@ -231,7 +232,8 @@ int uavqp_solve_corridor_batch_host(uavqp_ctx* ctx, int r, int n_traj, int unifo
 /* Warm-started corridor solve for outer loops (BASELINE config 5: the corridor QP is re-solved after every time
  * re-allocation, and its working set barely moves).  Same problem, same result as uavqp_solve_corridor_batch_device;
  * d_active_set [n_traj][3][2] uint64 holds per (trajectory, axis) the working set of the active-set method: word 0
- * bit k = the box of interior waypoint k (1 <= k <= M-1 <= 63) is active, word 1 bit k = at its upper bound.
+ * bit k = the box of interior waypoint k (1 <= k <= M-1 <= 62) is active, word 1 bit k = at its upper bound.
+ * M <= 63; a longer trajectory is flagged UAVQP_INVALID_INPUT.
  *   warm_start == 0: the buffer is only written (working set at the solution);
  *   warm_start != 0: it is read as the initial working set (any bit pattern is a valid guess: wrong guesses cost
  *                    iterations, never correctness) and overwritten with the final one.
