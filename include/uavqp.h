@@ -913,6 +913,67 @@ int uavqp_attitude_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_
                                  int32_t* accepted_out, double* peak_out, double* min_dist_out, int32_t* outside_out,
                                  double* attitude_peak_out);
 
+/* Certified continuous-time bounds of solved trajectories (no reference counterpart).  Everything above that tests a limit SAMPLES the
+ * trajectory; this BOUNDS it: between the knots a segment is a polynomial of degree n = 2r - 1, and the range of a polynomial over an
+ * interval can be enclosed.  Per segment and quantity four numbers (outer_lo, inner_lo, inner_hi, outer_hi): the quantity stays inside
+ * [outer_lo, outer_hi] for EVERY t in [0, T_i], and it takes the values inner_lo and inner_hi (up to the guard below) at some
+ * t = l T_i / 2^depth.  Quantities: each axis of position, velocity, acceleration and jerk; the norms |v|, |a|, |j|; the specific thrust
+ * |a + g e_z|, g = 9.81; the tilt polynomial w = z_z^2 - cos^2(tilt_max) |z|^2, z = a + g e_z (tilt <= tilt_max for all t iff w >= 0 and
+ * z_z > 0 throughout).
+ * Method, D = 0..3 the derivative order, m = n - D, u = t / T_i:
+ *   a_k = falling(k + D, D) c[k + D] T_i^k, k = 0..m;  S = sum_k |a_k|;  Bernstein coefficients b_i = sum_{k<=i} C(i,k) / C(m,k) a_k;
+ *   depth levels of midpoint de Casteljau (w_j + w_{j+1}) / 2 give 2^depth leaves (no pruning);
+ *   outer = [min over all leaf coefficients - G, max + G], G = 16 (m + 1) 2^-53 S;  inner = [min, max] over the leaf END coefficients.
+ *   Squared norms (degree 2m) from the undivided b: q_k = 1 / C(2m,k) sum_{i+j=k} C(m,i) C(m,j) sum_x b_{x,i} b_{x,j}, subdivided the same
+ *   way, guard Gq = 32 (2m + 1) 2^-53 sum_x S_x^2; reported norms are sqrt(max(0, .)) of the guarded squares.  Thrust: q of D = 2 with g
+ *   added to every z coefficient, S_z = S_z - |a_0| + |a_0 + g|.  w = [z products] - cos^2(tilt_max) q_thrust, guard Gq of the thrust,
+ *   reported unrooted.  A non-finite S (Gq) makes the four numbers of the quantity NaN.
+ * Outputs (each may be NULL; all NULL: UAVQP_OK, nothing done):
+ *   d_range        [sum_b M_b][4][3][4]: D, axis, (outer_lo, inner_lo, inner_hi, outer_hi)
+ *   d_norm         [sum_b M_b][5][4]: |v|, |a|, |j|, thrust, w, the same four numbers
+ *   d_peak         [n_traj][5][4]: min (the two lower numbers) / max (the two upper) of d_norm over the segments of the trajectory
+ *   d_seg_verdict  [sum_b M_b] and d_verdict [n_traj]: tests k = 0..6 = v_max, a_max, j_max, f_min, f_max, tilt_max, box.
+ *                  Bit 2k (UAVQP_ENVELOPE_CERTIFIED(k)): holds for ALL t -- the outer bound, guard included, satisfies the limit.
+ *                  Bit 2k + 1 (UAVQP_ENVELOPE_VIOLATED(k)): broken at a known t -- the inner bound moved TOWARDS the limit by the guard
+ *                  still breaks it.  Neither: undecided at this depth.  Norms are tested on their squares against limit * limit.  A limit
+ *                  of 0 switches its test off (both bits 0).  The trajectory's word is the AND of the certified bits and the OR of the
+ *                  violated bits of its segments.
+ *   d_box_lo / hi  [sum_b M_b][3], optional input, both or neither: one box per SEGMENT, tested on the D = 0 ranges.
+ * d_status as for uavqp_limit_penalty_device: a trajectory that is not UAVQP_SOLVED, or with M < 1, gets zeros everywhere.  Non-finite
+ * coefficients give non-finite bounds and no verdict bit.  Every output element is written exactly once, zeros included; min and max are
+ * exact, so the bytes are the same for any grid.  One launch, asynchronous on the ctx stream, no allocation, no workspace, no read-back.
+ * WHAT THE RESULT IS: a certificate, not an estimate.  After an optimiser with soft penalties this is the acceptance test: a certified
+ * bit needs no sampling density to be trusted.  An undecided test is decided by a larger depth (the outer gap falls about four-fold per
+ * level) or is genuinely on the limit.
+ * Out of scope: body-rate and clearance certificates (rational / not polynomial in t); pruned or adaptive subdivision; wiring the verdict
+ * into uavqp_corridor_pipeline_*.
+ * UAVQP_ERR_INVALID_ARG: r not 3 / 4, a negative count, a wrong struct_size, depth outside 0..8, a limit that is negative or not finite,
+ * f_max < f_min when both are set, tilt_max not 0 and outside (0, pi/2), NULL times / coeff, ragged without offsets, one box pointer
+ * without the other. */
+#define UAVQP_ENVELOPE_CERTIFIED(k) (1 << (2 * (k)))
+#define UAVQP_ENVELOPE_VIOLATED(k) (2 << (2 * (k)))
+enum { UAVQP_ENVELOPE_V_MAX = 0, UAVQP_ENVELOPE_A_MAX, UAVQP_ENVELOPE_J_MAX, UAVQP_ENVELOPE_F_MIN, UAVQP_ENVELOPE_F_MAX,
+       UAVQP_ENVELOPE_TILT_MAX, UAVQP_ENVELOPE_BOX, UAVQP_ENVELOPE_TESTS };
+typedef struct uavqp_envelope_params {
+    int32_t struct_size;
+    int32_t depth;       /* subdivision levels, 0..8 (default 4): 2^depth leaves per polynomial */
+    double v_max;        /* m/s, 0: off (every limit defaults to 0) */
+    double a_max;        /* m/s^2 */
+    double j_max;        /* m/s^3 */
+    double f_min;        /* smallest specific thrust, m/s^2 */
+    double f_max;        /* largest specific thrust, m/s^2, >= f_min when both are set */
+    double tilt_max;     /* rad, 0 or in (0, pi/2) */
+} uavqp_envelope_params;
+void uavqp_default_envelope_params(uavqp_envelope_params* out);   /* callable without a device */
+int uavqp_envelope_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
+                          const double* d_coeff, const int32_t* d_status, const uavqp_envelope_params* params, const double* d_box_lo,
+                          const double* d_box_hi, double* d_range, double* d_norm, double* d_peak, int32_t* d_seg_verdict,
+                          int32_t* d_verdict);
+/* The same from HOST pointers (H2D copy, run, D2H copy, synchronous). */
+int uavqp_envelope_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
+                        const double* coeff, const int32_t* status, const uavqp_envelope_params* params, const double* box_lo,
+                        const double* box_hi, double* range, double* norm, double* peak, int32_t* seg_verdict, int32_t* verdict);
+
 /* Swarm separation penalty: reciprocal avoidance between the vehicles of one swarm, compared at the same instant on a clock the swarm
  * shares, with its gradients in the coefficients, the durations and the departure times (no reference counterpart: its multi_agents.launch
  * is namespacing only; the term is that of EGO-Swarm / MINCO-swarm).  It is the one penalty here that couples trajectories.

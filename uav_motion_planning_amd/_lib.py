@@ -86,6 +86,9 @@ SYMBOLS = (
     "uavqp_attitude_penalty_host",
     "uavqp_attitude_optimize_device",
     "uavqp_attitude_optimize_host",
+    "uavqp_default_envelope_params",
+    "uavqp_envelope_device",
+    "uavqp_envelope_host",
     "uavqp_default_swarm_params",
     "uavqp_swarm_penalty_device",
     "uavqp_swarm_penalty_host",
@@ -195,6 +198,16 @@ class AttitudeParams(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_int32), ("samples_per_seg", ctypes.c_int32), ("gravity", ctypes.c_double), ("f_min", ctypes.c_double),
                 ("f_max", ctypes.c_double), ("tilt_max", ctypes.c_double), ("rate_max", ctypes.c_double), ("weight_thrust", ctypes.c_double),
                 ("weight_tilt", ctypes.c_double), ("weight_rate", ctypes.c_double)]
+
+
+class EnvelopeParams(ctypes.Structure):
+    """uavqp_envelope_params of include/uavqp.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("depth", ctypes.c_int32), ("v_max", ctypes.c_double), ("a_max", ctypes.c_double),
+                ("j_max", ctypes.c_double), ("f_min", ctypes.c_double), ("f_max", ctypes.c_double), ("tilt_max", ctypes.c_double)]
+
+
+# the tests of uavqp_envelope_*: bit 2k of a verdict word = certified, bit 2k + 1 = violated (UAVQP_ENVELOPE_* of include/uavqp.h)
+ENVELOPE_TESTS = ("v_max", "a_max", "j_max", "f_min", "f_max", "tilt_max", "box")
 
 
 class SwarmParams(ctypes.Structure):
@@ -323,6 +336,10 @@ def lib():
     L.uavqp_default_attitude_params.restype = None
     L.uavqp_attitude_penalty_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, ctypes.POINTER(AttitudeParams), dp, dp, dp, dp]
     L.uavqp_attitude_penalty_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, ctypes.POINTER(AttitudeParams), dp, dp, dp, dp]
+    L.uavqp_default_envelope_params.argtypes = [ctypes.POINTER(EnvelopeParams)]
+    L.uavqp_default_envelope_params.restype = None
+    L.uavqp_envelope_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, ctypes.POINTER(EnvelopeParams), dp, dp, dp, dp, dp, ip, ip]
+    L.uavqp_envelope_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, ctypes.POINTER(EnvelopeParams), dp, dp, dp, dp, dp, ip, ip]
     L.uavqp_attitude_optimize_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(LimitParams),
                                                  ctypes.POINTER(ClearanceParams), ctypes.POINTER(AttitudeParams),
                                                  ctypes.POINTER(SpacetimeLbfgsParams), dp, ip, dp, ip, dp, dp, ip, dp]

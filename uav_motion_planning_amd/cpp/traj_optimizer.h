@@ -397,6 +397,34 @@ class TrajOptimizer {
         return phi;
     }
     const std::vector<double>& attitudePeak() const { return attitude_peak_; }
+    // Certified bounds of the stored coefficients at the stored durations over WHOLE segments (after solve() or an optimiser;
+    // uavqp_envelope_host): the verdict word per trajectory (bit 2k certified for all t, bit 2k + 1 violated, UAVQP_ENVELOPE_* of
+    // include/uavqp.h), and envelopeRange() [sum M][4][3][4], envelopeNorm() [sum M][5][4], envelopePeak() [n_traj][5][4],
+    // envelopeSegVerdict() [sum M] filled.  box_lo / box_hi: [sum M][3], one box per segment, both or neither (nullptr: off).  A trajectory
+    // that did not solve carries zeros.  Empty on failure.
+    std::vector<int32_t> getEnvelope(const uavqp_envelope_params& envelope, const double* box_lo = nullptr, const double* box_hi = nullptr) {
+        std::vector<int32_t> verdict;
+        if (n_traj_ <= 0 || !ctx_ || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_]) ||
+            coef_.size() != static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_] || status_.size() != static_cast<size_t>(n_traj_))
+            return verdict;
+        const size_t tot = static_cast<size_t>(seg_offsets_[n_traj_]);
+        verdict.assign(n_traj_, 0);
+        envelope_range_.assign(48 * tot, 0.0);
+        envelope_norm_.assign(20 * tot, 0.0);
+        envelope_peak_.assign(static_cast<size_t>(20) * n_traj_, 0.0);
+        envelope_seg_verdict_.assign(tot, 0);
+        if (uavqp_envelope_host(ctx_, order_, n_traj_, 0, seg_offsets_.data(), T_.data(), coef_.data(), status_.data(), &envelope, box_lo, box_hi,
+                                envelope_range_.data(), envelope_norm_.data(), envelope_peak_.data(), envelope_seg_verdict_.data(),
+                                verdict.data()) != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            verdict.clear();
+        }
+        return verdict;
+    }
+    const std::vector<double>& envelopeRange() const { return envelope_range_; }
+    const std::vector<double>& envelopeNorm() const { return envelope_norm_; }
+    const std::vector<double>& envelopePeak() const { return envelope_peak_; }
+    const std::vector<int32_t>& envelopeSegVerdict() const { return envelope_seg_verdict_; }
     // optimizeTrajectory for the swarms set with setSwarm (include/uavqp.h uavqp_swarm_optimize_host; the reference's equality rows only:
     // false when a corridor or rows are set): the separation penalty `swarm` between the vehicles of each swarm joins the objective and
     // every trial is accepted or rejected per SWARM.  With params->start_window > 0 the departures of setSwarm are optimised too and the
@@ -699,7 +727,8 @@ class TrajOptimizer {
     std::vector<double> wp_, T_, bc_, coef_, lo_, hi_, pipe_lo_, pipe_hi_, row_tau_, row_lo_, row_hi_;
     std::vector<int32_t> row_deriv_, first_hit_, repair_deriv_;
     std::vector<double> repair_tau_, repair_lo_, repair_hi_;
-    std::vector<double> objective_, peak_, min_dist_, min_sep_, attitude_peak_;
+    std::vector<double> objective_, peak_, min_dist_, min_sep_, attitude_peak_, envelope_range_, envelope_norm_, envelope_peak_;
+    std::vector<int32_t> envelope_seg_verdict_;
     std::vector<int32_t> outside_;
     std::vector<int32_t> accepted_;
     std::vector<int32_t> groups_;   // setSwarm: empty = the whole batch is one swarm

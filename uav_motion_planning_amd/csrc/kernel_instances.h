@@ -172,3 +172,7 @@ static inline bool uavqp_twisted_group_exists(int r, int M, int tile) {
     UAVQP_INST __global__ void uavqp::attitude_penalty_kernel<R_, false>(uavqp::AttitudeArgs);      \
     UAVQP_INST __global__ void uavqp::attitude_penalty_kernel<R_, true>(uavqp::AttitudeArgs);
 #define UAVQP_INSTANCES_ATTITUDE UAVQP_ATTITUDE_R(3) UAVQP_ATTITUDE_R(4)
+
+// ---- qp_envelope.h: certified bounds of position, velocity, acceleration, jerk, thrust and tilt over whole segments
+#define UAVQP_ENVELOPE_R(R_) UAVQP_INST __global__ void uavqp::envelope_kernel<R_>(uavqp::EnvelopeArgs);
+#define UAVQP_INSTANCES_ENVELOPE UAVQP_ENVELOPE_R(3) UAVQP_ENVELOPE_R(4)

@@ -41,6 +41,7 @@
 #include "qp_swarm.h"
 #include "qp_swarm_opt.h"
 #include "qp_attitude.h"
+#include "qp_envelope.h"
 // Measured-slower alternatives kept as bit-identical cross-checks: `make experiments` (-DUAVQP_EXPERIMENTS) only
 #ifdef UAVQP_EXPERIMENTS
 #include "cloud_grid2d.h"
@@ -77,6 +78,7 @@ UAVQP_INSTANCES_SPACETIME_LBFGS
 UAVQP_INSTANCES_SWARM
 UAVQP_INSTANCES_SWARM_OPT
 UAVQP_INSTANCES_ATTITUDE
+UAVQP_INSTANCES_ENVELOPE
 #endif
 
 namespace uavqp {
@@ -1980,6 +1982,11 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
 // Attitude penalty: specific thrust, tilt and body rate of the vehicle that flies the trajectory
 // ===================================================================================================
 #include "uavqp_attitude.h"
+
+// ===================================================================================================
+// Certified continuous-time bounds (Bernstein enclosure) of solved trajectories and the verdict against limits
+// ===================================================================================================
+#include "uavqp_envelope.h"
 
 // ===================================================================================================
 // Signed distance field of an occupancy grid and the clearance penalty

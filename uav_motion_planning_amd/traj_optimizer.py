@@ -598,6 +598,54 @@ class Context:
         _lib.check(rc, "uavqp_attitude_penalty_host")
         return penalty, g_c, g_t, peak
 
+    @staticmethod
+    def _envelope_params(params):
+        ep = _lib.EnvelopeParams()
+        _lib.lib().uavqp_default_envelope_params(ctypes.byref(ep))
+        for k, v in params.items():
+            if not hasattr(ep, k) or k == "struct_size":
+                raise ValueError(f"unknown uavqp_envelope_params field {k!r}")
+            setattr(ep, k, v)
+        return ep
+
+    def envelope_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, status=None, box_lo=None, box_hi=None, range_out=None,
+                        norm_out=None, peak_out=None, seg_verdict_out=None, verdict_out=None, **params):
+        """uavqp_envelope_device on device buffers: certified bounds of solved trajectories over whole segments.  range_out
+        [sum M][4][3][4] (derivative order, axis, (outer_lo, inner_lo, inner_hi, outer_hi)), norm_out [sum M][5][4] (|v|, |a|, |j|, specific
+        thrust, tilt polynomial w), peak_out [n_traj][5][4], seg_verdict_out [sum M] and verdict_out [n_traj] (int32: bit 2k certified,
+        bit 2k + 1 violated, k indexing _lib.ENVELOPE_TESTS); each may be None.  box_lo / box_hi [sum M][3]: one box per segment, both or
+        neither.  params: fields of uavqp_envelope_params (depth, v_max, a_max, j_max, f_min, f_max, tilt_max; a limit of 0 is off).
+        Asynchronous."""
+        ep = self._envelope_params(params)
+        rc = _lib.lib().uavqp_envelope_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff), _ptr(status),
+                                              ctypes.byref(ep), _ptr(box_lo), _ptr(box_hi), _ptr(range_out), _ptr(norm_out), _ptr(peak_out),
+                                              _ptr(seg_verdict_out), _ptr(verdict_out))
+        _lib.check(rc, "uavqp_envelope_device")
+
+    def envelope(self, r, seg_offsets, times, coeff, uniform_segments=0, status=None, box_lo=None, box_hi=None, **params):
+        """uavqp_envelope_host: numpy in / numpy out (synchronous).  Returns (range [sum M][4][3][4], norm [sum M][5][4],
+        peak [n_traj][5][4], seg_verdict [sum M], verdict [n_traj]); see envelope_device."""
+        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
+        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total and coeff.size == 3 * 2 * r * total
+        if box_lo is not None:
+            box_lo = np.ascontiguousarray(box_lo, dtype=np.float64).reshape(total, 3)
+        if box_hi is not None:
+            box_hi = np.ascontiguousarray(box_hi, dtype=np.float64).reshape(total, 3)
+        ep = self._envelope_params(params)
+        rng = np.zeros((total, 4, 3, 4), dtype=np.float64)
+        norm = np.zeros((total, 5, 4), dtype=np.float64)
+        peak = np.zeros((n_traj, 5, 4), dtype=np.float64)
+        seg_verdict = np.zeros(total, dtype=np.int32)
+        verdict = np.zeros(n_traj, dtype=np.int32)
+        rc = _lib.lib().uavqp_envelope_host(self._h, r, n_traj, uniform_segments, _ptr(so), _ptr(times), _ptr(coeff), _ptr(status),
+                                            ctypes.byref(ep), _ptr(box_lo), _ptr(box_hi), _ptr(rng), _ptr(norm), _ptr(peak), _ptr(seg_verdict),
+                                            _ptr(verdict))
+        _lib.check(rc, "uavqp_envelope_host")
+        return rng, norm, peak, seg_verdict, verdict
+
     def attitude_optimize_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc, esdf,
                                  coeff_out, status_out, objective_out, accepted_out=None, peak_out=None, min_dist_out=None, outside_out=None,
                                  attitude_peak_out=None, limits=None, clearance=None, attitude=None, **params):
@@ -1020,6 +1068,7 @@ class TrajOptimizer:
     optimizeTrajectoryAttitude(esdf, ...)   optimizeTrajectoryLbfgs with the attitude penalty (thrust, tilt, body rate) in the objective
                                      (uavqp_attitude_optimize_host); .attitude_peak [n_traj][4] the sampled peaks at the result
     getAttitudePenalty(...)          [n_traj] attitude penalty of the stored coefficients at the stored durations; fills .attitude_peak
+    getEnvelope(depth, box, **limits)  certified bounds over whole segments and the certified / violated / undecided masks per limit
     getFlightPenalty(esdf, ...)      [n_traj] limit + clearance penalty of the stored coefficients in one launch
     setSwarm(group_offsets, start_times)   which trajectories fly together (swarm g = trajectories group_offsets[g] .. group_offsets[g + 1];
                                      None: the whole batch is one swarm) and when each departs on its swarm's clock (None: all at 0)
@@ -1227,6 +1276,27 @@ class TrajOptimizer:
             raise _lib.UavqpError("getAttitudePenalty: no solved coefficients (call solve() or an optimiser first)")
         phi, _, _, self.attitude_peak = self._ctx.attitude_penalty_host(self._r, self._so, self._T, self._coef, status=self.status, **params)
         return phi
+
+    def getEnvelope(self, depth=4, box=None, **limits):
+        """Certified bounds of the stored coefficients at the stored durations over WHOLE segments (uavqp_envelope_host; after solve() or
+        an optimiser): the acceptance test that needs no sampling density.  limits: v_max, a_max, j_max, f_min, f_max, tilt_max (0 or
+        absent: off); box: (lo, hi), each [sum M][3], one box per segment.  Returns a dict: range [sum M][4][3][4], norm [sum M][5][4],
+        peak [n_traj][5][4], seg_verdict, verdict (the int32 words) and, per trajectory, the boolean masks certified / violated /
+        undecided, each a dict keyed by test name (_lib.ENVELOPE_TESTS); a test that is off is False in all three."""
+        if self._ctx is None or self._coef.size != 3 * 2 * self._r * int(self._so[-1]) or self.status.size != self._so.size - 1:
+            raise _lib.UavqpError("getEnvelope: no solved coefficients (call solve() or an optimiser first)")
+        box_lo, box_hi = (None, None) if box is None else box
+        rng, norm, peak, seg_verdict, verdict = self._ctx.envelope(self._r, self._so, self._T, self._coef, status=self.status, box_lo=box_lo,
+                                                                   box_hi=box_hi, depth=depth, **limits)
+        on = {name: bool(limits.get(name, 0.0)) for name in _lib.ENVELOPE_TESTS}
+        on["box"] = box is not None
+        solved = self.status == _lib.UAVQP_SOLVED
+        out = dict(range=rng, norm=norm, peak=peak, seg_verdict=seg_verdict, verdict=verdict, certified={}, violated={}, undecided={})
+        for k, name in enumerate(_lib.ENVELOPE_TESTS):
+            c, v = (verdict >> (2 * k)) & 1 == 1, (verdict >> (2 * k + 1)) & 1 == 1
+            out["certified"][name], out["violated"][name] = c, v
+            out["undecided"][name] = ~c & ~v & solved if on[name] else np.zeros_like(c)
+        return out
 
     def getFlightPenalty(self, esdf, limits=None, clearance=None):
         """[n_traj] limit penalty + clearance penalty of the stored coefficients at the stored durations against `esdf`, in one launch
