@@ -43,6 +43,26 @@ static bool spacetime_params_valid(const uavqp_spacetime_params* p) {
     return true;
 }
 
+// the fields uavqp_spacetime_lbfgs_params and uavqp_swarm_opt_params share with the parameters of the projected-gradient entry, as that
+// struct (whose validity rule they follow)
+template <class P>
+static uavqp_spacetime_params spacetime_part_of(const P& p) {
+    uavqp_spacetime_params s;
+    std::memset(&s, 0, sizeof(s));
+    s.struct_size = (int32_t)sizeof(s);
+    s.max_iters = p.max_iters;
+    s.smooth_weight = p.smooth_weight; s.time_weight = p.time_weight; s.t_min = p.t_min; s.t_max = p.t_max; s.max_move = p.max_move;
+    s.initial_step_move = p.initial_step_move; s.initial_step_log = p.initial_step_log; s.armijo_c = p.armijo_c; s.shrink = p.shrink;
+    s.grow = p.grow;
+    return s;
+}
+
+// what the flight penalty needs of its caller: both parameter structs and a distance field of this ctx that has been updated
+static bool flight_params_valid(const uavqp_ctx* ctx, const uavqp_esdf* esdf, const uavqp_limit_params* limits,
+                                const uavqp_clearance_params* clearance) {
+    return limit_params_valid(limits) && esdf_usable(ctx, esdf) && esdf->updated && clearance_params_valid(clearance);
+}
+
 // (arguments checked by the callers)
 static int flight_penalty_enqueue(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
                                   const double* d_coeff, const int32_t* d_status, const uavqp_esdf* esdf, const uavqp_limit_params& L,
@@ -73,8 +93,7 @@ extern "C" int uavqp_flight_penalty_device(uavqp_ctx* ctx, int r, int n_traj, in
                                            const uavqp_limit_params* limits, const uavqp_clearance_params* clearance, double* d_penalty,
                                            double* d_grad_coeff, double* d_grad_times, double* d_peak, double* d_min_dist, int32_t* d_outside) {
     if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!limit_params_valid(limits)) return UAVQP_ERR_INVALID_ARG;
-    if (!esdf_usable(ctx, esdf) || !esdf->updated || !clearance_params_valid(clearance)) return UAVQP_ERR_INVALID_ARG;
+    if (!flight_params_valid(ctx, esdf, limits, clearance)) return UAVQP_ERR_INVALID_ARG;
     if (n_traj == 0 || (!d_penalty && !d_grad_coeff && !d_grad_times && !d_peak && !d_min_dist && !d_outside)) return UAVQP_OK;
     if (!d_times || !d_coeff || (uniform_segments == 0 && !d_seg_offsets)) return UAVQP_ERR_INVALID_ARG;
     UAVQP_HIP(hipSetDevice(ctx->device));
@@ -87,8 +106,7 @@ extern "C" int uavqp_flight_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int 
                                          const uavqp_clearance_params* clearance, double* penalty, double* grad_coeff, double* grad_times,
                                          double* peak, double* min_dist, int32_t* outside) {
     if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!limit_params_valid(limits)) return UAVQP_ERR_INVALID_ARG;
-    if (!esdf_usable(ctx, esdf) || !esdf->updated || !clearance_params_valid(clearance)) return UAVQP_ERR_INVALID_ARG;
+    if (!flight_params_valid(ctx, esdf, limits, clearance)) return UAVQP_ERR_INVALID_ARG;
     if (n_traj == 0 || (!penalty && !grad_coeff && !grad_times && !peak && !min_dist && !outside)) return UAVQP_OK;
     if (!times || !coeff || (uniform_segments == 0 && !seg_offsets)) return UAVQP_ERR_INVALID_ARG;
     BatchShape sh;
@@ -116,108 +134,144 @@ extern "C" int uavqp_flight_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int 
     return stage_end(ctx, st, "uavqp_flight_penalty_host");
 }
 
+// The workspace slots the three joint optimisers (this file, uavqp_spacetime_lbfgs.h, uavqp_swarm_opt.h) have in common, declared first;
+// the line-search state (per trajectory or per swarm) and the L-BFGS history follow with their owners.
+struct JointSlots {
+    size_t wp_bytes, t_bytes;
+    int wt, an, gp, thp;       // trial / anchor / gradient / through waypoints
+    int t0, t1, gt, tht, ex;   // the two trial-duration arrays, df/dT at the best point, dPhi/dT through the minimiser and explicit
+    int g, ph, ac, st;         // the coefficient gradient, phi, active, the status of the loop
+    void declare(Carve& c, int r, size_t n, size_t tot) {
+        wp_bytes = sizeof(double) * 3 * (tot + n); t_bytes = sizeof(double) * tot;
+        wt = c.add(wp_bytes); an = c.add(wp_bytes); gp = c.add(wp_bytes); thp = c.add(wp_bytes);
+        t0 = c.add(t_bytes); t1 = c.add(t_bytes); gt = c.add(t_bytes); tht = c.add(t_bytes); ex = c.add(t_bytes);
+        g = c.add(sizeof(double) * 3 * 2 * r * tot);
+        ph = c.add(sizeof(double) * n); ac = c.add(sizeof(int32_t) * n); st = c.add(sizeof(int32_t) * n);
+    }
+};
+
+// One call of a joint optimiser: the batch and the caller's arrays as the device entry got them, the workspace, where each point of the
+// sequence (uavqp_descent.h) lives, and the launches the three entries have in common.  The pointers are good behind carve_on(.., c).
+struct JointRun {
+    uavqp_ctx* ctx;
+    int r, n_traj, uniform_segments, max_segments, total_segments;
+    const int32_t* d_seg_offsets; double* d_waypoints; double* d_times; const double* d_bc;
+    const uavqp_esdf* esdf; const uavqp_limit_params* limits; const uavqp_clearance_params* clearance;
+    double* d_coeff_out; int32_t* d_status_out;
+    Carve c;
+    JointSlots k;
+
+    template <class T>
+    T* at(int i) const { return c.at<T>(i); }
+    // start and final: the caller's arrays.  Trial it: the trial waypoints, and of the two trial-duration arrays the one of parity it & 1
+    // (the step behind that solve reads it and writes the other)
+    double* trial_t(int it) const { return at<double>((it & 1) ? k.t1 : k.t0); }
+    const double* wp_at(const DescentPoint& p) const { return p.at == DescentAt::TRIAL ? at<double>(k.wt) : d_waypoints; }
+    const double* t_at(const DescentPoint& p) const { return p.at == DescentAt::TRIAL ? trial_t(p.it) : d_times; }
+    int32_t* status_at(const DescentPoint& p) const { return p.caller_status && d_status_out ? d_status_out : at<int32_t>(k.st); }
+    int32_t* status_final() const { return status_at(DescentPoint{DescentAt::FINAL, -1, true}); }   // (of what is handed back)
+
+    // the identically named fields of SpacetimeArgs and SwarmOptArgs, the ten scalar parameters included
+    template <class Args, class Params>
+    void fill(Args& a, const Params& P, double* d_objective_out, int32_t* d_accepted_out) const {
+        a.n_traj = n_traj; a.uniform = uniform_segments; a.seg_offsets = d_seg_offsets;
+        a.waypoints = d_waypoints; a.wp_trial = at<double>(k.wt); a.anchor = at<double>(k.an); a.gp_best = at<double>(k.gp);
+        a.times = d_times; a.gt_best = at<double>(k.gt);
+        a.coeff = d_coeff_out; a.status = status_at(DescentPoint{DescentAt::START, -1, P.max_iters == 0});
+        a.phi = at<double>(k.ph); a.explicit_t = at<double>(k.ex); a.through_p = at<double>(k.thp); a.through_t = at<double>(k.tht);
+        a.active = at<int32_t>(k.ac);
+        a.objective = d_objective_out; a.accepted = d_accepted_out;
+        a.ws = P.smooth_weight; a.wt = P.time_weight; a.t_min = P.t_min; a.t_max = P.t_max; a.max_move = P.max_move;
+        a.step_move = P.initial_step_move; a.step_log = P.initial_step_log; a.armijo = P.armijo_c; a.shrink = P.shrink; a.grow = P.grow;
+    }
+    // what changes from step to step: the durations the last solve ran at, those of the next trial, and whether there is one
+    template <class Args>
+    void before_step(Args& a, bool init, int it, bool propose) const {
+        a.t_eval = init ? d_times : trial_t(it);
+        a.t_next = trial_t(it + 1);
+        a.propose = propose ? 1 : 0;
+    }
+
+    // the start is the centre of the box; the trial waypoints start as a copy too, so that the rows no step writes (a trajectory without a
+    // segment) are the caller's
+    int anchor_copies(int max_iters) const {
+        UAVQP_HIP(hipMemcpyAsync(at<double>(k.an), d_waypoints, k.wp_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        if (max_iters > 0) UAVQP_HIP(hipMemcpyAsync(at<double>(k.wt), d_waypoints, k.wp_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        return UAVQP_OK;
+    }
+    // the inner solve is uavqp_solve_batch_device itself
+    int solve(const DescentPoint& p) const {
+        return uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, max_segments, d_seg_offsets, wp_at(p), t_at(p), d_bc, d_coeff_out,
+                                        status_at(p));
+    }
+    // the penalty of the point `coeff` was solved at and its two partial gradients ...
+    int flight_penalty(const DescentPoint& p) const {
+        return flight_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, t_at(p), d_coeff_out, status_at(p), esdf, *limits, *clearance,
+                                      at<double>(k.ph), at<double>(k.g), at<double>(k.ex), nullptr, nullptr, nullptr);
+    }
+    // ... and the coefficient gradient taken through the minimiser to the waypoints and the durations by ONE backward pass
+    int backward(const DescentPoint& p) const {
+        return uavqp_solve_backward_device(ctx, r, n_traj, uniform_segments, max_segments, total_segments, d_seg_offsets, wp_at(p), t_at(p), d_bc,
+                                           d_coeff_out, status_at(p), at<double>(k.g), at<double>(k.tht), at<double>(k.thp), nullptr);
+    }
+    // The sequence of all three: `a` is the entry's step arguments, more_penalty(point) what it accumulates on the flight penalty before the
+    // backward pass, launch(R, INIT) its step kernel (step_dispatch).
+    template <class Args, class Penalty, class Launch>
+    int descend(Args& a, int max_iters, Penalty&& more_penalty, Launch&& launch) const {
+        return descent_sequence(
+            max_iters, [&](const DescentPoint& p) -> int { return solve(p); },
+            [&](const DescentPoint& p) -> int {
+                int e = flight_penalty(p);
+                if (e == UAVQP_OK) e = more_penalty(p);
+                return e != UAVQP_OK ? e : backward(p);
+            },
+            [&](bool init, int it, bool propose) -> int {
+                before_step(a, init, it, propose);
+                return step_dispatch(r, init, launch);
+            });
+    }
+    // the penalty's diagnostics of what is handed back
+    int flight_diagnostics(double* d_peak_out, double* d_min_dist_out, int32_t* d_outside_out) const {
+        if (!d_peak_out && !d_min_dist_out && !d_outside_out) return UAVQP_OK;
+        return flight_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, status_final(), esdf, *limits, *clearance,
+                                      nullptr, nullptr, nullptr, d_peak_out, d_min_dist_out, d_outside_out);
+    }
+};
+
 extern "C" int uavqp_spacetime_optimize_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
                                                const int32_t* d_seg_offsets, double* d_waypoints, double* d_times, const double* d_bc,
                                                const uavqp_esdf* esdf, const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
                                                const uavqp_spacetime_params* params, double* d_coeff_out, int32_t* d_status_out,
                                                double* d_objective_out, int32_t* d_accepted_out, double* d_peak_out, double* d_min_dist_out,
                                                int32_t* d_outside_out) {
-    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0 || total_segments < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!spacetime_params_valid(params) || !limit_params_valid(limits)) return UAVQP_ERR_INVALID_ARG;
-    if (!esdf_usable(ctx, esdf) || !esdf->updated || !clearance_params_valid(clearance)) return UAVQP_ERR_INVALID_ARG;
-    if (n_traj == 0) return UAVQP_OK;
-    if (!d_waypoints || !d_times || !d_bc || !d_coeff_out || !d_objective_out) return UAVQP_ERR_INVALID_ARG;
-    if (uniform_segments == 0 && (!d_seg_offsets || max_segments < 1)) return UAVQP_ERR_INVALID_ARG;
-    if (uniform_segments > 0 && (long long)total_segments != (long long)uniform_segments * n_traj) return UAVQP_ERR_INVALID_ARG;
-    if ((long long)total_segments > 0x7fffffffLL - n_traj) return UAVQP_ERR_INVALID_ARG;   // (the waypoint rows are counted in ints)
-    UAVQP_HIP(hipSetDevice(ctx->device));
+    bool run;
+    int rc = descent_args_check(ctx, r, n_traj, 1, uniform_segments, max_segments, total_segments, d_seg_offsets,
+                                d_waypoints && d_times && d_bc && d_coeff_out && d_objective_out, true,
+                                [&] { return spacetime_params_valid(params) && flight_params_valid(ctx, esdf, limits, clearance); }, &run);
+    if (!run) return rc;
     const uavqp_spacetime_params P = *params;
-    const size_t n = (size_t)n_traj, tot = (size_t)total_segments, wp_bytes = sizeof(double) * 3 * (tot + n), t_bytes = sizeof(double) * tot;
+    const size_t n = (size_t)n_traj;
 
-    Carve c;
-    const int i_wt = c.add(wp_bytes), i_an = c.add(wp_bytes), i_gp = c.add(wp_bytes), i_thp = c.add(wp_bytes);
-    const int i_t0 = c.add(t_bytes), i_t1 = c.add(t_bytes), i_gt = c.add(t_bytes), i_tht = c.add(t_bytes), i_ex = c.add(t_bytes);
-    const int i_g = c.add(sizeof(double) * 3 * 2 * r * tot);
-    const int i_ph = c.add(sizeof(double) * n), i_fb = c.add(sizeof(double) * n), i_al = c.add(sizeof(double) * n), i_nd = c.add(sizeof(double) * n);
-    const int i_sg = c.add(sizeof(double) * 2 * n), i_ac = c.add(sizeof(int32_t) * n), i_st = c.add(sizeof(int32_t) * n);
-    int rc = carve_on(ctx->stream, ctx->topt, c);
+    JointRun j{ctx, r, n_traj, uniform_segments, max_segments, total_segments, d_seg_offsets, d_waypoints, d_times, d_bc, esdf, limits, clearance,
+               d_coeff_out, d_status_out};
+    j.k.declare(j.c, r, n, (size_t)total_segments);
+    const int i_fb = j.c.add(sizeof(double) * n), i_al = j.c.add(sizeof(double) * n), i_nd = j.c.add(sizeof(double) * n);
+    const int i_sg = j.c.add(sizeof(double) * 2 * n);
+    rc = carve_on(ctx->stream, ctx->topt, j.c);
     if (rc != UAVQP_OK) return rc;
-    int32_t* d_st_loop = c.at<int32_t>(i_st);
-    int32_t* d_st_final = d_status_out ? d_status_out : d_st_loop;
-    double* d_trial_t[2] = {c.at<double>(i_t0), c.at<double>(i_t1)};
 
     uavqp::SpacetimeArgs a;
-    a.n_traj = n_traj; a.uniform = uniform_segments; a.seg_offsets = d_seg_offsets;
-    a.waypoints = d_waypoints; a.wp_trial = c.at<double>(i_wt); a.anchor = c.at<double>(i_an); a.gp_best = c.at<double>(i_gp);
-    a.times = d_times; a.t_eval = d_times; a.t_next = d_trial_t[0]; a.gt_best = c.at<double>(i_gt);
-    a.coeff = d_coeff_out; a.status = P.max_iters > 0 ? d_st_loop : d_st_final;
-    a.phi = c.at<double>(i_ph); a.explicit_t = c.at<double>(i_ex); a.through_p = c.at<double>(i_thp); a.through_t = c.at<double>(i_tht);
-    a.fbest = c.at<double>(i_fb); a.alpha = c.at<double>(i_al); a.need = c.at<double>(i_nd); a.sigma = c.at<double>(i_sg);
-    a.active = c.at<int32_t>(i_ac);
-    a.objective = d_objective_out; a.accepted = d_accepted_out;
-    a.ws = P.smooth_weight; a.wt = P.time_weight; a.t_min = P.t_min; a.t_max = P.t_max; a.max_move = P.max_move;
-    a.step_move = P.initial_step_move; a.step_log = P.initial_step_log; a.armijo = P.armijo_c; a.shrink = P.shrink; a.grow = P.grow;
-    a.propose = P.max_iters > 0 ? 1 : 0;
-    // the penalty of the point `coeff` was solved at, its two partial gradients, and the coefficient gradient taken through the minimiser to
-    // the waypoints and the durations by ONE backward pass
-    auto penalty_and_backward = [&](const double* d_wp, const double* d_T, const int32_t* d_st) -> int {
-        int e = flight_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_T, d_coeff_out, d_st, esdf, *limits, *clearance,
-                                       c.at<double>(i_ph), c.at<double>(i_g), c.at<double>(i_ex), nullptr, nullptr, nullptr);
-        if (e != UAVQP_OK) return e;
-        return uavqp_solve_backward_device(ctx, r, n_traj, uniform_segments, max_segments, total_segments, d_seg_offsets, d_wp, d_T, d_bc,
-                                           d_coeff_out, d_st, c.at<double>(i_g), c.at<double>(i_tht), c.at<double>(i_thp), nullptr);
-    };
+    j.fill(a, P, d_objective_out, d_accepted_out);
+    a.fbest = j.at<double>(i_fb); a.alpha = j.at<double>(i_al); a.need = j.at<double>(i_nd); a.sigma = j.at<double>(i_sg);
     const int grid = topt_grid(ctx, n_traj);
-    hipStream_t s = ctx->stream;
-    auto step = [&](bool init) -> int {
-        if (r == 3 && init) hipLaunchKernelGGL((uavqp::spacetime_step_kernel<3, true>), dim3(grid), dim3(64), 0, s, a);
-        else if (r == 3) hipLaunchKernelGGL((uavqp::spacetime_step_kernel<3, false>), dim3(grid), dim3(64), 0, s, a);
-        else if (init) hipLaunchKernelGGL((uavqp::spacetime_step_kernel<4, true>), dim3(grid), dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((uavqp::spacetime_step_kernel<4, false>), dim3(grid), dim3(64), 0, s, a);
-        UAVQP_HIP(hipGetLastError());
-        return UAVQP_OK;
-    };
-    // the start is the centre of the box; the trial waypoints start as a copy too, so that the rows no step writes (a trajectory without a
-    // segment) are the caller's
-    UAVQP_HIP(hipMemcpyAsync(c.at<double>(i_an), d_waypoints, wp_bytes, hipMemcpyDeviceToDevice, s));
-    if (P.max_iters > 0) UAVQP_HIP(hipMemcpyAsync(a.wp_trial, d_waypoints, wp_bytes, hipMemcpyDeviceToDevice, s));
-    {
-        uavqp::TimeOptArgs k;   // (the clamp of the duration optimiser: it reads the span, the durations and the two bounds)
-        std::memset(&k, 0, sizeof(k));
-        k.n_traj = n_traj; k.uniform = uniform_segments; k.seg_offsets = d_seg_offsets; k.times = d_times; k.t_min = P.t_min; k.t_max = P.t_max;
-        if (r == 3) hipLaunchKernelGGL(uavqp::time_opt_clamp_kernel<3>, dim3(grid), dim3(64), 0, s, k);
-        else hipLaunchKernelGGL(uavqp::time_opt_clamp_kernel<4>, dim3(grid), dim3(64), 0, s, k);
-        UAVQP_HIP(hipGetLastError());
-    }
-    rc = uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, max_segments, d_seg_offsets, d_waypoints, d_times, d_bc, d_coeff_out,
-                                  const_cast<int32_t*>(a.status));
+    rc = j.anchor_copies(P.max_iters);
+    if (rc == UAVQP_OK) rc = time_clamp_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, P.t_min, P.t_max);
+    if (rc == UAVQP_OK)
+        rc = j.descend(a, P.max_iters, [](const DescentPoint&) { return UAVQP_OK; }, [&](auto R, auto INIT) {
+            hipLaunchKernelGGL((uavqp::spacetime_step_kernel<decltype(R)::value, decltype(INIT)::value>), dim3(grid), dim3(64), 0, ctx->stream, a);
+        });
     if (rc != UAVQP_OK) return rc;
-    rc = penalty_and_backward(d_waypoints, d_times, a.status);
-    if (rc != UAVQP_OK) return rc;
-    rc = step(true);
-    if (rc != UAVQP_OK) return rc;
-    for (int it = 0; it < P.max_iters; ++it) {
-        double* d_T = d_trial_t[it & 1];
-        rc = uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, max_segments, d_seg_offsets, a.wp_trial, d_T, d_bc, d_coeff_out, d_st_loop);
-        if (rc != UAVQP_OK) return rc;
-        rc = penalty_and_backward(a.wp_trial, d_T, d_st_loop);
-        if (rc != UAVQP_OK) return rc;
-        a.t_eval = d_T; a.t_next = d_trial_t[(it + 1) & 1];
-        a.propose = it + 1 < P.max_iters ? 1 : 0;
-        rc = step(false);
-        if (rc != UAVQP_OK) return rc;
-    }
-    if (P.max_iters > 0) {
-        // the coefficients on return are the solve AT the accepted point (the last trial of a trajectory may have been rejected, and a
-        // trajectory that never took part must carry what a plain solve leaves there)
-        rc = uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, max_segments, d_seg_offsets, d_waypoints, d_times, d_bc, d_coeff_out,
-                                      d_st_final);
-        if (rc != UAVQP_OK) return rc;
-    }
-    if (d_peak_out || d_min_dist_out || d_outside_out)   // the penalty's diagnostics of what is handed back
-        rc = flight_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, d_st_final, esdf, *limits, *clearance,
-                                    nullptr, nullptr, nullptr, d_peak_out, d_min_dist_out, d_outside_out);
-    return rc;
+    return j.flight_diagnostics(d_peak_out, d_min_dist_out, d_outside_out);
 }
 
 extern "C" int uavqp_spacetime_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
@@ -225,34 +279,12 @@ extern "C" int uavqp_spacetime_optimize_host(uavqp_ctx* ctx, int r, int n_traj, 
                                              const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
                                              const uavqp_spacetime_params* params, double* coeff_out, int32_t* status_out, double* objective_out,
                                              int32_t* accepted_out, double* peak_out, double* min_dist_out, int32_t* outside_out) {
-    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!spacetime_params_valid(params) || !limit_params_valid(limits)) return UAVQP_ERR_INVALID_ARG;
-    if (!esdf_usable(ctx, esdf) || !esdf->updated || !clearance_params_valid(clearance)) return UAVQP_ERR_INVALID_ARG;
-    if (n_traj == 0) return UAVQP_OK;
-    if (!waypoints || !times || !bc || !coeff_out || !objective_out) return UAVQP_ERR_INVALID_ARG;
-    if (uniform_segments == 0 && !seg_offsets) return UAVQP_ERR_INVALID_ARG;
-    BatchShape sh;
-    int rc = batch_shape(n_traj, uniform_segments, max_segments, seg_offsets, &sh);
-    if (rc != UAVQP_OK) return rc;
-    UAVQP_HIP(hipSetDevice(ctx->device));
-    const size_t n = (size_t)n_traj, tot = (size_t)sh.total_seg;
-    Stage st;
-    const int i_off = uniform_segments > 0 ? -1 : st.in(seg_offsets, sizeof(int32_t) * (n + 1));
-    const int i_wp = st.inout(waypoints, sizeof(double) * 3 * (tot + n));
-    const int i_t = st.inout(times, sizeof(double) * tot);
-    const int i_bc = st.in(bc, sizeof(double) * n * 2 * (r - 1) * 3);
-    const int i_out = st.out(coeff_out, sizeof(double) * 3 * 2 * r * tot, true);
-    const int i_st = st.out(status_out, sizeof(int32_t) * n);
-    const int i_obj = st.out(objective_out, sizeof(double) * 2 * n), i_acc = st.out(accepted_out, sizeof(int32_t) * n);
-    const int i_pk = peak_out ? st.out(peak_out, sizeof(double) * 2 * n) : -1;
-    const int i_md = min_dist_out ? st.out(min_dist_out, sizeof(double) * n) : -1;
-    const int i_o = outside_out ? st.out(outside_out, sizeof(int32_t) * n) : -1;
-    rc = stage_begin(ctx, st);
-    if (rc != UAVQP_OK) return rc;
-    rc = uavqp_spacetime_optimize_device(ctx, r, n_traj, uniform_segments, sh.Mmax, (int)sh.total_seg, st.at<int32_t>(i_off), st.at<double>(i_wp),
-                                         st.at<double>(i_t), st.at<double>(i_bc), esdf, limits, clearance, params, st.at<double>(i_out),
-                                         st.at<int32_t>(i_st), st.at<double>(i_obj), st.at<int32_t>(i_acc), st.at<double>(i_pk),
-                                         st.at<double>(i_md), st.at<int32_t>(i_o));
-    if (rc != UAVQP_OK) return rc;
-    return stage_end(ctx, st, "uavqp_spacetime_optimize_host");
+    return descent_run_host(
+        ctx, r, n_traj, uniform_segments, max_segments, seg_offsets, waypoints, waypoints, times, times, bc,
+        [&] { return spacetime_params_valid(params) && flight_params_valid(ctx, esdf, limits, clearance); }, coeff_out, status_out, objective_out,
+        accepted_out, peak_out, min_dist_out, outside_out, nullptr, 0, "uavqp_spacetime_optimize_host", [&](const DescentStaged& d) {
+            return uavqp_spacetime_optimize_device(ctx, r, n_traj, uniform_segments, d.Mmax, d.total_segments, d.seg_offsets, d.waypoints, d.times,
+                                                   d.bc, esdf, limits, clearance, params, d.coeff, d.status, d.objective, d.accepted, d.peak,
+                                                   d.min_dist, d.outside);
+        });
 }

@@ -32,21 +32,9 @@ extern "C" void uavqp_default_swarm_opt_params(uavqp_swarm_opt_params* p) {
     p->initial_step_start = 0.1;    // the first trial moves the most sensitive departure by 0.1 s
 }
 
-// the fields shared with uavqp_spacetime_params, as that struct
-static uavqp_spacetime_params swarm_opt_spacetime_part(const uavqp_swarm_opt_params& p) {
-    uavqp_spacetime_params s;
-    std::memset(&s, 0, sizeof(s));
-    s.struct_size = (int32_t)sizeof(s);
-    s.max_iters = p.max_iters;
-    s.smooth_weight = p.smooth_weight; s.time_weight = p.time_weight; s.t_min = p.t_min; s.t_max = p.t_max; s.max_move = p.max_move;
-    s.initial_step_move = p.initial_step_move; s.initial_step_log = p.initial_step_log;
-    s.armijo_c = p.armijo_c; s.shrink = p.shrink; s.grow = p.grow;
-    return s;
-}
-
 static bool swarm_opt_params_valid(const uavqp_swarm_opt_params* p) {
     if (!p || p->struct_size != (int32_t)sizeof(uavqp_swarm_opt_params)) return false;
-    const uavqp_spacetime_params s = swarm_opt_spacetime_part(*p);
+    const uavqp_spacetime_params s = spacetime_part_of(*p);
     if (!spacetime_params_valid(&s)) return false;
     if (!(p->start_window >= 0.0 && p->start_window < INFINITY)) return false;
     if (!(p->initial_step_start > 0.0 && p->initial_step_start < INFINITY)) return false;
@@ -60,127 +48,65 @@ extern "C" int uavqp_swarm_optimize_device(uavqp_ctx* ctx, int r, int n_traj, in
                                            const uavqp_swarm_params* swarm, const uavqp_swarm_opt_params* params, double* d_coeff_out,
                                            int32_t* d_status_out, double* d_objective_out, int32_t* d_accepted_out, double* d_peak_out,
                                            double* d_min_dist_out, int32_t* d_outside_out, double* d_min_sep_out) {
-    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0 || total_segments < 0 || n_groups < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!swarm_opt_params_valid(params) || !swarm_params_valid(swarm) || !limit_params_valid(limits)) return UAVQP_ERR_INVALID_ARG;
-    if (!esdf_usable(ctx, esdf) || !esdf->updated || !clearance_params_valid(clearance)) return UAVQP_ERR_INVALID_ARG;
-    if (!d_group_offsets && n_groups != 1) return UAVQP_ERR_INVALID_ARG;
-    if (params->start_window > 0.0 && !d_start) return UAVQP_ERR_INVALID_ARG;
-    if (n_traj == 0 || n_groups == 0) return UAVQP_OK;
-    if (!d_waypoints || !d_times || !d_bc || !d_coeff_out || !d_objective_out) return UAVQP_ERR_INVALID_ARG;
-    if (uniform_segments == 0 && (!d_seg_offsets || max_segments < 1)) return UAVQP_ERR_INVALID_ARG;
-    if (uniform_segments > 0 && (long long)total_segments != (long long)uniform_segments * n_traj) return UAVQP_ERR_INVALID_ARG;
-    if ((long long)total_segments > 0x7fffffffLL - n_traj) return UAVQP_ERR_INVALID_ARG;   // (the waypoint rows are counted in ints)
-    UAVQP_HIP(hipSetDevice(ctx->device));
+    bool run;
+    int rc = descent_args_check(ctx, r, n_traj, n_groups, uniform_segments, max_segments, total_segments, d_seg_offsets,
+                                d_waypoints && d_times && d_bc && d_coeff_out && d_objective_out, true, [&] {
+                                    return swarm_opt_params_valid(params) && swarm_params_valid(swarm) &&
+                                           flight_params_valid(ctx, esdf, limits, clearance) && (d_group_offsets || n_groups == 1) &&
+                                           (d_start || !(params->start_window > 0.0));
+                                }, &run);
+    if (!run) return rc;
     const uavqp_swarm_opt_params P = *params;
-    const size_t n = (size_t)n_traj, tot = (size_t)total_segments, ng = (size_t)n_groups;
-    const size_t wp_bytes = sizeof(double) * 3 * (tot + n), t_bytes = sizeof(double) * tot, s_bytes = sizeof(double) * n;
+    const size_t n = (size_t)n_traj, ng = (size_t)n_groups, s_bytes = sizeof(double) * n;
     const bool starts = d_start != nullptr;
 
-    Carve c;
-    const int i_wt = c.add(wp_bytes), i_an = c.add(wp_bytes), i_gp = c.add(wp_bytes), i_thp = c.add(wp_bytes);
-    const int i_t0 = c.add(t_bytes), i_t1 = c.add(t_bytes), i_gt = c.add(t_bytes), i_tht = c.add(t_bytes), i_ex = c.add(t_bytes);
-    const int i_g = c.add(sizeof(double) * 3 * 2 * r * tot);
-    const int i_ph = c.add(sizeof(double) * n), i_ac = c.add(sizeof(int32_t) * n), i_st = c.add(sizeof(int32_t) * n);
+    JointRun j{ctx, r, n_traj, uniform_segments, max_segments, total_segments, d_seg_offsets, d_waypoints, d_times, d_bc, esdf, limits, clearance,
+               d_coeff_out, d_status_out};
+    Carve& c = j.c;
+    j.k.declare(c, r, n, (size_t)total_segments);
     const int i_str = c.add(s_bytes, starts), i_san = c.add(s_bytes, starts), i_gs = c.add(s_bytes, starts), i_gsb = c.add(s_bytes, starts);
     const int i_phs = c.add(sizeof(double) * ng), i_fb = c.add(sizeof(double) * ng), i_al = c.add(sizeof(double) * ng);
     const int i_nd = c.add(sizeof(double) * ng), i_sg = c.add(sizeof(double) * 3 * ng), i_ga = c.add(sizeof(int32_t) * ng);
-    int rc = carve_on(ctx->stream, ctx->topt, c);
+    rc = carve_on(ctx->stream, ctx->topt, c);
     if (rc != UAVQP_OK) return rc;
-    int32_t* d_st_loop = c.at<int32_t>(i_st);
-    int32_t* d_st_final = d_status_out ? d_status_out : d_st_loop;
-    double* d_trial_t[2] = {c.at<double>(i_t0), c.at<double>(i_t1)};
 
     uavqp::SwarmOptArgs a;
-    a.n_traj = n_traj; a.uniform = uniform_segments; a.n_groups = n_groups; a.seg_offsets = d_seg_offsets; a.group_offsets = d_group_offsets;
-    a.waypoints = d_waypoints; a.wp_trial = c.at<double>(i_wt); a.anchor = c.at<double>(i_an); a.gp_best = c.at<double>(i_gp);
-    a.times = d_times; a.t_eval = d_times; a.t_next = d_trial_t[0]; a.gt_best = c.at<double>(i_gt);
-    a.coeff = d_coeff_out; a.status = P.max_iters > 0 ? d_st_loop : d_st_final;
-    a.phi = c.at<double>(i_ph); a.explicit_t = c.at<double>(i_ex); a.through_p = c.at<double>(i_thp); a.through_t = c.at<double>(i_tht);
-    a.active = c.at<int32_t>(i_ac);
+    j.fill(a, P, d_objective_out, d_accepted_out);
+    a.n_groups = n_groups; a.group_offsets = d_group_offsets;
     a.start = d_start; a.start_trial = c.at<double>(i_str); a.start_anchor = c.at<double>(i_san); a.grad_start = c.at<double>(i_gs);
     a.gs_best = c.at<double>(i_gsb);
     a.phi_swarm = c.at<double>(i_phs); a.fbest = c.at<double>(i_fb); a.alpha = c.at<double>(i_al); a.need = c.at<double>(i_nd);
     a.sigma = c.at<double>(i_sg); a.g_active = c.at<int32_t>(i_ga);
-    a.objective = d_objective_out; a.accepted = d_accepted_out;
-    a.ws = P.smooth_weight; a.wt = P.time_weight; a.t_min = P.t_min; a.t_max = P.t_max; a.max_move = P.max_move;
-    a.step_move = P.initial_step_move; a.step_log = P.initial_step_log; a.armijo = P.armijo_c; a.shrink = P.shrink; a.grow = P.grow;
     a.window = P.start_window; a.step_start = P.initial_step_start;
-    a.propose = P.max_iters > 0 ? 1 : 0;
-    // both penalties of the point `coeff` was solved at, the sum of their partial gradients in ONE pair of arrays, and that coefficient
-    // gradient taken through the minimiser to the waypoints and the durations by ONE backward pass
-    auto penalties_and_backward = [&](const double* d_wp, const double* d_T, const double* d_s, const int32_t* d_st) -> int {
-        int e = flight_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_T, d_coeff_out, d_st, esdf, *limits, *clearance,
-                                       c.at<double>(i_ph), c.at<double>(i_g), c.at<double>(i_ex), nullptr, nullptr, nullptr);
-        if (e != UAVQP_OK) return e;
-        e = swarm_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_T, d_coeff_out, d_st, n_groups, d_group_offsets, d_s, *swarm,
-                                  c.at<double>(i_phs), c.at<double>(i_g), c.at<double>(i_ex), c.at<double>(i_gs), nullptr, true);
-        if (e != UAVQP_OK) return e;
-        return uavqp_solve_backward_device(ctx, r, n_traj, uniform_segments, max_segments, total_segments, d_seg_offsets, d_wp, d_T, d_bc,
-                                           d_coeff_out, d_st, c.at<double>(i_g), c.at<double>(i_tht), c.at<double>(i_thp), nullptr);
+    // the swarm penalty at the departures of the point `coeff` was solved at ADDS to what the flight penalty has just written: the sum of
+    // the partial gradients in ONE pair of arrays, for ONE backward pass
+    auto swarm_penalty = [&](const DescentPoint& p) -> int {
+        const double* d_s = p.at == DescentAt::TRIAL ? a.start_trial : d_start;   // (null without departures, either way)
+        return swarm_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, j.t_at(p), d_coeff_out, j.status_at(p), n_groups,
+                                     d_group_offsets, d_s, *swarm, c.at<double>(i_phs), j.at<double>(j.k.g), j.at<double>(j.k.ex),
+                                     c.at<double>(i_gs), nullptr, true);
     };
     // one workgroup per swarm, grid-stride past eight resident workgroups per CU
     const int cap = ctx->num_cus * 8;
     const int grid = n_groups < cap ? n_groups : cap;
     hipStream_t s = ctx->stream;
-    auto step = [&](bool init) -> int {
-        const dim3 blk(uavqp::SWOPT_BLOCK);
-        if (r == 3 && init) hipLaunchKernelGGL((uavqp::swarm_step_kernel<3, true>), dim3(grid), blk, 0, s, a);
-        else if (r == 3) hipLaunchKernelGGL((uavqp::swarm_step_kernel<3, false>), dim3(grid), blk, 0, s, a);
-        else if (init) hipLaunchKernelGGL((uavqp::swarm_step_kernel<4, true>), dim3(grid), blk, 0, s, a);
-        else hipLaunchKernelGGL((uavqp::swarm_step_kernel<4, false>), dim3(grid), blk, 0, s, a);
-        UAVQP_HIP(hipGetLastError());
-        return UAVQP_OK;
-    };
     // the start is the centre of the box and of the window; the trial waypoints and departures start as copies too, so that what no step
     // writes (a trajectory without a segment, a vehicle outside every swarm) is the caller's
-    UAVQP_HIP(hipMemcpyAsync(c.at<double>(i_an), d_waypoints, wp_bytes, hipMemcpyDeviceToDevice, s));
-    if (P.max_iters > 0) UAVQP_HIP(hipMemcpyAsync(a.wp_trial, d_waypoints, wp_bytes, hipMemcpyDeviceToDevice, s));
+    rc = j.anchor_copies(P.max_iters);
+    if (rc != UAVQP_OK) return rc;
     if (starts) {
         UAVQP_HIP(hipMemcpyAsync(c.at<double>(i_san), d_start, s_bytes, hipMemcpyDeviceToDevice, s));
         UAVQP_HIP(hipMemcpyAsync(a.start_trial, d_start, s_bytes, hipMemcpyDeviceToDevice, s));
     }
-    const int tgrid = topt_grid(ctx, n_traj);
-    {
-        uavqp::TimeOptArgs k;   // (the clamp of the duration optimiser: it reads the span, the durations and the two bounds)
-        std::memset(&k, 0, sizeof(k));
-        k.n_traj = n_traj; k.uniform = uniform_segments; k.seg_offsets = d_seg_offsets; k.times = d_times; k.t_min = P.t_min; k.t_max = P.t_max;
-        if (r == 3) hipLaunchKernelGGL(uavqp::time_opt_clamp_kernel<3>, dim3(tgrid), dim3(64), 0, s, k);
-        else hipLaunchKernelGGL(uavqp::time_opt_clamp_kernel<4>, dim3(tgrid), dim3(64), 0, s, k);
-        UAVQP_HIP(hipGetLastError());
-    }
-    rc = uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, max_segments, d_seg_offsets, d_waypoints, d_times, d_bc, d_coeff_out,
-                                  const_cast<int32_t*>(a.status));
-    if (rc != UAVQP_OK) return rc;
-    rc = penalties_and_backward(d_waypoints, d_times, d_start, a.status);
-    if (rc != UAVQP_OK) return rc;
-    rc = step(true);
-    if (rc != UAVQP_OK) return rc;
-    for (int it = 0; it < P.max_iters; ++it) {
-        double* d_T = d_trial_t[it & 1];
-        rc = uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, max_segments, d_seg_offsets, a.wp_trial, d_T, d_bc, d_coeff_out, d_st_loop);
-        if (rc != UAVQP_OK) return rc;
-        rc = penalties_and_backward(a.wp_trial, d_T, starts ? a.start_trial : nullptr, d_st_loop);
-        if (rc != UAVQP_OK) return rc;
-        a.t_eval = d_T; a.t_next = d_trial_t[(it + 1) & 1];
-        a.propose = it + 1 < P.max_iters ? 1 : 0;
-        rc = step(false);
-        if (rc != UAVQP_OK) return rc;
-    }
-    if (P.max_iters > 0) {
-        // the coefficients on return are the solve AT the accepted point (the last trial of a swarm may have been rejected, and a
-        // trajectory that never took part must carry what a plain solve leaves there)
-        rc = uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, max_segments, d_seg_offsets, d_waypoints, d_times, d_bc, d_coeff_out,
-                                      d_st_final);
-        if (rc != UAVQP_OK) return rc;
-    }
-    if (d_peak_out || d_min_dist_out || d_outside_out) {   // the penalties' diagnostics of what is handed back
-        rc = flight_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, d_st_final, esdf, *limits, *clearance,
-                                    nullptr, nullptr, nullptr, d_peak_out, d_min_dist_out, d_outside_out);
-        if (rc != UAVQP_OK) return rc;
-    }
-    if (d_min_sep_out)
-        rc = swarm_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, d_st_final, n_groups, d_group_offsets,
-                                   d_start, *swarm, nullptr, nullptr, nullptr, nullptr, d_min_sep_out);
+    rc = time_clamp_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, P.t_min, P.t_max);
+    if (rc == UAVQP_OK)
+        rc = j.descend(a, P.max_iters, swarm_penalty, [&](auto R, auto INIT) {
+            hipLaunchKernelGGL((uavqp::swarm_step_kernel<decltype(R)::value, decltype(INIT)::value>), dim3(grid), dim3(uavqp::SWOPT_BLOCK), 0, s, a);
+        });
+    if (rc == UAVQP_OK) rc = j.flight_diagnostics(d_peak_out, d_min_dist_out, d_outside_out);   // the penalties' diagnostics of what is handed back
+    if (rc == UAVQP_OK && d_min_sep_out)
+        rc = swarm_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, j.status_final(), n_groups,
+                                   d_group_offsets, d_start, *swarm, nullptr, nullptr, nullptr, nullptr, d_min_sep_out);
     return rc;
 }
 
@@ -192,8 +118,8 @@ extern "C" int uavqp_swarm_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int 
                                          int32_t* accepted_out, double* peak_out, double* min_dist_out, int32_t* outside_out,
                                          double* min_sep_out) {
     if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0 || n_groups < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!swarm_opt_params_valid(params) || !swarm_params_valid(swarm) || !limit_params_valid(limits)) return UAVQP_ERR_INVALID_ARG;
-    if (!esdf_usable(ctx, esdf) || !esdf->updated || !clearance_params_valid(clearance)) return UAVQP_ERR_INVALID_ARG;
+    if (!swarm_opt_params_valid(params) || !swarm_params_valid(swarm)) return UAVQP_ERR_INVALID_ARG;
+    if (!flight_params_valid(ctx, esdf, limits, clearance)) return UAVQP_ERR_INVALID_ARG;
     if (!group_offsets && n_groups != 1) return UAVQP_ERR_INVALID_ARG;
     if (params->start_window > 0.0 && !start) return UAVQP_ERR_INVALID_ARG;
     if (n_traj == 0 || n_groups == 0) return UAVQP_OK;

@@ -8,7 +8,12 @@
 // With limits (uavqp_time_optimize_limits_device, uavqp_limits.h) every step is preceded by the penalty of the point just solved and the
 // backward pass of its coefficient gradient:
 //     clamp -> solve(times) -> penalty, backward -> step<INIT> -> max_iters x { solve(trial) -> penalty, backward -> step<ITER> } -> solve(times)
+// The order itself is descent_sequence (uavqp_descent.h), here and in every optimiser included behind this file; what they share around it
+// is here too: descent_args_check, time_clamp_enqueue, step_dispatch and the staging of the _host entries (descent_run_host).
 #pragma once
+#include <type_traits>
+#include "uavqp_descent.h"
+static_assert(UAVQP_OK == 0, "descent_sequence goes on while its hooks return 0");
 
 // (uavqp_limits.h, included behind this file and uavqp_adjoint.h)
 static int limit_penalty_enqueue(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
@@ -65,18 +70,63 @@ static bool topt_params_valid(const uavqp_time_opt_params* p) {
     return true;
 }
 
+// What every descent entry refuses, in the precedence their contracts state: ctx, r and the counts (n_groups: the swarm entry's, 1
+// elsewhere); the entry's parameter structs (params_ok, called only behind the former); nothing to do -- UAVQP_OK, *run stays false;
+// a missing array (arrays: the entry's own pointers, all non-null), offsets or max_segments; uniform_segments x n_traj against
+// total_segments; and, under int_rows, the waypoint rows total_segments + n_traj that the kernels count in ints.  *run: the device is set.
+template <class ParamsOk>
+static int descent_args_check(const uavqp_ctx* ctx, int r, int n_traj, int n_groups, int uniform_segments, int max_segments, int total_segments,
+                              const int32_t* d_seg_offsets, bool arrays, bool int_rows, ParamsOk&& params_ok, bool* run) {
+    *run = false;
+    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || n_groups < 0 || uniform_segments < 0 || total_segments < 0) return UAVQP_ERR_INVALID_ARG;
+    if (!params_ok()) return UAVQP_ERR_INVALID_ARG;
+    if (n_traj == 0 || n_groups == 0) return UAVQP_OK;
+    if (!arrays) return UAVQP_ERR_INVALID_ARG;
+    if (uniform_segments == 0 && (!d_seg_offsets || max_segments < 1)) return UAVQP_ERR_INVALID_ARG;
+    if (uniform_segments > 0 && (long long)total_segments != (long long)uniform_segments * n_traj) return UAVQP_ERR_INVALID_ARG;
+    if (int_rows && (long long)total_segments > 0x7fffffffLL - n_traj) return UAVQP_ERR_INVALID_ARG;
+    UAVQP_HIP(hipSetDevice(ctx->device));
+    *run = true;
+    return UAVQP_OK;
+}
+
+// the clamp of the duration optimiser: it reads the span, the durations and the two bounds
+static int time_clamp_enqueue(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, double* d_times, double t_min,
+                              double t_max) {
+    uavqp::TimeOptArgs k;
+    std::memset(&k, 0, sizeof(k));
+    k.n_traj = n_traj; k.uniform = uniform_segments; k.seg_offsets = d_seg_offsets; k.times = d_times; k.t_min = t_min; k.t_max = t_max;
+    const int grid = topt_grid(ctx, n_traj);
+    if (r == 3) hipLaunchKernelGGL(uavqp::time_opt_clamp_kernel<3>, dim3(grid), dim3(64), 0, ctx->stream, k);
+    else hipLaunchKernelGGL(uavqp::time_opt_clamp_kernel<4>, dim3(grid), dim3(64), 0, ctx->stream, k);
+    UAVQP_HIP(hipGetLastError());
+    return UAVQP_OK;
+}
+
+// The four-way <R, INIT> dispatch of a step kernel and the error of its launch.  launch(R, INIT) gets the two as integral constants and
+// names its kernel with decltype(R)::value, decltype(INIT)::value (and whatever further template arguments it has).
+template <class Launch>
+static int step_dispatch(int r, bool init, Launch&& launch) {
+    using R3 = std::integral_constant<int, 3>;
+    using R4 = std::integral_constant<int, 4>;
+    if (r == 3 && init) launch(R3{}, std::true_type{});
+    else if (r == 3) launch(R3{}, std::false_type{});
+    else if (init) launch(R4{}, std::true_type{});
+    else launch(R4{}, std::false_type{});
+    UAVQP_HIP(hipGetLastError());
+    return UAVQP_OK;
+}
+
 // limits = null: uavqp_time_optimize_device.  Otherwise (validated by the caller) f and its gradient carry the limit penalty.
 static int time_optimize_run(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
                              const int32_t* d_seg_offsets, const double* d_waypoints, double* d_times, const double* d_bc,
                              const uavqp_time_opt_params* params, double* d_coeff_out, int32_t* d_status_out, double* d_objective_out,
                              int32_t* d_accepted_out, const uavqp_limit_params* limits, double* d_peak_out) {
-    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0 || total_segments < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!topt_params_valid(params)) return UAVQP_ERR_INVALID_ARG;
-    if (n_traj == 0) return UAVQP_OK;
-    if (!d_waypoints || !d_times || !d_bc || !d_coeff_out || !d_objective_out) return UAVQP_ERR_INVALID_ARG;
-    if (uniform_segments == 0 && (!d_seg_offsets || max_segments < 1)) return UAVQP_ERR_INVALID_ARG;
-    if (uniform_segments > 0 && (long long)total_segments != (long long)uniform_segments * n_traj) return UAVQP_ERR_INVALID_ARG;
-    UAVQP_HIP(hipSetDevice(ctx->device));
+    bool run;
+    int rc = descent_args_check(ctx, r, n_traj, 1, uniform_segments, max_segments, total_segments, d_seg_offsets,
+                                d_waypoints && d_times && d_bc && d_coeff_out && d_objective_out, false,
+                                [&] { return topt_params_valid(params); }, &run);
+    if (!run) return rc;
     const uavqp_time_opt_params P = *params;
     const size_t n = (size_t)n_traj, tot = (size_t)total_segments;
 
@@ -86,7 +136,7 @@ static int time_optimize_run(uavqp_ctx* ctx, int r, int n_traj, int uniform_segm
     const bool lim = limits != nullptr;
     const int i_lg = c.add(sizeof(double) * 3 * 2 * r * tot, lim), i_le = c.add(sizeof(double) * tot, lim), i_lt = c.add(sizeof(double) * tot, lim);
     const int i_lp = c.add(sizeof(double) * n, lim);
-    int rc = carve_on(ctx->stream, ctx->topt, c);
+    rc = carve_on(ctx->stream, ctx->topt, c);
     if (rc != UAVQP_OK) return rc;
     int32_t* d_st_loop = c.at<int32_t>(i_st);
     int32_t* d_st_final = d_status_out ? d_status_out : d_st_loop;
@@ -94,74 +144,46 @@ static int time_optimize_run(uavqp_ctx* ctx, int r, int n_traj, int uniform_segm
     uavqp::TimeOptArgs a;
     a.n_traj = n_traj; a.uniform = uniform_segments; a.seg_offsets = d_seg_offsets;
     a.times = d_times; a.trial = c.at<double>(i_tr); a.gbest = c.at<double>(i_gb);
-    a.coeff = d_coeff_out; a.status = P.max_iters > 0 ? d_st_loop : d_st_final;
+    a.coeff = d_coeff_out;
     a.fbest = c.at<double>(i_fb); a.alpha = c.at<double>(i_al); a.need = c.at<double>(i_nd); a.active = c.at<int32_t>(i_ac);
     a.objective = d_objective_out; a.accepted = d_accepted_out;
     a.w = P.time_weight; a.t_min = P.t_min; a.t_max = P.t_max; a.initial_step = P.initial_step; a.armijo = P.armijo_c;
     a.shrink = P.shrink; a.grow = P.grow;
-    a.propose = P.max_iters > 0 ? 1 : 0;
     a.phi = c.at<double>(i_lp); a.lim_explicit = c.at<double>(i_le); a.lim_through = c.at<double>(i_lt);
-    // the penalty of the point `coeff` was solved at, its gradient in the coefficients, and that gradient taken through the minimiser
-    auto penalty_and_backward = [&](const double* d_T, const int32_t* d_st) -> int {
-        int e = limit_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_T, d_coeff_out, d_st, *limits, c.at<double>(i_lp),
-                                      c.at<double>(i_lg), c.at<double>(i_le), nullptr);
-        if (e != UAVQP_OK) return e;
-        return uavqp_solve_backward_device(ctx, r, n_traj, uniform_segments, max_segments, total_segments, d_seg_offsets, d_waypoints, d_T, d_bc,
-                                           d_coeff_out, d_st, c.at<double>(i_lg), c.at<double>(i_lt), nullptr, nullptr);
-    };
     const int grid = topt_grid(ctx, n_traj);
     hipStream_t s = ctx->stream;
-#define UAVQP_TOPT_LAUNCH(KERNEL_)                                                                            \
-    do {                                                                                                      \
-        if (r == 3) hipLaunchKernelGGL((uavqp::KERNEL_(3)), dim3(grid), dim3(64), 0, s, a);                    \
-        else hipLaunchKernelGGL((uavqp::KERNEL_(4)), dim3(grid), dim3(64), 0, s, a);                           \
-        UAVQP_HIP(hipGetLastError());                                                                         \
-    } while (0)
-#define UAVQP_TOPT_CLAMP(R_) time_opt_clamp_kernel<R_>
-#define UAVQP_TOPT_INIT(R_) time_opt_step_kernel<R_, true>
-#define UAVQP_TOPT_ITER(R_) time_opt_step_kernel<R_, false>
-#define UAVQP_TOPT_INIT_LIM(R_) time_opt_step_kernel<R_, true, true>
-#define UAVQP_TOPT_ITER_LIM(R_) time_opt_step_kernel<R_, false, true>
-    UAVQP_TOPT_LAUNCH(UAVQP_TOPT_CLAMP);
-    rc = uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, max_segments, d_seg_offsets, d_waypoints, d_times, d_bc, d_coeff_out,
-                                  const_cast<int32_t*>(a.status));
+    // the durations and the status of a point of the sequence; the step kernel reads the status of the solve before it
+    auto times_at = [&](const DescentPoint& p) { return p.at == DescentAt::TRIAL ? a.trial : d_times; };
+    auto solve = [&](const DescentPoint& p) -> int {
+        a.status = p.caller_status ? d_st_final : d_st_loop;
+        return uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, max_segments, d_seg_offsets, d_waypoints, times_at(p), d_bc, d_coeff_out,
+                                        const_cast<int32_t*>(a.status));
+    };
+    // the penalty of the point `coeff` was solved at, its gradient in the coefficients, and that gradient taken through the minimiser
+    auto penalty_and_backward = [&](const DescentPoint& p) -> int {
+        if (!lim) return UAVQP_OK;
+        int e = limit_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, times_at(p), d_coeff_out, a.status, *limits,
+                                      c.at<double>(i_lp), c.at<double>(i_lg), c.at<double>(i_le), nullptr);
+        if (e != UAVQP_OK) return e;
+        return uavqp_solve_backward_device(ctx, r, n_traj, uniform_segments, max_segments, total_segments, d_seg_offsets, d_waypoints, times_at(p),
+                                           d_bc, d_coeff_out, a.status, c.at<double>(i_lg), c.at<double>(i_lt), nullptr, nullptr);
+    };
+    auto step = [&](bool init, int, bool propose) -> int {
+        a.propose = propose ? 1 : 0;
+        return step_dispatch(r, init, [&](auto R, auto INIT) {
+            constexpr int R_ = decltype(R)::value;
+            constexpr bool INIT_ = decltype(INIT)::value;
+            if (lim) hipLaunchKernelGGL((uavqp::time_opt_step_kernel<R_, INIT_, true>), dim3(grid), dim3(64), 0, s, a);
+            else hipLaunchKernelGGL((uavqp::time_opt_step_kernel<R_, INIT_>), dim3(grid), dim3(64), 0, s, a);
+        });
+    };
+    rc = time_clamp_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, P.t_min, P.t_max);
     if (rc != UAVQP_OK) return rc;
-    if (lim) {
-        rc = penalty_and_backward(d_times, a.status);
-        if (rc != UAVQP_OK) return rc;
-        UAVQP_TOPT_LAUNCH(UAVQP_TOPT_INIT_LIM);
-    } else {
-        UAVQP_TOPT_LAUNCH(UAVQP_TOPT_INIT);
-    }
-    for (int it = 0; it < P.max_iters; ++it) {
-        rc = uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, max_segments, d_seg_offsets, d_waypoints, a.trial, d_bc, d_coeff_out,
-                                      d_st_loop);
-        if (rc != UAVQP_OK) return rc;
-        a.propose = it + 1 < P.max_iters ? 1 : 0;
-        if (lim) {
-            rc = penalty_and_backward(a.trial, d_st_loop);
-            if (rc != UAVQP_OK) return rc;
-            UAVQP_TOPT_LAUNCH(UAVQP_TOPT_ITER_LIM);
-        } else {
-            UAVQP_TOPT_LAUNCH(UAVQP_TOPT_ITER);
-        }
-    }
-    if (P.max_iters > 0) {
-        // the coefficients on return are the solve AT the accepted durations (the last trial of a trajectory may have been rejected, and a
-        // trajectory that never took part must carry what a plain solve leaves there)
-        rc = uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, max_segments, d_seg_offsets, d_waypoints, d_times, d_bc, d_coeff_out,
-                                      d_st_final);
-        if (rc != UAVQP_OK) return rc;
-    }
+    rc = descent_sequence(P.max_iters, solve, penalty_and_backward, step);
+    if (rc != UAVQP_OK) return rc;
     if (lim && d_peak_out)   // the sampled peaks of what is handed back
         rc = limit_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, d_st_final, *limits, nullptr, nullptr,
                                    nullptr, d_peak_out);
-#undef UAVQP_TOPT_LAUNCH
-#undef UAVQP_TOPT_CLAMP
-#undef UAVQP_TOPT_INIT
-#undef UAVQP_TOPT_ITER
-#undef UAVQP_TOPT_INIT_LIM
-#undef UAVQP_TOPT_ITER_LIM
     return rc;
 }
 
@@ -173,12 +195,26 @@ extern "C" int uavqp_time_optimize_device(uavqp_ctx* ctx, int r, int n_traj, int
                              d_coeff_out, d_status_out, d_objective_out, d_accepted_out, nullptr, nullptr);
 }
 
-static int time_optimize_run_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
-                                  const double* waypoints, double* times, const double* bc, const uavqp_time_opt_params* params,
-                                  double* coeff_out, int32_t* status_out, double* objective_out, int32_t* accepted_out,
-                                  const uavqp_limit_params* limits, double* peak_out, const char* who) {
+// The device arrays of a descent optimiser's _host entry, as its device implementation takes them (null: an output the entry does not
+// have or the caller does not want; extra: the one diagnostic beyond peak / min_dist / outside).
+struct DescentStaged {
+    int Mmax, total_segments;
+    const int32_t* seg_offsets; double* waypoints; double* times; const double* bc;
+    double* coeff; int32_t* status; double* objective; int32_t* accepted;
+    double* peak; double* min_dist; int32_t* outside; double* extra;
+};
+
+// The _host entries of the per-trajectory optimisers: the checks (params_ok: the entry's parameter structs), the staging of the arrays and
+// device(DescentStaged) between stage_begin and stage_end.  waypoints_back / times_back: the same pointer where the entry optimises the
+// array (inout), null where it only reads it.  extra_out: extra_per_traj doubles per trajectory.
+template <class ParamsOk, class Device>
+static int descent_run_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                            const double* waypoints, double* waypoints_back, const double* times, double* times_back, const double* bc,
+                            ParamsOk&& params_ok, double* coeff_out, int32_t* status_out, double* objective_out, int32_t* accepted_out,
+                            double* peak_out, double* min_dist_out, int32_t* outside_out, double* extra_out, size_t extra_per_traj, const char* who,
+                            Device&& device) {
     if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!topt_params_valid(params)) return UAVQP_ERR_INVALID_ARG;
+    if (!params_ok()) return UAVQP_ERR_INVALID_ARG;
     if (n_traj == 0) return UAVQP_OK;
     if (!waypoints || !times || !bc || !coeff_out || !objective_out) return UAVQP_ERR_INVALID_ARG;
     if (uniform_segments == 0 && !seg_offsets) return UAVQP_ERR_INVALID_ARG;
@@ -189,20 +225,36 @@ static int time_optimize_run_host(uavqp_ctx* ctx, int r, int n_traj, int uniform
     const size_t n = (size_t)n_traj, tot = (size_t)sh.total_seg;
     Stage st;
     const int i_off = uniform_segments > 0 ? -1 : st.in(seg_offsets, sizeof(int32_t) * (n + 1));
-    const int i_wp = st.in(waypoints, sizeof(double) * 3 * (tot + n));
-    const int i_t = st.inout(times, sizeof(double) * tot);
+    const int i_wp = st.add(waypoints, waypoints_back, sizeof(double) * 3 * (tot + n), false);
+    const int i_t = st.add(times, times_back, sizeof(double) * tot, false);
     const int i_bc = st.in(bc, sizeof(double) * n * 2 * (r - 1) * 3);
     const int i_out = st.out(coeff_out, sizeof(double) * 3 * 2 * r * tot, true);
     const int i_st = st.out(status_out, sizeof(int32_t) * n);
     const int i_obj = st.out(objective_out, sizeof(double) * 2 * n), i_acc = st.out(accepted_out, sizeof(int32_t) * n);
-    const int i_pk = limits && peak_out ? st.out(peak_out, sizeof(double) * 2 * n) : -1;
+    const int i_pk = peak_out ? st.out(peak_out, sizeof(double) * 2 * n) : -1;
+    const int i_md = min_dist_out ? st.out(min_dist_out, sizeof(double) * n) : -1;
+    const int i_o = outside_out ? st.out(outside_out, sizeof(int32_t) * n) : -1;
+    const int i_x = extra_out ? st.out(extra_out, sizeof(double) * extra_per_traj * n) : -1;
     rc = stage_begin(ctx, st);
     if (rc != UAVQP_OK) return rc;
-    rc = time_optimize_run(ctx, r, n_traj, uniform_segments, sh.Mmax, (int)sh.total_seg, st.at<int32_t>(i_off), st.at<double>(i_wp),
-                           st.at<double>(i_t), st.at<double>(i_bc), params, st.at<double>(i_out), st.at<int32_t>(i_st), st.at<double>(i_obj),
-                           st.at<int32_t>(i_acc), limits, st.at<double>(i_pk));
+    rc = device(DescentStaged{sh.Mmax, (int)sh.total_seg, st.at<int32_t>(i_off), st.at<double>(i_wp), st.at<double>(i_t), st.at<double>(i_bc),
+                              st.at<double>(i_out), st.at<int32_t>(i_st), st.at<double>(i_obj), st.at<int32_t>(i_acc), st.at<double>(i_pk),
+                              st.at<double>(i_md), st.at<int32_t>(i_o), st.at<double>(i_x)});
     if (rc != UAVQP_OK) return rc;
     return stage_end(ctx, st, who);
+}
+
+static int time_optimize_run_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                                  const double* waypoints, double* times, const double* bc, const uavqp_time_opt_params* params,
+                                  double* coeff_out, int32_t* status_out, double* objective_out, int32_t* accepted_out,
+                                  const uavqp_limit_params* limits, double* peak_out, const char* who) {
+    return descent_run_host(
+        ctx, r, n_traj, uniform_segments, max_segments, seg_offsets, waypoints, nullptr, times, times, bc, [&] { return topt_params_valid(params); },
+        coeff_out, status_out, objective_out, accepted_out, limits ? peak_out : nullptr, nullptr, nullptr, nullptr, 0, who,
+        [&](const DescentStaged& d) {
+            return time_optimize_run(ctx, r, n_traj, uniform_segments, d.Mmax, d.total_segments, d.seg_offsets, d.waypoints, d.times, d.bc, params,
+                                     d.coeff, d.status, d.objective, d.accepted, limits, d.peak);
+        });
 }
 
 extern "C" int uavqp_time_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
