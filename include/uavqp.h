@@ -945,8 +945,9 @@ int uavqp_attitude_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_
  * WHAT THE RESULT IS: a certificate, not an estimate.  After an optimiser with soft penalties this is the acceptance test: a certified
  * bit needs no sampling density to be trusted.  An undecided test is decided by a larger depth (the outer gap falls about four-fold per
  * level) or is genuinely on the limit.
- * Out of scope: body-rate and clearance certificates (rational / not polynomial in t); pruned or adaptive subdivision; wiring the verdict
- * into uavqp_corridor_pipeline_*.
+ * Out of scope of THIS entry: body-rate and clearance certificates (rational / not polynomial in t) -- clearance against the distance
+ * field has its own entry, uavqp_clearance_certificate_* below; pruned or adaptive subdivision; wiring the verdict into
+ * uavqp_corridor_pipeline_*.
  * UAVQP_ERR_INVALID_ARG: r not 3 / 4, a negative count, a wrong struct_size, depth outside 0..8, a limit that is negative or not finite,
  * f_max < f_min when both are set, tilt_max not 0 and outside (0, pi/2), NULL times / coeff, ragged without offsets, one box pointer
  * without the other. */
@@ -973,6 +974,62 @@ int uavqp_envelope_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segment
 int uavqp_envelope_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
                         const double* coeff, const int32_t* status, const uavqp_envelope_params* params, const double* box_lo,
                         const double* box_hi, double* range, double* norm, double* peak, int32_t* seg_verdict, int32_t* verdict);
+
+/* Certified continuous-time clearance of solved trajectories against the distance field (no reference counterpart).  The clearance
+ * penalty's min_dist, uavqp_ellipsoid_check_* and the pipeline's grid check SAMPLE: a thin pillar between two samples passes them.  This
+ * BOUNDS min_t dist(p(t), O) per segment from both sides: `lower` holds for EVERY t in [0, T_i], `upper` is taken at a known t.
+ * Obstacle set O: the union of the closed cubes of the occupied voxels of `esdf`, plus everything outside the map (unknown space counts
+ * as occupied).  res the voxel edge, c_v = origin + (v + 0.5) res, s_v = res sqrt(sq_pos[v]) with sq_pos the exact integer squared voxel
+ * distance to the nearest occupied voxel that uavqp_esdf_update_device keeps (+inf where it is INT32_MAX).  For a point p and its voxel v
+ * (floor((p - origin) / res), clamped into the grid):
+ *   dist(p, occupied cubes) >= s_v - (sqrt(3)/2) res - |p - c_v|       (every occupied centre is at least s_v from c_v, every point of an
+ *                                                                       occupied cube within (sqrt(3)/2) res of its centre)
+ *   dist(p, occupied cubes) <= s_v + |p - c_v| - res/2, 0 if sq_pos[v] = 0   (the nearest occupied cube holds the ball of radius res/2)
+ * Method: the D = 0 Bernstein coefficients of uavqp_envelope_* and `depth` levels of midpoint subdivision give 2^depth leaves; the curve
+ * over a leaf stays in the box of the leaf's coefficients widened per axis by the envelope's guard G_x = 16 (n + 1) 2^-53 S_x.  With m the
+ * centre of that box, h its half diagonal and v the voxel of m,
+ *   L_leaf = min( s_v - (sqrt(3)/2) res - |m - c_v| - h, distance from the box to the nearest face of the map ) - R
+ * (the face distance is negative when the box crosses a face: a box that leaves the map cannot be certified).  Witness points are the
+ * leaf end coefficients, the curve at t = l T_i / 2^depth, l = 0..2^depth:  U_l = [upper bound above] + sqrt(3) max_x G_x + R, and
+ * U_l = sqrt(3) max_x G_x + R for a witness outside the map or in an occupied voxel.  R = 64 2^-53 (max_x S_x + A), A the largest
+ * |coordinate| of the map plus its diagonal, is the rounding allowance of the field arithmetic.
+ *   lower = max(0, min over leaves of L_leaf),  upper = min_l U_l;  the true min_t dist(p(t), O) lies in [lower, upper].
+ * Outputs (each may be NULL; all NULL: UAVQP_OK, nothing done):
+ *   d_clear        [sum_b M_b][2]: lower, upper
+ *   d_witness      [sum_b M_b]: the l of the smallest U_l (a tie: the smallest l); the witness is at t = l T_i / 2^depth
+ *   d_peak         [n_traj][2]: min of lower and min of upper over the segments of the trajectory
+ *   d_seg_verdict  [sum_b M_b] and d_verdict [n_traj]: UAVQP_CLEARANCE_CERTIFIED (lower >= d_req: holds for ALL t),
+ *                  UAVQP_CLEARANCE_VIOLATED (upper < d_req: broken at the witness), UAVQP_CLEARANCE_OUTSIDE (some witness point lies
+ *                  outside the map); neither of the first two: undecided.  The trajectory's word is the AND of the certified bits and the
+ *                  OR of the other two over its segments.
+ * d_status as for uavqp_envelope_device: a trajectory that is not UAVQP_SOLVED, or with M < 1, gets zeros everywhere.  Non-finite
+ * coefficients give NaN bounds, witness 0 and no bit.  Every output element is written exactly once, zeros included; min is exact and a
+ * tie has a rule, so the bytes are the same for any grid.  One launch, asynchronous on the ctx stream, no allocation, no workspace, no
+ * read-back; each leaf costs one gathered int32 load, each witness one more.
+ * WHAT THE RESULT IS: a certificate against the VOXEL map, as conservative as the map is.  The field alone leaves an undecided band of
+ * about 2 res + 2 h between lower and upper; a larger depth shrinks h, not the 2 res.
+ * Out of scope: a tighter bound from a scan of the voxel's neighbourhood; adaptive subdivision; a body-rate certificate; wiring the
+ * verdict into uavqp_corridor_pipeline_*.
+ * UAVQP_ERR_INVALID_ARG: r not 3 / 4, a negative count, a wrong struct_size, depth outside 0..8, d_req not finite or <= 0, esdf NULL, of
+ * another device or never updated, NULL times / coeff, ragged without offsets. */
+#define UAVQP_CLEARANCE_CERTIFIED 1   /* lower >= d_req: holds for ALL t */
+#define UAVQP_CLEARANCE_VIOLATED 2    /* upper <  d_req: broken at the witness */
+#define UAVQP_CLEARANCE_OUTSIDE 4     /* some witness point lies outside the map */
+typedef struct uavqp_clearance_cert_params {
+    int32_t struct_size;
+    int32_t depth;       /* subdivision levels, 0..8 (default 4): 2^depth leaves per segment */
+    double d_req;        /* required clearance, m, finite, > 0 (default 0.5) */
+} uavqp_clearance_cert_params;
+void uavqp_default_clearance_cert_params(uavqp_clearance_cert_params* out);   /* callable without a device */
+int uavqp_clearance_certificate_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
+                                       const double* d_times, const double* d_coeff, const int32_t* d_status, const uavqp_esdf* esdf,
+                                       const uavqp_clearance_cert_params* params, double* d_clear, int32_t* d_witness, double* d_peak,
+                                       int32_t* d_seg_verdict, int32_t* d_verdict);
+/* The same from HOST pointers (H2D copy, run, D2H copy, synchronous); the map stays a device object. */
+int uavqp_clearance_certificate_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
+                                     const double* coeff, const int32_t* status, const uavqp_esdf* esdf,
+                                     const uavqp_clearance_cert_params* params, double* clear, int32_t* witness, double* peak,
+                                     int32_t* seg_verdict, int32_t* verdict);
 
 /* Swarm separation penalty: reciprocal avoidance between the vehicles of one swarm, compared at the same instant on a clock the swarm
  * shares, with its gradients in the coefficients, the durations and the departure times (no reference counterpart: its multi_agents.launch

@@ -89,6 +89,9 @@ SYMBOLS = (
     "uavqp_default_envelope_params",
     "uavqp_envelope_device",
     "uavqp_envelope_host",
+    "uavqp_default_clearance_cert_params",
+    "uavqp_clearance_certificate_device",
+    "uavqp_clearance_certificate_host",
     "uavqp_default_swarm_params",
     "uavqp_swarm_penalty_device",
     "uavqp_swarm_penalty_host",
@@ -208,6 +211,17 @@ class EnvelopeParams(ctypes.Structure):
 
 # the tests of uavqp_envelope_*: bit 2k of a verdict word = certified, bit 2k + 1 = violated (UAVQP_ENVELOPE_* of include/uavqp.h)
 ENVELOPE_TESTS = ("v_max", "a_max", "j_max", "f_min", "f_max", "tilt_max", "box")
+
+
+class ClearanceCertParams(ctypes.Structure):
+    """uavqp_clearance_cert_params of include/uavqp.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("depth", ctypes.c_int32), ("d_req", ctypes.c_double)]
+
+
+# the bits of a uavqp_clearance_certificate_* verdict word (UAVQP_CLEARANCE_* of include/uavqp.h)
+UAVQP_CLEARANCE_CERTIFIED = 1
+UAVQP_CLEARANCE_VIOLATED = 2
+UAVQP_CLEARANCE_OUTSIDE = 4
 
 
 class SwarmParams(ctypes.Structure):
@@ -340,6 +354,10 @@ def lib():
     L.uavqp_default_envelope_params.restype = None
     L.uavqp_envelope_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, ctypes.POINTER(EnvelopeParams), dp, dp, dp, dp, dp, ip, ip]
     L.uavqp_envelope_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, ctypes.POINTER(EnvelopeParams), dp, dp, dp, dp, dp, ip, ip]
+    L.uavqp_default_clearance_cert_params.argtypes = [ctypes.POINTER(ClearanceCertParams)]
+    L.uavqp_default_clearance_cert_params.restype = None
+    L.uavqp_clearance_certificate_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, vp, ctypes.POINTER(ClearanceCertParams), dp, ip, dp, ip, ip]
+    L.uavqp_clearance_certificate_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, vp, ctypes.POINTER(ClearanceCertParams), dp, ip, dp, ip, ip]
     L.uavqp_attitude_optimize_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(LimitParams),
                                                  ctypes.POINTER(ClearanceParams), ctypes.POINTER(AttitudeParams),
                                                  ctypes.POINTER(SpacetimeLbfgsParams), dp, ip, dp, ip, dp, dp, ip, dp]

@@ -425,6 +425,36 @@ class TrajOptimizer {
     const std::vector<double>& envelopeNorm() const { return envelope_norm_; }
     const std::vector<double>& envelopePeak() const { return envelope_peak_; }
     const std::vector<int32_t>& envelopeSegVerdict() const { return envelope_seg_verdict_; }
+    // Certified clearance of the stored coefficients at the stored durations against a distance field over WHOLE segments (after solve()
+    // or an optimiser; uavqp_clearance_certificate_host).  map: a uavqp::EsdfMap of cpp/esdf_map.h built on context() and updated.
+    // Returns the verdict word per trajectory (UAVQP_CLEARANCE_CERTIFIED: at least d_req for ALL t, UAVQP_CLEARANCE_VIOLATED: less at
+    // the witness, UAVQP_CLEARANCE_OUTSIDE: a witness point left the map; include/uavqp.h) and fills clearanceBounds() [sum M][2]
+    // (lower, upper), clearanceWitness() [sum M], clearancePeak() [n_traj][2], clearanceSegVerdict() [sum M].  A trajectory that did not
+    // solve carries zeros.  Empty on failure.
+    template <class Map>
+    std::vector<int32_t> getClearanceCertificate(const Map& map, const uavqp_clearance_cert_params& params) {
+        std::vector<int32_t> verdict;
+        if (n_traj_ <= 0 || !ctx_ || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_]) ||
+            coef_.size() != static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_] || status_.size() != static_cast<size_t>(n_traj_))
+            return verdict;
+        const size_t tot = static_cast<size_t>(seg_offsets_[n_traj_]);
+        verdict.assign(n_traj_, 0);
+        clearance_bounds_.assign(2 * tot, 0.0);
+        clearance_witness_.assign(tot, 0);
+        clearance_peak_.assign(static_cast<size_t>(2) * n_traj_, 0.0);
+        clearance_seg_verdict_.assign(tot, 0);
+        if (uavqp_clearance_certificate_host(ctx_, order_, n_traj_, 0, seg_offsets_.data(), T_.data(), coef_.data(), status_.data(), map.handle(),
+                                             &params, clearance_bounds_.data(), clearance_witness_.data(), clearance_peak_.data(),
+                                             clearance_seg_verdict_.data(), verdict.data()) != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            verdict.clear();
+        }
+        return verdict;
+    }
+    const std::vector<double>& clearanceBounds() const { return clearance_bounds_; }
+    const std::vector<int32_t>& clearanceWitness() const { return clearance_witness_; }
+    const std::vector<double>& clearancePeak() const { return clearance_peak_; }
+    const std::vector<int32_t>& clearanceSegVerdict() const { return clearance_seg_verdict_; }
     // optimizeTrajectory for the swarms set with setSwarm (include/uavqp.h uavqp_swarm_optimize_host; the reference's equality rows only:
     // false when a corridor or rows are set): the separation penalty `swarm` between the vehicles of each swarm joins the objective and
     // every trial is accepted or rejected per SWARM.  With params->start_window > 0 the departures of setSwarm are optimised too and the
@@ -728,7 +758,8 @@ class TrajOptimizer {
     std::vector<int32_t> row_deriv_, first_hit_, repair_deriv_;
     std::vector<double> repair_tau_, repair_lo_, repair_hi_;
     std::vector<double> objective_, peak_, min_dist_, min_sep_, attitude_peak_, envelope_range_, envelope_norm_, envelope_peak_;
-    std::vector<int32_t> envelope_seg_verdict_;
+    std::vector<int32_t> envelope_seg_verdict_, clearance_witness_, clearance_seg_verdict_;
+    std::vector<double> clearance_bounds_, clearance_peak_;
     std::vector<int32_t> outside_;
     std::vector<int32_t> accepted_;
     std::vector<int32_t> groups_;   // setSwarm: empty = the whole batch is one swarm

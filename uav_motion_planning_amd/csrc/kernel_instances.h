@@ -176,3 +176,7 @@ static inline bool uavqp_twisted_group_exists(int r, int M, int tile) {
 // ---- qp_envelope.h: certified bounds of position, velocity, acceleration, jerk, thrust and tilt over whole segments
 #define UAVQP_ENVELOPE_R(R_) UAVQP_INST __global__ void uavqp::envelope_kernel<R_>(uavqp::EnvelopeArgs);
 #define UAVQP_INSTANCES_ENVELOPE UAVQP_ENVELOPE_R(3) UAVQP_ENVELOPE_R(4)
+
+// ---- qp_clearance_cert.h: certified clearance of whole segments against the distance field's integer squared distances
+#define UAVQP_CLEARANCE_CERT_R(R_) UAVQP_INST __global__ void uavqp::clearance_cert_kernel<R_>(uavqp::ClearanceCertArgs);
+#define UAVQP_INSTANCES_CLEARANCE_CERT UAVQP_CLEARANCE_CERT_R(3) UAVQP_CLEARANCE_CERT_R(4)

@@ -29,8 +29,9 @@
 // coefficients would put them in scratch); which half is a branch, uniform over the wave below the third level.
 // One launch, no scratch memory, no workspace; every output element is written exactly once (zeros included).
 //
-// Out of scope: body-rate and clearance certificates (rational / not polynomial in t), pruned or adaptive subdivision, and wiring the
-// verdict into uavqp_corridor_pipeline_*.  Registers: DESIGN.md section 5.25.
+// Out of scope of this kernel: body-rate and clearance certificates (rational / not polynomial in t) -- clearance against the distance
+// field is certified by qp_clearance_cert.h on this kernel's leaves --, pruned or adaptive subdivision, and wiring the verdict into
+// uavqp_corridor_pipeline_*.  Registers: DESIGN.md section 5.25.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -42,6 +42,7 @@
 #include "qp_swarm_opt.h"
 #include "qp_attitude.h"
 #include "qp_envelope.h"
+#include "qp_clearance_cert.h"
 // Measured-slower alternatives kept as bit-identical cross-checks: `make experiments` (-DUAVQP_EXPERIMENTS) only
 #ifdef UAVQP_EXPERIMENTS
 #include "cloud_grid2d.h"
@@ -79,6 +80,7 @@ UAVQP_INSTANCES_SWARM
 UAVQP_INSTANCES_SWARM_OPT
 UAVQP_INSTANCES_ATTITUDE
 UAVQP_INSTANCES_ENVELOPE
+UAVQP_INSTANCES_CLEARANCE_CERT
 #endif
 
 namespace uavqp {
@@ -235,6 +237,8 @@ struct uavqp_ctx {
     DevBuf rows_warm2;        // rows part of the starting set of the general-rows solve + the "box phase needed" flags (qp_rows_dual.h)
     void* dbg_queue = nullptr;  // (debug builds) where the last corridor solve kept its work counter
     int dual_trips_extra = 0;   // added to the trip budget 4 n + 16 of the dual preludes (UAVQP_DUAL_TRIPS_EXTRA, may be negative: tools/ experiments)
+    int clearance_cert_blocks = 0;   // cap on the blocks of the clearance certificate's launch (UAVQP_CLEARANCE_CERT_BLOCKS; 0: topt_grid's cap
+                                     // alone): the tests set it to run the grid-stride loop on a small batch
     int wave_prelude = 2;       // re-solves with G in the cache: 2 = corridor_dual_wave2_kernel (two trajectories per wave), 1 = corridor_dual_wave_kernel (one),
                                 // 0 = the batch kernels (UAVQP_WAVE_PRELUDE=0|1|2, UAVQP_NO_WAVE_PRELUDE: A/B runs)
     void* dbg_dual = nullptr;   // (UAVQP_DUAL_DEBUG builds) dump area of corridor_dual_kernel
@@ -412,6 +416,7 @@ extern "C" int uavqp_create(uavqp_ctx** out_ctx, int device) {
     if (std::getenv("UAVQP_NO_WAVE_PRELUDE")) ctx->wave_prelude = 0;
     if (const char* e = std::getenv("UAVQP_DEAL_TICKETS")) ctx->deal_tickets = std::atoi(e) != 0;
     if (const char* e = std::getenv("UAVQP_DUAL_TRIPS_EXTRA")) ctx->dual_trips_extra = std::atoi(e);
+    if (const char* e = std::getenv("UAVQP_CLEARANCE_CERT_BLOCKS")) { const int v = std::atoi(e); if (v > 0) ctx->clearance_cert_blocks = v; }
     if (const char* e = std::getenv("UAVQP_WAVE_PRELUDE")) { const int v = std::atoi(e); if (v >= 0 && v <= 2) ctx->wave_prelude = v; }
     if (const char* e = std::getenv("UAVQP_GENERIC_NAX")) ctx->settings.generic_lanes_per_traj = std::atoi(e) == 3 ? 1 : 3;
     if (const char* e = std::getenv("UAVQP_GENERIC_WPC")) {
@@ -1992,6 +1997,11 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
 // Signed distance field of an occupancy grid and the clearance penalty
 // ===================================================================================================
 #include "uavqp_esdf.h"
+
+// ===================================================================================================
+// Certified continuous-time clearance of solved trajectories against the distance field (needs the map of uavqp_esdf.h)
+// ===================================================================================================
+#include "uavqp_clearance_cert.h"
 
 // ===================================================================================================
 // Waypoint gradient of the control cost and the waypoint optimiser against the distance field

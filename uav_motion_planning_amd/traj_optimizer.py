@@ -646,6 +646,49 @@ class Context:
         _lib.check(rc, "uavqp_envelope_host")
         return rng, norm, peak, seg_verdict, verdict
 
+    @staticmethod
+    def _clearance_cert_params(params):
+        cp = _lib.ClearanceCertParams()
+        _lib.lib().uavqp_default_clearance_cert_params(ctypes.byref(cp))
+        for k, v in params.items():
+            if not hasattr(cp, k) or k == "struct_size":
+                raise ValueError(f"unknown uavqp_clearance_cert_params field {k!r}")
+            setattr(cp, k, v)
+        return cp
+
+    def clearance_certificate_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, esdf, status=None, clear_out=None,
+                                     witness_out=None, peak_out=None, seg_verdict_out=None, verdict_out=None, **params):
+        """uavqp_clearance_certificate_device on device buffers: certified clearance of solved trajectories against the distance field
+        `esdf` (an EsdfMap, updated) over whole segments.  clear_out [sum M][2] (lower: holds for ALL t; upper: taken at the witness),
+        witness_out [sum M] (int32 l: the witness is at t = l T_i / 2^depth), peak_out [n_traj][2] (the smallest lower / upper of the
+        trajectory), seg_verdict_out [sum M] and verdict_out [n_traj] (int32: _lib.UAVQP_CLEARANCE_CERTIFIED / _VIOLATED / _OUTSIDE); each
+        may be None.  params: depth (0..8, default 4), d_req (m, default 0.5).  Asynchronous."""
+        cp = self._clearance_cert_params(params)
+        rc = _lib.lib().uavqp_clearance_certificate_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff),
+                                                           _ptr(status), getattr(esdf, "handle", esdf), ctypes.byref(cp), _ptr(clear_out),
+                                                           _ptr(witness_out), _ptr(peak_out), _ptr(seg_verdict_out), _ptr(verdict_out))
+        _lib.check(rc, "uavqp_clearance_certificate_device")
+
+    def clearance_certificate(self, r, seg_offsets, times, coeff, esdf, uniform_segments=0, status=None, **params):
+        """uavqp_clearance_certificate_host: numpy in / numpy out (synchronous; the map stays on the device).  Returns (clear [sum M][2],
+        witness [sum M], peak [n_traj][2], seg_verdict [sum M], verdict [n_traj]); see clearance_certificate_device."""
+        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
+        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total and coeff.size == 3 * 2 * r * total
+        cp = self._clearance_cert_params(params)
+        clear = np.zeros((total, 2), dtype=np.float64)
+        witness = np.zeros(total, dtype=np.int32)
+        peak = np.zeros((n_traj, 2), dtype=np.float64)
+        seg_verdict = np.zeros(total, dtype=np.int32)
+        verdict = np.zeros(n_traj, dtype=np.int32)
+        rc = _lib.lib().uavqp_clearance_certificate_host(self._h, r, n_traj, uniform_segments, _ptr(so), _ptr(times), _ptr(coeff), _ptr(status),
+                                                         getattr(esdf, "handle", esdf), ctypes.byref(cp), _ptr(clear), _ptr(witness), _ptr(peak),
+                                                         _ptr(seg_verdict), _ptr(verdict))
+        _lib.check(rc, "uavqp_clearance_certificate_host")
+        return clear, witness, peak, seg_verdict, verdict
+
     def attitude_optimize_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc, esdf,
                                  coeff_out, status_out, objective_out, accepted_out=None, peak_out=None, min_dist_out=None, outside_out=None,
                                  attitude_peak_out=None, limits=None, clearance=None, attitude=None, **params):
@@ -1297,6 +1340,19 @@ class TrajOptimizer:
             out["certified"][name], out["violated"][name] = c, v
             out["undecided"][name] = ~c & ~v & solved if on[name] else np.zeros_like(c)
         return out
+
+    def getClearanceCertificate(self, esdf, depth=4, d_req=0.5):
+        """Certified clearance of the stored coefficients at the stored durations against the distance field `esdf` over WHOLE segments
+        (uavqp_clearance_certificate_host; after solve() or an optimiser): what no sampled check gives.  Returns a dict: clear [sum M][2]
+        (lower, upper), witness [sum M], peak [n_traj][2], seg_verdict, verdict (the int32 words) and, per trajectory, the boolean masks
+        certified (>= d_req for ALL t), violated (< d_req at the witness), undecided and outside (a witness point left the map)."""
+        if self._ctx is None or self._coef.size != 3 * 2 * self._r * int(self._so[-1]) or self.status.size != self._so.size - 1:
+            raise _lib.UavqpError("getClearanceCertificate: no solved coefficients (call solve() or an optimiser first)")
+        clear, witness, peak, seg_verdict, verdict = self._ctx.clearance_certificate(self._r, self._so, self._T, self._coef, esdf,
+                                                                                     status=self.status, depth=depth, d_req=d_req)
+        c, v = verdict & _lib.UAVQP_CLEARANCE_CERTIFIED != 0, verdict & _lib.UAVQP_CLEARANCE_VIOLATED != 0
+        return dict(clear=clear, witness=witness, peak=peak, seg_verdict=seg_verdict, verdict=verdict, certified=c, violated=v,
+                    undecided=~c & ~v & (self.status == _lib.UAVQP_SOLVED), outside=verdict & _lib.UAVQP_CLEARANCE_OUTSIDE != 0)
 
     def getFlightPenalty(self, esdf, limits=None, clearance=None):
         """[n_traj] limit penalty + clearance penalty of the stored coefficients at the stored durations against `esdf`, in one launch
