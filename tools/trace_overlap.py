@@ -3,8 +3,8 @@
 Reads a `rocprofv3 --kernel-trace --output-format csv` trace and reports, for the dispatches that carry the last N solves of the kernels
 that match (the timed block of a bench.py run: everything before it is warm-up and the first replay), how far they overlap: the span from
 the first start to the last end, per dispatch and per solve, the mean kernel duration, and how many kernels started before the kernel
-dispatched in front of them had ended.  A launch of solve_twisted_group_kernel (a replay with UAVQP_CAPTURE_FUSE > 1: csrc/uavqp_capture.h)
-carries one solve per row of its grid (Grid_Size_Y); every other dispatch is one solve."""
+dispatched in front of them had ended.  A launch of solve_twisted_group_kernel or solve_twisted_group8_kernel (a replay with
+UAVQP_CAPTURE_FUSE > 1: csrc/uavqp_capture.h) carries one solve per row of its grid (Grid_Size_Y); every other dispatch is one solve."""
 import argparse
 import csv
 import re
@@ -13,13 +13,13 @@ import re
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("trace")
-    ap.add_argument("--kernel", default="solve_twisted(_group)?_kernel")
+    ap.add_argument("--kernel", default="solve_twisted(_group8?)?_kernel")
     ap.add_argument("--last", type=int, default=40, help="solves (not dispatches) to look at, counted from the end of the trace")
     a = ap.parse_args()
     rows = []
     for r in csv.DictReader(open(a.trace)):
         if re.search(a.kernel, r["Kernel_Name"]):
-            solves = max(1, int(r.get("Grid_Size_Y") or 1) // max(1, int(r.get("Workgroup_Size_Y") or 1))) if "_group_kernel" in r["Kernel_Name"] else 1
+            solves = max(1, int(r.get("Grid_Size_Y") or 1) // max(1, int(r.get("Workgroup_Size_Y") or 1))) if re.search("_group8?_kernel", r["Kernel_Name"]) else 1
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), solves))
     rows.sort()
     kept, solves = [], 0

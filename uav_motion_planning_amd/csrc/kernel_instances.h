@@ -46,6 +46,20 @@
 #define UAVQP_TWISTED_GROUP_T8(R_, M_) UAVQP_INST __global__ void uavqp::solve_twisted_group_kernel<R_, M_, 8, 8>(UAVQP_TWISTED_GROUP_SIG);
 #define UAVQP_INSTANCES_TWISTED3_GROUP UAVQP_GROUP_PAIRS3_T4(UAVQP_TWISTED_GROUP_T4) UAVQP_GROUP_PAIRS3_T8(UAVQP_TWISTED_GROUP_T8)
 #define UAVQP_INSTANCES_TWISTED4_GROUP UAVQP_GROUP_PAIRS4_T4(UAVQP_TWISTED_GROUP_T4) UAVQP_GROUP_PAIRS4_T8(UAVQP_TWISTED_GROUP_T8)
+// and the group of tile-4 solves with eight trajectories per wave (solve_twisted_group8_kernel; k_twisted3_group8.hip / k_twisted4_group8.hip):
+// every shape of the tile-4 group lists -- all of them compile without scratch and fit two waves to a SIMD (at most 256 VGPRs;
+// tests/test_twisted_group8_resources.py reads the counts from a cross-compile, docs/measurement_log.md tables them).
+#define UAVQP_GROUP8_PAIRS4(X) UAVQP_GROUP_PAIRS4_T4(X)
+#define UAVQP_GROUP8_PAIRS3(X) UAVQP_GROUP_PAIRS3_T4(X)
+#define UAVQP_TWISTED_GROUP8(R_, M_) UAVQP_INST __global__ void uavqp::solve_twisted_group8_kernel<R_, M_>(UAVQP_TWISTED_GROUP8_SIG);
+#define UAVQP_INSTANCES_TWISTED3_GROUP8 UAVQP_GROUP8_PAIRS3(UAVQP_TWISTED_GROUP8)
+#define UAVQP_INSTANCES_TWISTED4_GROUP8 UAVQP_GROUP8_PAIRS4(UAVQP_TWISTED_GROUP8)
+static inline bool uavqp_twisted_group8_exists(int r, int M) {
+#define UAVQP_GROUP_HAS(R_, M_) if (r == R_ && M == M_) return true;
+    UAVQP_GROUP8_PAIRS4(UAVQP_GROUP_HAS) UAVQP_GROUP8_PAIRS3(UAVQP_GROUP_HAS)
+#undef UAVQP_GROUP_HAS
+    return false;
+}
 // the same lists for host code without the HIP runtime (tests): is there a group kernel for (r, M) at this tile?
 static inline bool uavqp_twisted_group_exists(int r, int M, int tile) {
 #define UAVQP_GROUP_HAS(R_, M_) if (r == R_ && M == M_) return true;

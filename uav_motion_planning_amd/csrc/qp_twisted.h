@@ -19,6 +19,7 @@
 
 #include "qp_core_kernels.h"
 #include "qp_twisted_map.h"
+#include "qp_twisted_map8.h"
 #include "qp_wave_utils.h"
 
 #ifndef UAVQP_STAMP   // (probe builds under tools/ubench define their own: per-wave timelines)
@@ -63,6 +64,10 @@ struct TwistedCfg {
     static constexpr int ROWS8 = LPT >= 8 ? TILE * 6 * (LPT / 8) : 0, RS8 = 10;
     static_assert(LPT < 8 || ROWS8 == 48, "the copy-out maps 3 axes x 16 rows");
     static constexpr int OUT_D = LPT >= 8 ? (ROWS8 + 16) * RS8 + 16 : ((LPT == 2 && !ALIAS) ? STAGE_D : 2);
+    // solve_twisted_group8_kernel (eight trajectories per wave, both segments of a step per lane pair): six blocks of 16 rows and 16 rows
+    // behind them for the writes of the idle pairs, laid out by qp_twisted_map8.h.
+    static constexpr int OUT2_D = TWMAP8_STAGE_DOUBLES;
+    static_assert(RS8 == TWMAP8_ROW_STRIDE, "one row stride for the latency shapes");
     static_assert(!ALIAS || STAGE_D <= IN_D, "aliased staging rows must fit the input buffer");
     static_assert(WP_D % 2 == 0 && T_D % 2 == 0 && BC_D % 2 == 0, "tile arrays must be whole 16-B pairs");
 };
@@ -104,6 +109,7 @@ template <int R, int M, int TILE, int LPT = 2, bool ONE = false>
 __global__ __launch_bounds__(64, 1) void solve_twisted_kernel(const double* waypoints, const double* times, const double* bc, double* coeff,
                                                               int32_t* status, int n_traj UAVQP_TWISTED_STAMPS_PARAM) {
     const TwistedArgs a{waypoints, times, bc, coeff, status, n_traj UAVQP_TWISTED_STAMPS_INIT};
+    constexpr bool EMIT2 = false;
 #include "qp_twisted_body.h"
 }
 
@@ -130,6 +136,29 @@ template <int R, int M, int TILE, int LPT>
 __global__ __launch_bounds__(64, 1) void solve_twisted_group_kernel(const TwistedGroupArgs group) {
     static_assert(LPT >= 8, "groups are built from launches of one whole tile per wave: latency shapes only");
     constexpr bool ONE = true;
+    const TwistedGroupSet& mine = group.set[blockIdx.y];
+#ifdef UAVQP_PHASE_TIMING
+    const TwistedArgs a{mine.waypoints, mine.times, mine.bc, mine.coeff, mine.status, 0, nullptr};
+#else
+    const TwistedArgs a{mine.waypoints, mine.times, mine.bc, mine.coeff, mine.status, 0};
+#endif
+    constexpr bool EMIT2 = false;
+#include "qp_twisted_body.h"
+}
+
+// The group of 16-lane solves once more, with EIGHT trajectories per wave: what uavqp_capture_end puts into a group of two or more tile-4
+// launches whose batch is a whole number of eights (uavqp_capture.h: group_kernel_choice).  The 16-lane shape gives every (trajectory,
+// axis, side) two lane pairs that both run elimination, meeting knot and back-substitution and split only the emission: latency for an
+// isolated launch, where a SIMD holds one wave -- and pure cost in a fused replay, whose SIMDs are full.  Here a wave is laid out as the
+// 8-lane shape (one pair per (trajectory, axis)), runs those statements once, and then emits BOTH segments of every step with the 16-lane
+// shape's arithmetic (qp_twisted_body.h, EMIT2: segment_coeffs on the reloaded duration, not the 8-lane shape's kept inverse powers):
+// per (trajectory, axis, side, segment) the operations of solve_twisted_kernel<R, M, 4, 16, true>, so a replay stays bitwise equal to
+// eager order.  Grid (n_traj / 8, members), block 64; the copy-out map is qp_twisted_map8.h.
+#define UAVQP_TWISTED_GROUP8_SIG const uavqp::TwistedGroupArgs
+template <int R, int M>
+__global__ __launch_bounds__(64, 1) void solve_twisted_group8_kernel(const TwistedGroupArgs group) {
+    constexpr int TILE = TWMAP8_TILE, LPT = 8;
+    constexpr bool ONE = true, EMIT2 = true;
     const TwistedGroupSet& mine = group.set[blockIdx.y];
 #ifdef UAVQP_PHASE_TIMING
     const TwistedArgs a{mine.waypoints, mine.times, mine.bc, mine.coeff, mine.status, 0, nullptr};

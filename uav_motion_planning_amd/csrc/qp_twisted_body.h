@@ -3,9 +3,11 @@
 // way of getting the arguments, so the two run the same arithmetic by construction -- and solve_twisted_kernel compiles to exactly the
 // instructions it had when the statements stood in it (a shared __device__ function, even one that is always inlined, reaches the
 // optimiser in another order and came out with other schedules and operand orders in most instantiations).
-// The including scope provides: the template parameters R, M, TILE, LPT, a compile-time bool ONE, and `const TwistedArgs a`.
+// The including scope provides: the template parameters R, M, TILE, LPT, the compile-time bools ONE and EMIT2, and `const TwistedArgs a`.
+// EMIT2 (solve_twisted_group8_kernel only: TILE = LPT = 8, ONE): the lane pair emits both segments of a 16-lane step itself.
 // The wave's tiles go by blockIdx.x / gridDim.x alone.  No include guard: included once per kernel.
     using C = TwistedCfg<R, M, TILE, LPT>;
+    static_assert(!EMIT2 || (ONE && LPT == 8 && TILE == TWMAP8_TILE), "both segments of a step per lane pair: eight trajectories per wave, one whole tile");
     constexpr int NAX = C::NAX;
     constexpr int ND = C::ND, NC = C::NC, NK = C::NK, mL = C::mL, mR = C::mR;
     static_assert(M >= 2, "twisted kernel needs an interior knot");
@@ -13,7 +15,7 @@
     static_assert((LPT == 2 && (TILE == 32 || TILE == 16)) || (LPT == 8 && TILE == 8) || (LPT == 16 && TILE == 4), "tile shapes: 2 lanes x 32|16, 8 lanes x 8, 16 lanes x 4");
 
     __shared__ __attribute__((aligned(16))) double s_in[ONE ? 1 : 2][C::IN_D];
-    __shared__ __attribute__((aligned(16))) double s_out[C::OUT_D];
+    __shared__ __attribute__((aligned(16))) double s_out[EMIT2 ? C::OUT2_D : C::OUT_D];
     (void)s_out;
 
     const int lane = threadIdx.x;
@@ -119,12 +121,13 @@
         // (LPT == 2: the own durations stay in registers for the emission -- the duration tile has a row stride of M doubles, a
         // 4-way bank conflict per read for M = 8)
         // (LPT == 8: also their inverse powers T^-R..T^-(2R-1), which SegBlocks::build computes anyway and the emission needs again)
-        constexpr bool KEEP_T = LPT == 2 || LPT == 8;
-        double Town[KEEP_T ? mL : 1], Tip[LPT == 8 ? mL : 1][R];
+        // (EMIT2: neither -- its emission is the 16-lane shape's, which reloads the duration and takes its reciprocal)
+        constexpr bool KEEP_T = (LPT == 2 || LPT == 8) && !EMIT2, KEEP_IP = LPT == 8 && !EMIT2;
+        double Town[KEEP_T ? mL : 1], Tip[KEEP_IP ? mL : 1][R];
 #pragma unroll
         for (int j = 0; j < (KEEP_T ? mL : 1); ++j) Town[j] = 1.0;
 #pragma unroll
-        for (int j = 0; j < (LPT == 8 ? mL : 1); ++j)
+        for (int j = 0; j < (KEEP_IP ? mL : 1); ++j)
 #pragma unroll
             for (int k = 0; k < R; ++k) Tip[j][k] = 1.0;
         SegBlocks<R> sa;
@@ -133,7 +136,7 @@
             Town[0] = t0;
             double ipw[NC];
             sa.build(t0, ipw);
-            if constexpr (LPT == 8) {
+            if constexpr (KEEP_IP) {
 #pragma unroll
                 for (int k = 0; k < R; ++k) Tip[0][k] = ipw[R + k];
             }
@@ -164,7 +167,7 @@
                     if constexpr (KEEP_T) Town[j] = tj;
                     double ipw[NC];
                     sb.build(tj, ipw);
-                    if constexpr (LPT == 8) {
+                    if constexpr (KEEP_IP) {
 #pragma unroll
                         for (int k = 0; k < R; ++k) Tip[j][k] = ipw[R + k];
                     }
@@ -305,6 +308,121 @@
                         }
                 }
             }
+            if constexpr (EMIT2) {
+            // Eight trajectories per wave, one lane pair per (trajectory, axis, side): in step s the pair evaluates BOTH own segments
+            // 2 s and 2 s + 1 -- the NSUB == 2 step below once per `sub`, now a compile-time constant (same candidates, same
+            // segment_coeffs on the reloaded duration and its fast_rcp, same `finite` rule), so every segment gets the operations the
+            // 16-lane shape gives it.  A sub-step in which no lane has a segment (2 s + 1 == mL) is not evaluated at all; one in which
+            // only the reversed lanes have none (odd M) leaves them a chunk that is dropped, as there.  Both chunks go to LDS rows laid
+            // out as TWO 16-lane tiles of four trajectories (qp_twisted_map8.h), and the copy-out of a step is six stores of 16 bytes
+            // per lane, each the 16-lane kernel's store of one axis of four trajectories: the same lines from the same lane groups,
+            // write-through, dropped pieces out of range, interleaved with the next step's arithmetic.
+            constexpr int H = (mL + 1) / 2, RS = C::RS8, NIT = TWMAP8_PIECES;
+            static_assert(twmap8_steps(M) == H, "the map's steps are the kernel's");
+            // (where the rows lie, and why the twelve b128 writes of 16 consecutive lanes start in twelve bank quads: qp_twisted_map8.h)
+            auto row_addr = [&](int blk, int rest) -> int { return twmap8_row_addr(blk, rest); };
+            static_assert(NC <= TWMAP8_ROW_DOUBLES, "a chunk fits its row");
+            const unsigned tile_bytes = (unsigned)TILE * 3u * M * NC * 8u;
+            const unsigned long long obase = (unsigned long long)out;
+            const unsigned ob_lo = __builtin_amdgcn_readfirstlane((unsigned)obase), ob_hi = __builtin_amdgcn_readfirstlane((unsigned)(obase >> 32));
+            const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)ob_hi << 32) | ob_lo), 0,
+                                                                __builtin_amdgcn_readfirstlane(tile_bytes), 0x00020000);
+            typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+            // the piece this lane copies: the same row slot of the six blocks (half x axis).  The decode is written out here from the
+            // map's building blocks (twmap_rest_*, twmap8_block_*, twmap_own_segment, twmap_global_segment) so that everything that does
+            // not depend on the step or the block is computed once in front of the loop; twmap8_piece() is the same composition as ONE
+            // function, and it is that function the CPU test walks -- the kernel's own composition (c_off + (axis * M + segment) * NC * 8,
+            // keep) is covered by the bitwise GPU tests only (tests/test_gpu_twisted_group8.py).  Keep the two in step.
+            const int c_rest = lane >> 2, c_col = lane & 3;
+            const int c_R = twmap_rest_side<2>(c_rest), c_sub = twmap_rest_sub<2>(c_rest), c_tl4 = twmap_rest_traj<2>(c_rest);
+            const int c_m = c_R ? mR : mL;
+            bool c_keep[2];
+            unsigned c_off[2];   // + axis * M * NC * 8 + segment * NC * 8
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                const int c_tl = hf * 4 + c_tl4;
+                c_keep[hf] = (c_col < NC / 2) && ((okmask >> (LPT * c_tl)) & 1ull);
+                c_off[hf] = (unsigned)(((c_tl * 3 * M) * NC + 2 * c_col) * 8);
+            }
+            const int c_lds = c_rest * RS + 2 * c_col;
+            // own rows: one per sub; the idle pairs write behind the blocks
+            int my_lds[2];
+#pragma unroll
+            for (int sb = 0; sb < 2; ++sb)
+                my_lds[sb] = axl < 3 ? row_addr(twmap8_block(tlc, axl), twmap8_rest(tlc, sb, isR))
+                                     : twmap8_idle_addr((lane >> 3) * 2 + isR);
+            auto flush = [&](int sp) {   // copy-out of step sp: NIT LDS reads, NIT stores
+                // (every row is read, also one nobody wrote in this step: where 2 sp + 1 == mL the sub-1 rows hold the previous step's
+                //  chunks -- or, for M = 2, whatever LDS held at wave start.  Those pieces are never stored: jv < c_m below is false for
+                //  them and the store gets the out-of-range offset)
+                double2 v[NIT];
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) v[it] = *reinterpret_cast<const double2*>(s_out + row_addr(it, 0) + c_lds);
+                const int jv = twmap_own_segment<2>(sp, c_sub);               // own segment of the producing lane
+                const int cseg = twmap_global_segment(M, c_R, jv);
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    const int hf = twmap8_block_half(it), cax = twmap8_block_axis(it);
+                    u32x4 w;
+                    w.x = (unsigned)__double2loint(v[it].x); w.y = (unsigned)__double2hiint(v[it].x);
+                    w.z = (unsigned)__double2loint(v[it].y); w.w = (unsigned)__double2hiint(v[it].y);
+                    const unsigned off = (c_keep[hf] && jv < c_m) ? c_off[hf] + (unsigned)((cax * M + cseg) * NC * 8) : 0xFFFFFFF0u;
+                    __builtin_amdgcn_raw_buffer_store_b128(w, rsrc, off, 0, 17 /* sc0 sc1: write-through, nothing left dirty for the kernel boundary */);
+                }
+            };
+#pragma unroll
+            for (int s = 0; s < H; ++s) {
+                if (s > 0) flush(s - 1);
+                double c8[2][NC];
+                auto sub_step = [&](auto sub_c) {
+                    constexpr int sb = decltype(sub_c)::value;
+                    const int j = twmap_own_segment<2>(s, sb);
+                    if (j < mL) {
+                        const bool act = (j < m);
+                        const int jc = act ? j : (m > 0 ? m - 1 : 0);
+                        const double pj = pos(jc, 0), pj1 = pos(jc + 1, 0);
+                        double ys[ND], ye[ND];
+#pragma unroll
+                        for (int d = 0; d < ND; ++d) {
+                            const double fs = ((d & 1) == 0) ? -1.0 : 1.0;
+                            auto Y = [&](int q) -> double { return (q >= mL || q == m) ? ynext[d][0] : h[q < mL ? q : mL - 1][d][0]; };
+                            // pair 1's segment lies behind pair 0's: its start is pair 0's end
+                            const double yj = sb ? Y(2 * s + 1) : h[2 * s][d][0], yj1 = sb ? Y(2 * s + 2) : Y(2 * s + 1);
+                            ys[d] = isR ? fs * yj1 : yj;
+                            ye[d] = isR ? fs * yj : yj1;
+                        }
+                        const double Tj = Tof(jc);
+                        segment_coeffs<R>(isR ? pj1 : pj, ys, isR ? pj : pj1, ye, Tj, fast_rcp(Tj), c8[sb]);
+                        if (act) finite = finite && (fabs(c8[sb][NC - 1]) < INFINITY) && (fabs(c8[sb][R]) < INFINITY);
+                    }
+                };
+                sub_step(std::integral_constant<int, 0>{});
+                sub_step(std::integral_constant<int, 1>{});
+                if (s > 0) {
+                    // the previous step's copy-out between this step's arithmetic: LDS reads first, then one store per ~20 VALU instructions
+                    __builtin_amdgcn_sched_group_barrier(0x100, NIT, 0);
+#pragma unroll
+                    for (int it = 0; it < NIT; ++it) {
+                        __builtin_amdgcn_sched_group_barrier(0x2, 20, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x40, 1, 0);
+                    }
+                }
+#pragma unroll
+                for (int sb = 0; sb < 2; ++sb) {
+                    if (twmap_own_segment<2>(s, sb) < mL) {
+                        // (idle pairs and lanes without a segment in this sub-step write too -- rows / chunks that are never copied out)
+                        double* so = s_out + my_lds[sb];
+#pragma unroll
+                        for (int k = 0; k < NC; k += 2) *reinterpret_cast<double2*>(so + k) = make_double2(c8[sb][k], c8[sb][k + 1]);
+                    }
+                }
+                // single-wave workgroup: LDS operations execute in issue order; this only pins the compiler's order of the accesses
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                if (s == H - 1) flush(s);
+            }
+            } else {
             // LPT == 16: two lane pairs per (trajectory, axis) repeat elimination and back-substitution and split the EMISSION --
             // in step s pair `sub` evaluates the own segment s * NSUB + sub (selects between compile-time candidates, one instruction
             // stream): 4 trajectories per wave, a 4096-trajectory batch fills all 1024 SIMDs.  The two pairs of a side emit ADJACENT
@@ -442,6 +560,7 @@
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 if (s == H - 1) flush(s);
             }
+            }   // !EMIT2
         } else {
             // ---------------- chunk mode (LPT == 2): CH own segments x one axis per emission unit ----------------
             // Every lane writes the 2r*CH coefficients of its chunk, in ORIGINAL segment order, to its own LDS

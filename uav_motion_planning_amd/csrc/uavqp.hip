@@ -60,6 +60,8 @@ UAVQP_INSTANCES_TWISTED3_ONE
 UAVQP_INSTANCES_TWISTED4_ONE
 UAVQP_INSTANCES_TWISTED3_GROUP
 UAVQP_INSTANCES_TWISTED4_GROUP
+UAVQP_INSTANCES_TWISTED3_GROUP8
+UAVQP_INSTANCES_TWISTED4_GROUP8
 UAVQP_INSTANCES_GENERIC
 UAVQP_INSTANCES_CORRIDOR
 UAVQP_INSTANCES_CORRIDOR_DUAL
@@ -138,6 +140,14 @@ static const void* find_twisted_group(int r, int M, int tile) {
     UAVQP_GROUP_PAIRS4_T8(UAVQP_CASE8) UAVQP_GROUP_PAIRS3_T8(UAVQP_CASE8)
 #undef UAVQP_CASE4
 #undef UAVQP_CASE8
+    return nullptr;
+}
+// The kernel that replays a group of tile-4 one-tile-per-wave solves of (r, M) with eight trajectories per wave, or null where the shape
+// has none (kernel_instances.h: UAVQP_GROUP8_PAIRS*).
+static const void* find_twisted_group8(int r, int M) {
+#define UAVQP_CASE(RR, MM) if (r == RR && M == MM) return (const void*)&solve_twisted_group8_kernel<RR, MM>;
+    UAVQP_GROUP8_PAIRS4(UAVQP_CASE) UAVQP_GROUP8_PAIRS3(UAVQP_CASE)
+#undef UAVQP_CASE
     return nullptr;
 }
 }  // namespace uavqp
@@ -222,6 +232,8 @@ struct CapturedLaunch {
     unsigned int lds_bytes = 0;
     BatchArgs args{};  // fn != null: a solve_twisted_kernel launch, re-added through TwistedParams (a barrier launch is re-added with the parameters of its captured node)
     const void* group_fn = nullptr;   // the launch took the one-tile-per-wave instantiation and its shape has a group kernel: that kernel
+    const void* group8_fn = nullptr;  // ... and the eight-trajectories-per-wave kernel of its shape, where it has one (tile 4 only)
+    int tile = 0;                     // trajectories per wave of the launch (fn != null)
 };
 
 struct uavqp_ctx {
@@ -271,7 +283,8 @@ struct uavqp_ctx {
 };
 
 // (capture only) remember a launch just made on the ctx stream; `a` null = a launch that cannot be analysed (a barrier)
-static void capture_note(uavqp_ctx* ctx, const void* fn, dim3 grid, dim3 block, size_t lds_bytes, const BatchArgs* a, int r, const void* group_fn = nullptr) {
+static void capture_note(uavqp_ctx* ctx, const void* fn, dim3 grid, dim3 block, size_t lds_bytes, const BatchArgs* a, int r, const void* group_fn = nullptr,
+                         const void* group8_fn = nullptr, int tile = 0) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusActive) {   // the capture ended behind the library's back
         ctx->capturing = false;
@@ -282,6 +295,8 @@ static void capture_note(uavqp_ctx* ctx, const void* fn, dim3 grid, dim3 block, 
     CapturedLaunch l;
     l.fn = fn; l.grid = grid; l.block = block; l.lds_bytes = (unsigned int)lds_bytes;
     l.group_fn = a ? group_fn : nullptr;
+    l.group8_fn = a && group_fn ? group8_fn : nullptr;
+    l.tile = tile;
     uavqp_capture::Record rec;
     rec.barrier = a == nullptr;
     if (a) {
@@ -534,7 +549,8 @@ extern "C" int uavqp_solve_batch_device(uavqp_ctx* ctx, int r, int n_traj, int u
             uavqp::TwistedParams tp(a);
             UAVQP_HIP(hipLaunchKernel((const void*)fn, dim3(g), dim3(64), tp.ptr, 0, ctx->stream));
             if (ctx->capturing)   // no workspace of the ctx: the one analysable launch
-                capture_note(ctx, (const void*)fn, dim3(g), dim3(64), 0, &a, r, one ? uavqp::find_twisted_group(r, uniform_segments, tile) : nullptr);
+                capture_note(ctx, (const void*)fn, dim3(g), dim3(64), 0, &a, r, one ? uavqp::find_twisted_group(r, uniform_segments, tile) : nullptr,
+                             one && tile == 4 ? uavqp::find_twisted_group8(r, uniform_segments) : nullptr, tile);
             return UAVQP_OK;
         }
         if (ctx->variant == 2) {
@@ -823,9 +839,12 @@ static bool rebuild_captured(uavqp_ctx* ctx, hipGraph_t captured, int lanes, int
                         const BatchArgs& am = ctx->cap_launch[km].args;
                         sets.set[m] = uavqp::TwistedGroupSet{am.waypoints, am.times, am.bc, am.coeff, status_dead[km] ? nullptr : am.status};
                     }
+                    // which kernel: uavqp_capture.h: group_kernel_choice (a group of tile-4 launches over a whole number of eights runs eight trajectories per wave)
+                    const bool eight = uavqp_capture::group_kernel_choice((int)members.size(), l.tile, shape[k].one, l.args.n_traj, l.group8_fn != nullptr) ==
+                                       uavqp_capture::GROUP_EIGHT_PER_WAVE;
                     p = hipKernelNodeParams{};
-                    p.func = const_cast<void*>(l.group_fn);
-                    p.gridDim = dim3(l.grid.x, (unsigned int)members.size());
+                    p.func = const_cast<void*>(eight ? l.group8_fn : l.group_fn);
+                    p.gridDim = dim3(eight ? (unsigned int)(l.args.n_traj / uavqp::TWMAP8_TILE) : l.grid.x, (unsigned int)members.size());
                     p.blockDim = l.block;
                     p.sharedMemBytes = l.lds_bytes;
                     p.kernelParams = group_ptr;

@@ -322,6 +322,21 @@ static inline Fused fuse_groups(const std::vector<Record>& rec, const std::vecto
     return out;
 }
 
+// Which kernel the node of a group gets (uavqp.hip: rebuild_captured).  A group of two or more launches of the 16-lane one-tile-per-wave
+// kernel (tile 4) whose batch is a whole number of eights takes the eight-trajectories-per-wave kernel of its shape, where there is one
+// (qp_twisted.h: solve_twisted_group8_kernel -- the 16-lane arithmetic without the elimination two lane pairs repeat); every other group
+// of two or more takes the group kernel of its launches' own tile; a group of one is the launch as it was captured.
+//   members      solves in the group (fuse_groups)
+//   tile         trajectories per wave of the captured launches (4, 8, ...)
+//   one          the launches take the one-tile-per-wave instantiation and their shape has a group kernel at that tile (Shape::one)
+//   has_group8   the shape has a solve_twisted_group8_kernel (kernel_instances.h: uavqp_twisted_group8_exists)
+enum GroupKernel { GROUP_AS_CAPTURED = 0, GROUP_OWN_TILE = 1, GROUP_EIGHT_PER_WAVE = 2 };
+static inline GroupKernel group_kernel_choice(int members, int tile, bool one, int n_traj, bool has_group8) {
+    if (members < 2 || !one) return GROUP_AS_CAPTURED;   // (fuse_groups never gives a launch without `one` a second member)
+    if (tile == 4 && has_group8 && n_traj > 0 && n_traj % 8 == 0) return GROUP_EIGHT_PER_WAVE;
+    return GROUP_OWN_TILE;
+}
+
 // The knobs as the process environment has them NOW: read when a capture ends (uavqp_capture_end), never on a launch path.
 struct Knobs { int lanes, nodes_per_lane, fuse; };
 static inline Knobs knobs_from_environment() {
