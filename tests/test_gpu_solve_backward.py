@@ -6,7 +6,8 @@ linear in the waypoints and the boundary derivatives); for grad_times central di
 Richardson rule (the scheme's own error, h against h / 2, below 1e-5; the device within 10 x of it).  Tolerance for waypoints / bc: the project's
 parity tolerance, 1e-9 relative to max|grad| of that array per trajectory.
 
-Figures: docs/measurement_log.md, "Backward pass of the solve" (every test prints its worst case with -s)."""
+Figures: docs/measurement_log.md, "Backward pass of the solve" (every test prints its worst case with -s).
+Trajectories of more than 24 segments (25 to 96, every forward kernel, workspace records of interior knots): tests/test_gpu_long_gradients.py."""
 import os
 import subprocess
 
