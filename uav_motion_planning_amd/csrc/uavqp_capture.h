@@ -6,7 +6,7 @@
 // (lane of node k: k % lanes), kept with their results as the reference the conflict rules are pinned against.
 // fuse_groups then cuts every lane into groups of independent solves of one shape, each replayed as ONE launch.
 // Host-only: byte ranges and indices, no HIP type -- compiles without the runtime (tests/cpp/test_capture_deps.cpp, test_capture_lanes.cpp,
-// test_capture_fuse.cpp).
+// test_capture_fuse.cpp, test_capture_fuse_waves.cpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -258,19 +258,46 @@ struct Shape {
 static inline bool same_shape(const Shape& a, const Shape& b) {
     return a.fn == b.fn && a.grid == b.grid && a.block == b.block && a.lds_bytes == b.lds_bytes && a.n_traj == b.n_traj && a.one == b.one;
 }
-// UAVQP_CAPTURE_FUSE (1..8, anything else: the default): the most solves one launch of a replay carries; 1 = every solve its own launch.
-// The default is 2, chosen by measurement on MI355X among 2 / 4 / 8 (docs/measurement_log.md, 2026-10-20; 4096 x 8-segment min-snap, us per step,
-// medians of six plain runs, one launch per solve first): replayed graph of 200 steps 3.15 -> 2.44 / 2.19 / 2.10, of 20 steps (one lane)
-// 5.95 -> 4.47 / 3.91 / 3.74, of 1500 steps 3.09 -> 2.60 / 2.68 / 2.71.  4 and 8 are faster at 200 and at 20 steps, but with them a
-// two-lane replay depends on which hardware queues the runtime gave the two streams: a process that initialised its communication
-// library first replays 4-5 % (F = 4) and 5-8 % (F = 8) faster than a plain one, at F = 2 0.5 % -- and a default whose speed depends on
+// UAVQP_CAPTURE_FUSE (1..8): the most solves one launch of a replay carries, for every group; 1 = every solve its own launch.
+// Not set (or anything else): the cap of a group follows from a BUDGET OF WAVES per launch, UAVQP_CAPTURE_FUSE_WAVES (a positive
+// integer, anything else: FUSE_WAVES_DEFAULT), and from the waves one member adds in the kernel the group will run (member_waves):
+//   fuse_cap = min(FUSE_MAX, max(FUSE_DEFAULT, budget / waves per member)).
+// Why waves and not solves.  More members per launch replay faster at 200 and at 20 steps, but launches of 4096 and 8192 waves from two
+// lanes compete for the wave slots, and then a two-lane replay depends on which hardware queues the runtime gave the two streams: with
+// the four-per-wave group kernel a process that had initialised its communication library first replayed 4-5 % (4 members, 4096 waves)
+// and 5-8 % (8 members, 8192 waves) faster than a plain one, with 2 members (2048 waves) 0.5 % -- and a default whose speed depends on
 // what else the process did was ruled out when the lane count was chosen (REPLAY_LANES_DEFAULT; tests/test_gpu_bench_two_ranks.py holds
-// the two kinds of process within 6 % of each other).  UAVQP_CAPTURE_FUSE=8 is there for a caller that wants the fewest launches.
+// the two kinds of process within 6 % of each other).  That finding is about the size of a launch; a count of solves stands for it only
+// while every kernel puts as many trajectories in a wave.  The eight-per-wave kernel (group_kernel_choice) halves the waves of a solve:
+// two of its members are 1024 waves, one per SIMD, and a lone wave has nothing to issue during its own load wait and LDS round trips.
+// FUSE_DEFAULT, the cap before there was a budget, remains as the lower bound: no shape gets fewer members than it had.
+// FUSE_WAVES_DEFAULT is 2048 waves, chosen on MI355X between 4096 and 2048 by plain / communication-library / plain triples of the
+// benchmark (docs/measurement_log.md, 2026-10-21; the process with the library against the faster plain run): at 4096 the headline
+// shape (8 members of the eight-per-wave kernel, 512 waves each) stayed inside +4 % (+0.1 .. +3.5 %), but a batch of 4092 -- no whole
+// number of eights, 4 members of the 16-lane group kernel at 1023 waves each -- replayed 5.8-6.4 % faster with the library; at 2048 the
+// headline shape has 4 members (-2.6 .. +0.3 %) and the batch of 4092 the 2 it had.
 static constexpr int FUSE_MAX = 8;             // == uavqp::GROUP_MAX (qp_twisted.h): the pointer sets one kernarg struct holds
 static constexpr int FUSE_DEFAULT = 2;
+static constexpr int FUSE_WAVES_DEFAULT = 2048;
 static inline int fuse_from_env(const char* env) {
     const int v = env && *env ? std::atoi(env) : 0;
     return v >= 1 && v <= FUSE_MAX ? v : FUSE_DEFAULT;
+}
+// The count UAVQP_CAPTURE_FUSE names (1..8, what fuse_from_env returns for it), or 0 where it names none and the budget decides.
+static inline int fuse_named_from_env(const char* env) {
+    const int v = env && *env ? std::atoi(env) : 0;
+    return v >= 1 && v <= FUSE_MAX ? v : 0;
+}
+static inline int fuse_waves_from_env(const char* env) {
+    if (!env || !*env) return FUSE_WAVES_DEFAULT;
+    char* end = nullptr;
+    const long long v = std::strtoll(env, &end, 10);   // (saturates on overflow: out of range below)
+    return *end == '\0' && env[0] >= '0' && env[0] <= '9' && v >= 1 && v <= 2147483647LL ? (int)v : FUSE_WAVES_DEFAULT;
+}
+static inline int fuse_cap(int budget, int waves_per_member) {
+    if (budget <= 0 || waves_per_member <= 0) return FUSE_DEFAULT;
+    const int fit = budget / waves_per_member;
+    return fit < FUSE_DEFAULT ? FUSE_DEFAULT : (fit > FUSE_MAX ? FUSE_MAX : fit);
 }
 // The replay as it is built: stage s runs on width[s] lanes (lanes_that_pay; node k in lane lay.lane[k] % width[s]), and
 // group[s][l] holds the nodes of lane l of stage s, in capture order, cut into groups -- one launch each.  In capture order a node joins the
@@ -278,7 +305,9 @@ static inline int fuse_from_env(const char* env) {
 //   * it is no barrier and takes the one-tile-per-wave instantiation (Shape::one),
 //   * its shape key equals the group's,
 //   * it conflicts with NO member of the group (conflict(), with the dead-status flags lay_out was given),
-//   * the group has fewer than F members;
+//   * the group has fewer than F members -- with one cap per node (`cap`, cut to FUSE_MAX): fewer than the cap of its FIRST member.
+//     (rebuild_captured derives a node's cap from its shape, and equal shape keys are equal n_traj, grid and kernel function: one
+//     group, one cap);
 // otherwise it opens a new group.  Hence
 //   * every node is in exactly one group;
 //   * the groups of a lane are in capture order: every node of a group comes before every node of the next one;
@@ -292,11 +321,10 @@ struct Fused {
     bool fused = false;                                                // some group has two members
 };
 static inline Fused fuse_groups(const std::vector<Record>& rec, const std::vector<char>& status_dead, const Layout& lay, const std::vector<Shape>& shape,
-                                int F, int lanes, int nodes_per_lane = NODES_PER_LANE_MIN) {
+                                const std::vector<int>& cap, int lanes, int nodes_per_lane = NODES_PER_LANE_MIN) {
     Fused out;
     const int n = (int)rec.size();
-    if (n == 0 || lay.lane.size() != (size_t)n || lay.starts.empty() || shape.size() != (size_t)n) return out;
-    if (F > FUSE_MAX) F = FUSE_MAX;
+    if (n == 0 || lay.lane.size() != (size_t)n || lay.starts.empty() || shape.size() != (size_t)n || cap.size() != (size_t)n) return out;
     if (lanes < 1) lanes = 1;
     const bool have_dead = status_dead.size() == (size_t)n;
     for (size_t s = 0; s < lay.starts.size(); ++s) {
@@ -307,6 +335,7 @@ static inline Fused fuse_groups(const std::vector<Record>& rec, const std::vecto
         for (int k = first; k < last; ++k) {
             std::vector<std::vector<int>>& chain = out.group.back()[(size_t)(lay.lane[k] % width)];
             const bool k_dead = have_dead && status_dead[k] != 0;
+            const int F = chain.empty() ? 0 : (cap[(size_t)chain.back()[0]] < FUSE_MAX ? cap[(size_t)chain.back()[0]] : FUSE_MAX);
             bool join = !chain.empty() && !rec[k].barrier && shape[k].one && (int)chain.back().size() < F && same_shape(shape[chain.back()[0]], shape[k]);
             if (join)    // (the first member of a group that takes a second is no barrier and `one`: same_shape compares the flag)
                 for (int i : chain.back())
@@ -320,6 +349,11 @@ static inline Fused fuse_groups(const std::vector<Record>& rec, const std::vecto
         if (busy > 1) out.side_by_side = true;
     }
     return out;
+}
+// One cap F for every node (UAVQP_CAPTURE_FUSE names a count; the CPU programs under tests/cpp).
+static inline Fused fuse_groups(const std::vector<Record>& rec, const std::vector<char>& status_dead, const Layout& lay, const std::vector<Shape>& shape,
+                                int F, int lanes, int nodes_per_lane = NODES_PER_LANE_MIN) {
+    return fuse_groups(rec, status_dead, lay, shape, std::vector<int>(rec.size(), F), lanes, nodes_per_lane);
 }
 
 // Which kernel the node of a group gets (uavqp.hip: rebuild_captured).  A group of two or more launches of the 16-lane one-tile-per-wave
@@ -336,12 +370,19 @@ static inline GroupKernel group_kernel_choice(int members, int tile, bool one, i
     if (tile == 4 && has_group8 && n_traj > 0 && n_traj % 8 == 0) return GROUP_EIGHT_PER_WAVE;
     return GROUP_OWN_TILE;
 }
+// The waves ONE member adds to a group launch, in the kernel a group of launches of this shape runs: the eight-per-wave kernel has a
+// wave for every eight trajectories, the group kernel of the launch's own tile the waves of the captured launch (`grid`, block 64).
+// A launch that is never fused (not `one`) counts as captured.
+static inline int member_waves(int tile, bool one, int n_traj, unsigned grid, bool has_group8) {
+    return group_kernel_choice(FUSE_DEFAULT, tile, one, n_traj, has_group8) == GROUP_EIGHT_PER_WAVE ? n_traj / 8 : (int)grid;
+}
 
 // The knobs as the process environment has them NOW: read when a capture ends (uavqp_capture_end), never on a launch path.
-struct Knobs { int lanes, nodes_per_lane, fuse; };
+// fuse_named: the count UAVQP_CAPTURE_FUSE names, 0 where the budget fuse_waves decides (fuse_named_from_env).
+struct Knobs { int lanes, nodes_per_lane, fuse_named, fuse_waves; };
 static inline Knobs knobs_from_environment() {
     return Knobs{replay_lanes_from_env(std::getenv("UAVQP_CAPTURE_LANES"), std::getenv("GPU_MAX_HW_QUEUES")), lane_nodes_from_env(std::getenv("UAVQP_CAPTURE_LANE_NODES")),
-                 fuse_from_env(std::getenv("UAVQP_CAPTURE_FUSE"))};
+                 fuse_named_from_env(std::getenv("UAVQP_CAPTURE_FUSE")), fuse_waves_from_env(std::getenv("UAVQP_CAPTURE_FUSE_WAVES"))};
 }
 
 }  // namespace uavqp_capture
