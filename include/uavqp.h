@@ -1162,6 +1162,7 @@ int uavqp_swarm_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segm
  * trial) holds back the step of every vehicle of its swarm, and the scales are fixed at the FIRST gradient, as in
  * uavqp_spacetime_optimize_device; a second call re-scales.  The hard tests remain uavqp_time_reallocate_device (limits) and
  * uavqp_ellipsoid_check_* (collisions); separation is reported by d_min_sep_out on the swarm's clock samples only.
+ * Between the samples it is BOUNDED by uavqp_separation_certificate_* below, the hard test of the separation.
  * Out of scope: quasi-Newton directions per swarm, capture into a graph, corridor and general-rows solves, a swarm sharded over several
  * GPUs. */
 typedef struct uavqp_swarm_opt_params {
@@ -1196,6 +1197,83 @@ int uavqp_swarm_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_seg
                               const uavqp_swarm_params* swarm, const uavqp_swarm_opt_params* params, double* coeff_out, int32_t* status_out,
                               double* objective_out, int32_t* accepted_out, double* peak_out, double* min_dist_out, int32_t* outside_out,
                               double* min_sep_out);
+
+/* Certified continuous-time separation between the vehicles of a swarm (no reference counterpart): the acceptance test after
+ * uavqp_swarm_optimize_*.  The swarm penalty's min_sep and the optimiser's d_min_sep_out SAMPLE the shared clock: two vehicles that cross at
+ * 5 m/s each close 1 m between two samples 0.1 s apart, so a pair can pass every sample and still touch between them.  This BOUNDS, for
+ * every vehicle, its separation from every partner from both sides: `lower` holds for EVERY t of the clock window [clock_start,
+ * clock_start + n_cells dt] and every partner, `upper` is taken at a reported instant and partner.
+ * The batch and the swarms are described exactly as for uavqp_swarm_penalty_device (r, n_traj, uniform_segments, d_seg_offsets, d_times,
+ * d_coeff, d_status, n_groups, d_group_offsets, d_start), with the same UAVQP_SWARM_MAX_VEHICLES rule: the _host entry refuses a larger
+ * swarm, the _device entry gives such a swarm NaN bounds, `where` {-1, 0, -1, 0} and zero words.
+ * The certified curve.  The clock knots of vehicle b are the DOUBLES K_0 = start_b, K_{m+1} = fl(K_m + T_m).  For t <= K_0, q_b(t) is
+ * segment 0 at local time 0 (the vehicle waits); for t in [K_m, K_{m+1}] it is segment m at local time t - K_m (real arithmetic); for
+ * t >= K_M it is the last segment at T_{M-1} (it has arrived).  Pieces are closed, so at a knot both values belong to the curve (each is
+ * seen by the leaf on its side of the knot; at the last instant of the window the curve is the piece the last leaf lies in).  This is the
+ * swarm penalty's curve, except that it leaves out the 1e-4 s of overhang that the segment rule of uavqp_eval_batch_device allows.
+ *       s_ij(t) = sqrt(dx^2 + dy^2 + (dz / downwash)^2) of q_i(t) - q_j(t)
+ * Leaves.  Every clock cell is cut into 2^depth leaves: tau_w = clock_start + w (dt / 2^depth) (the nearest double), w = 0..NL,
+ * NL = n_cells 2^depth; leaf l is [tau_l, tau_{l+1}].  With depth = 0 the tau_w are exactly the penalty's sample instants.
+ * Method (n = 2r - 1; csrc/qp_separation_cert.h derives the constants, tests/separation_cert_reference.py restates it in numpy).  Per
+ * (vehicle, leaf), every segment whose closed piece meets the leaf is restricted to it: the Bernstein coefficients of uavqp_envelope_*
+ * on the segment, then two general-ratio de Casteljau splits at lambda_1 = lb / T_m (left half kept) and lambda_2 = la / lb (right half
+ * kept), la = max(tau_l - K_m, 0), lb = min(tau_{l+1} - K_m, T_m), both ratios clamped to [0, 1]; a hold is a constant polynomial.  A
+ * leaf inside ONE piece (all waiting, all arrived, or K_m <= tau_l and tau_{l+1} <= K_{m+1} on the doubles) gives a SINGLE entry, the
+ * 3 x (n + 1) coefficients; a leaf that straddles a knot, the departure or the arrival gives a BOX entry, the per-axis [lo, hi] over the
+ * coefficients of all its pieces.  Guard per axis G_x = (64 (n + 1) + 2 n kappa) 2^-53 S_x, S_x = sum_k |c_k T^k| of the segment, kappa =
+ * max(|K_m|, |K_{m+1}|) / T_m (K_{m+1} is a rounded sum), the largest over the pieces of the entry.
+ * Pair (i, j) on a leaf: both single, the range of q_i - q_j per axis is [min_k, max_k] of b_ik - b_jk (both are Bernstein in the same
+ * parameter over the same leaf, so correlated motion cancels); otherwise the interval difference of the two boxes (the box of a single
+ * entry: min / max of its coefficients).  Widened by G_i + G_j; g_x = max(0, lo_x, -hi_x);
+ *       L = sqrt(g_x^2 + g_y^2 + (g_z / downwash)^2) - R,                          R = 16 2^-53 (sum_x max(|lo_x|, |hi_x|))
+ *       U = s_ij(tau_w) + sqrt(3) max_x (G_ix + G_jx) + R_w  at the leaf ends,      R_w = 16 2^-53 (|d_x| + |d_y| + |d_z|) of the difference
+ *   lower_i = max(0, min over j and leaves of L),  upper_i = min over j and witnesses of U;  min_t min_j s_ij(t) over the window lies in
+ * [lower_i, upper_i].  A tie goes to the smaller partner, then the smaller index.
+ * Outputs (each may be NULL; all NULL: UAVQP_OK, nothing done; every element is written exactly once):
+ *   d_lower          [n_traj]: holds for every t of the window and every partner
+ *   d_upper          [n_traj]: taken at a witness
+ *   d_where          [n_traj][4] int32: {partner of lower, leaf of lower, partner of upper, witness index w of upper (the instant tau_w)};
+ *                    partners are batch indices, -1 (and index 0) when there is none
+ *   d_verdict        [n_traj] int32: UAVQP_SEPARATION_CERTIFIED (lower >= d_req: holds for ALL t of the window), UAVQP_SEPARATION_VIOLATED
+ *                    (upper < d_req: broken at the witness), neither: undecided at this depth; UAVQP_SEPARATION_MOVING: the vehicle is
+ *                    still under way at the end of the window (K_M > tau_NL) -- the certificate says nothing about what happens afterwards
+ *   d_group_verdict  [n_groups] int32: AND of the certified bit, OR of the other bits over the vehicles of the swarm that take part; 0 for
+ *                    a swarm in which none does
+ * A vehicle that is not UAVQP_SOLVED (d_status NULL: all are), or has M < 1, is left out of every pair; its outputs are INFINITY, INFINITY,
+ * {-1, 0, -1, 0}, 0.  A solved vehicle without a partner gets INFINITY bounds and counts as certified.  Non-finite coefficients or a
+ * duration <= 0 in a piece the window meets give the vehicle AND its partners NaN bounds, {-1, 0, -1, 0} and no bits.
+ * Every min is exact and a pair's numbers are the same bits from both sides: the same bytes for any grid, run to run, and for a swarm
+ * computed alone or in the middle of a batch.  One launch, asynchronous on the ctx stream, no allocation, no workspace, no atomics, no
+ * read-back.
+ * UAVQP_ERR_INVALID_ARG: r not 3 / 4, a negative count, a wrong struct_size, depth outside 0..6, n_cells < 1 or above
+ * UAVQP_SEPARATION_MAX_CELLS, dt or d_req not finite or <= 0, downwash not finite or < 1, clock_start not finite, NULL times / coeff, ragged
+ * without offsets, n_groups < 0, NULL group offsets with n_groups != 1; from the _host entry also group offsets that do not ascend from 0
+ * to n_traj or a swarm larger than UAVQP_SWARM_MAX_VEHICLES.
+ * Out of scope: splitting a straddling leaf at the pair's merged knots (without it a straddling leaf falls back to boxes); a degree-2n
+ * squared-distance polynomial per pair; adaptive subdivision; non-cooperative obstacles; wiring the verdict into uavqp_swarm_optimize_*. */
+#define UAVQP_SEPARATION_CERTIFIED 1   /* lower >= d_req: holds for ALL t of the window */
+#define UAVQP_SEPARATION_VIOLATED 2    /* upper <  d_req: broken at the witness */
+#define UAVQP_SEPARATION_MOVING 4      /* still under way at the end of the window */
+#define UAVQP_SEPARATION_MAX_CELLS 1048576
+typedef struct uavqp_separation_params {
+    int32_t struct_size;
+    int32_t depth;        /* 0..6: every clock cell is cut into 2^depth leaves (default 2) */
+    int32_t n_cells;      /* N >= 1 cells of dt: the window is [clock_start, clock_start + N dt] (default 64) */
+    double clock_start;   /* as in uavqp_swarm_params (default 0) */
+    double dt;            /* (default 0.1) */
+    double downwash;      /* (default 1.0) */
+    double d_req;         /* required separation, m, finite, > 0 (default 1.0) */
+} uavqp_separation_params;
+void uavqp_default_separation_params(uavqp_separation_params* out);   /* callable without a device */
+int uavqp_separation_certificate_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
+                                        const double* d_times, const double* d_coeff, const int32_t* d_status, int n_groups,
+                                        const int32_t* d_group_offsets, const double* d_start, const uavqp_separation_params* params,
+                                        double* d_lower, double* d_upper, int32_t* d_where, int32_t* d_verdict, int32_t* d_group_verdict);
+/* The same from HOST pointers (H2D copy, run, D2H copy, synchronous). */
+int uavqp_separation_certificate_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
+                                      const double* coeff, const int32_t* status, int n_groups, const int32_t* group_offsets,
+                                      const double* start, const uavqp_separation_params* params, double* lower, double* upper,
+                                      int32_t* where, int32_t* verdict, int32_t* group_verdict);
 
 /* Batched evaluation of solved trajectories on a uniform time grid.
  * Replaces, for a whole batch, PolyTraj::evaluatePos / evaluateVel / evaluateAcc

@@ -98,6 +98,9 @@ SYMBOLS = (
     "uavqp_default_swarm_opt_params",
     "uavqp_swarm_optimize_device",
     "uavqp_swarm_optimize_host",
+    "uavqp_default_separation_params",
+    "uavqp_separation_certificate_device",
+    "uavqp_separation_certificate_host",
     "uavqp_eval_batch_device",
     "uavqp_traj_length_device",
     "uavqp_ellipsoid_check_device",
@@ -243,6 +246,18 @@ class SwarmOptParams(ctypes.Structure):
 UAVQP_SWARM_MAX_VEHICLES = 128
 
 
+class SeparationParams(ctypes.Structure):
+    """uavqp_separation_params of include/uavqp.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("depth", ctypes.c_int32), ("n_cells", ctypes.c_int32), ("clock_start", ctypes.c_double),
+                ("dt", ctypes.c_double), ("downwash", ctypes.c_double), ("d_req", ctypes.c_double)]
+
+
+# the bits of a uavqp_separation_certificate_* verdict word (UAVQP_SEPARATION_* of include/uavqp.h)
+UAVQP_SEPARATION_CERTIFIED = 1
+UAVQP_SEPARATION_VIOLATED = 2
+UAVQP_SEPARATION_MOVING = 4
+
+
 def build(force=False):
     """Compile csrc/*.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
     csrc = os.path.join(_PKG, "csrc")
@@ -368,6 +383,10 @@ def lib():
     L.uavqp_default_swarm_params.restype = None
     L.uavqp_swarm_penalty_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, i32, ip, dp, ctypes.POINTER(SwarmParams), dp, dp, dp, dp, dp]
     L.uavqp_swarm_penalty_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, i32, ip, dp, ctypes.POINTER(SwarmParams), dp, dp, dp, dp, dp]
+    L.uavqp_default_separation_params.argtypes = [ctypes.POINTER(SeparationParams)]
+    L.uavqp_default_separation_params.restype = None
+    L.uavqp_separation_certificate_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, i32, ip, dp, ctypes.POINTER(SeparationParams), dp, dp, ip, ip, ip]
+    L.uavqp_separation_certificate_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, i32, ip, dp, ctypes.POINTER(SeparationParams), dp, dp, ip, ip, ip]
     L.uavqp_default_swarm_opt_params.argtypes = [ctypes.POINTER(SwarmOptParams)]
     L.uavqp_default_swarm_opt_params.restype = None
     L.uavqp_swarm_optimize_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, i32, ip, dp, vp, ctypes.POINTER(LimitParams),

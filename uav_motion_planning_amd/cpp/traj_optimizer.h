@@ -220,6 +220,37 @@ class TrajOptimizer {
         }
         return phi;
     }
+    // Certified separation between the vehicles of each swarm set with setSwarm, at the stored coefficients, durations and departures, for
+    // EVERY t of the clock window of `params` (after solve() or optimizeSwarm(); uavqp_separation_certificate_host): the hard test that
+    // the sampled min_sep is not.  Returns the verdict word per trajectory (UAVQP_SEPARATION_CERTIFIED: at least d_req from every partner
+    // for ALL t of the window, UAVQP_SEPARATION_VIOLATED: less at the witness, neither: undecided; UAVQP_SEPARATION_MOVING: still under way
+    // at the end of the window) and fills separationLower() / separationUpper() [n_traj], separationWhere() [n_traj][4] ({partner of lower,
+    // leaf of lower, partner of upper, witness index of upper}) and separationGroupVerdict() [n_groups].  Empty on failure.
+    std::vector<int32_t> getSeparationCertificate(const uavqp_separation_params& params) {
+        std::vector<int32_t> verdict;
+        if (n_traj_ <= 0 || !ctx_ || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_]) ||
+            coef_.size() != static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_] || status_.size() != static_cast<size_t>(n_traj_) ||
+            (!start_.empty() && start_.size() != static_cast<size_t>(n_traj_)))
+            return verdict;
+        const int n_groups = groups_.empty() ? 1 : static_cast<int>(groups_.size()) - 1;
+        verdict.assign(n_traj_, 0);
+        separation_lower_.assign(n_traj_, 0.0);
+        separation_upper_.assign(n_traj_, 0.0);
+        separation_where_.assign(static_cast<size_t>(4) * n_traj_, 0);
+        separation_group_verdict_.assign(n_groups, 0);
+        if (uavqp_separation_certificate_host(ctx_, order_, n_traj_, 0, seg_offsets_.data(), T_.data(), coef_.data(), status_.data(), n_groups,
+                                              groups_.empty() ? nullptr : groups_.data(), start_.empty() ? nullptr : start_.data(), &params,
+                                              separation_lower_.data(), separation_upper_.data(), separation_where_.data(), verdict.data(),
+                                              separation_group_verdict_.data()) != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            verdict.clear();
+        }
+        return verdict;
+    }
+    const std::vector<double>& separationLower() const { return separation_lower_; }
+    const std::vector<double>& separationUpper() const { return separation_upper_; }
+    const std::vector<int32_t>& separationWhere() const { return separation_where_; }
+    const std::vector<int32_t>& separationGroupVerdict() const { return separation_group_verdict_; }
     // Clearance penalty per trajectory of the stored coefficients at the stored durations against a distance field (uavqp::EsdfMap of
     // cpp/esdf_map.h, built on context() and updated; uavqp_clearance_penalty_host).  min_dist / outside, when given, receive the smallest
     // sampled distance and the count of samples outside the map per trajectory.  A trajectory that did not solve carries zero.  Empty on failure.
@@ -762,6 +793,8 @@ class TrajOptimizer {
     std::vector<double> clearance_bounds_, clearance_peak_;
     std::vector<int32_t> outside_;
     std::vector<int32_t> accepted_;
+    std::vector<double> separation_lower_, separation_upper_;
+    std::vector<int32_t> separation_where_, separation_group_verdict_;
     std::vector<int32_t> groups_;   // setSwarm: empty = the whole batch is one swarm
     std::vector<double> start_;     // setSwarm: empty = every vehicle departs at 0
     int rows_k_ = 0;

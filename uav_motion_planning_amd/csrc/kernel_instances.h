@@ -194,3 +194,7 @@ static inline bool uavqp_twisted_group_exists(int r, int M, int tile) {
 // ---- qp_clearance_cert.h: certified clearance of whole segments against the distance field's integer squared distances
 #define UAVQP_CLEARANCE_CERT_R(R_) UAVQP_INST __global__ void uavqp::clearance_cert_kernel<R_>(uavqp::ClearanceCertArgs);
 #define UAVQP_INSTANCES_CLEARANCE_CERT UAVQP_CLEARANCE_CERT_R(3) UAVQP_CLEARANCE_CERT_R(4)
+
+// ---- qp_separation_cert.h: certified separation between the vehicles of a swarm over a whole clock window
+#define UAVQP_SEPARATION_CERT_R(R_) UAVQP_INST __global__ void uavqp::separation_cert_kernel<R_>(uavqp::SeparationCertArgs);
+#define UAVQP_INSTANCES_SEPARATION_CERT UAVQP_SEPARATION_CERT_R(3) UAVQP_SEPARATION_CERT_R(4)

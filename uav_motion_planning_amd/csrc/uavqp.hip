@@ -43,6 +43,7 @@
 #include "qp_attitude.h"
 #include "qp_envelope.h"
 #include "qp_clearance_cert.h"
+#include "qp_separation_cert.h"
 // Measured-slower alternatives kept as bit-identical cross-checks: `make experiments` (-DUAVQP_EXPERIMENTS) only
 #ifdef UAVQP_EXPERIMENTS
 #include "cloud_grid2d.h"
@@ -83,6 +84,7 @@ UAVQP_INSTANCES_SWARM_OPT
 UAVQP_INSTANCES_ATTITUDE
 UAVQP_INSTANCES_ENVELOPE
 UAVQP_INSTANCES_CLEARANCE_CERT
+UAVQP_INSTANCES_SEPARATION_CERT
 #endif
 
 namespace uavqp {
@@ -251,6 +253,7 @@ struct uavqp_ctx {
     int dual_trips_extra = 0;   // added to the trip budget 4 n + 16 of the dual preludes (UAVQP_DUAL_TRIPS_EXTRA, may be negative: tools/ experiments)
     int clearance_cert_blocks = 0;   // cap on the blocks of the clearance certificate's launch (UAVQP_CLEARANCE_CERT_BLOCKS; 0: topt_grid's cap
                                      // alone): the tests set it to run the grid-stride loop on a small batch
+    int separation_cert_blocks = 0;  // the same for the separation certificate's launch (UAVQP_SEPARATION_CERT_BLOCKS; 0: the cap of its LDS alone)
     int wave_prelude = 2;       // re-solves with G in the cache: 2 = corridor_dual_wave2_kernel (two trajectories per wave), 1 = corridor_dual_wave_kernel (one),
                                 // 0 = the batch kernels (UAVQP_WAVE_PRELUDE=0|1|2, UAVQP_NO_WAVE_PRELUDE: A/B runs)
     void* dbg_dual = nullptr;   // (UAVQP_DUAL_DEBUG builds) dump area of corridor_dual_kernel
@@ -432,6 +435,7 @@ extern "C" int uavqp_create(uavqp_ctx** out_ctx, int device) {
     if (const char* e = std::getenv("UAVQP_DEAL_TICKETS")) ctx->deal_tickets = std::atoi(e) != 0;
     if (const char* e = std::getenv("UAVQP_DUAL_TRIPS_EXTRA")) ctx->dual_trips_extra = std::atoi(e);
     if (const char* e = std::getenv("UAVQP_CLEARANCE_CERT_BLOCKS")) { const int v = std::atoi(e); if (v > 0) ctx->clearance_cert_blocks = v; }
+    if (const char* e = std::getenv("UAVQP_SEPARATION_CERT_BLOCKS")) { const int v = std::atoi(e); if (v > 0) ctx->separation_cert_blocks = v; }
     if (const char* e = std::getenv("UAVQP_WAVE_PRELUDE")) { const int v = std::atoi(e); if (v >= 0 && v <= 2) ctx->wave_prelude = v; }
     if (const char* e = std::getenv("UAVQP_GENERIC_NAX")) ctx->settings.generic_lanes_per_traj = std::atoi(e) == 3 ? 1 : 3;
     if (const char* e = std::getenv("UAVQP_GENERIC_WPC")) {
@@ -2043,6 +2047,11 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
 // ===================================================================================================
 #include "uavqp_swarm.h"
 #include "uavqp_swarm_opt.h"
+
+// ===================================================================================================
+// Certified continuous-time separation between the vehicles of a swarm (shares the swarm penalty's description of the swarms)
+// ===================================================================================================
+#include "uavqp_separation_cert.h"
 
 // ===================================================================================================
 // N3: quadrotor_msgs/PolynomialTrajectory packer (host only)

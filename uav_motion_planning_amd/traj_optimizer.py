@@ -241,6 +241,56 @@ class Context:
         return penalty, g_c, g_t, g_s, min_sep
 
     @staticmethod
+    def _separation_params(params):
+        sp = _lib.SeparationParams()
+        _lib.lib().uavqp_default_separation_params(ctypes.byref(sp))
+        for k, v in params.items():
+            if not hasattr(sp, k) or k == "struct_size":
+                raise ValueError(f"unknown uavqp_separation_params field {k!r}")
+            setattr(sp, k, v)
+        return sp
+
+    def separation_certificate_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, n_groups=1, group_offsets=None, start=None,
+                                      status=None, lower_out=None, upper_out=None, where_out=None, verdict_out=None, group_verdict_out=None,
+                                      **params):
+        """uavqp_separation_certificate_device on device buffers: certified separation between the vehicles of each swarm (described as for
+        swarm_penalty_device) over the WHOLE clock window, not at its samples.  lower_out [n_traj] holds for every t of the window and every
+        partner, upper_out [n_traj] is taken at a witness, where_out [n_traj][4] int32 = {partner of lower, leaf of lower, partner of upper,
+        witness index of upper}, verdict_out [n_traj] and group_verdict_out [n_groups] int32 (_lib.UAVQP_SEPARATION_CERTIFIED / _VIOLATED /
+        _MOVING); each may be None.  params: fields of uavqp_separation_params that differ from uavqp_default_separation_params (depth,
+        n_cells, clock_start, dt, downwash, d_req).  Asynchronous."""
+        sp = self._separation_params(params)
+        rc = _lib.lib().uavqp_separation_certificate_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff),
+                                                            _ptr(status), int(n_groups), _ptr(group_offsets), _ptr(start), ctypes.byref(sp),
+                                                            _ptr(lower_out), _ptr(upper_out), _ptr(where_out), _ptr(verdict_out),
+                                                            _ptr(group_verdict_out))
+        _lib.check(rc, "uavqp_separation_certificate_device")
+
+    def separation_certificate(self, r, seg_offsets, times, coeff, group_offsets=None, start=None, uniform_segments=0, status=None, **params):
+        """uavqp_separation_certificate_host: numpy in / numpy out (synchronous).  group_offsets None: the whole batch is one swarm.  Returns
+        (lower [n_traj], upper [n_traj], where [n_traj][4], verdict [n_traj], group_verdict [n_groups]); see separation_certificate_device."""
+        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
+        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total and coeff.size == 3 * 2 * r * total
+        go = None if group_offsets is None else np.ascontiguousarray(group_offsets, dtype=np.int32)
+        n_groups = 1 if go is None else go.size - 1
+        start = None if start is None else np.ascontiguousarray(start, dtype=np.float64).ravel()
+        assert start is None or start.size == n_traj
+        sp = self._separation_params(params)
+        lower = np.zeros(n_traj, dtype=np.float64)
+        upper = np.zeros(n_traj, dtype=np.float64)
+        where = np.zeros((n_traj, 4), dtype=np.int32)
+        verdict = np.zeros(n_traj, dtype=np.int32)
+        group_verdict = np.zeros(n_groups, dtype=np.int32)
+        rc = _lib.lib().uavqp_separation_certificate_host(self._h, r, n_traj, uniform_segments, _ptr(so), _ptr(times), _ptr(coeff), _ptr(status),
+                                                          n_groups, _ptr(go), _ptr(start), ctypes.byref(sp), _ptr(lower), _ptr(upper),
+                                                          _ptr(where), _ptr(verdict), _ptr(group_verdict))
+        _lib.check(rc, "uavqp_separation_certificate_host")
+        return lower, upper, where, verdict, group_verdict
+
+    @staticmethod
     def _clearance_params(params):
         cp = _lib.ClearanceParams()
         _lib.lib().uavqp_default_clearance_params(ctypes.byref(cp))
@@ -1116,6 +1166,8 @@ class TrajOptimizer:
     setSwarm(group_offsets, start_times)   which trajectories fly together (swarm g = trajectories group_offsets[g] .. group_offsets[g + 1];
                                      None: the whole batch is one swarm) and when each departs on its swarm's clock (None: all at 0)
     getSwarmPenalty(...)             [n_groups] separation penalty between the vehicles of each swarm at the stored coefficients
+    getSeparationCertificate(...)    certified separation between the vehicles of each swarm for EVERY t of a clock window (lower / upper
+                                     bounds, witness, verdict against d_req): the hard test after optimizeSwarm
     optimizeSwarm(esdf, ...)         optimizeTrajectory with that penalty in the objective and one accept / reject per SWARM; with
                                      start_window > 0 the departures are optimised too (getSwarmStart()); .min_sep per trajectory
     getCostWaypointGradient()        [sum (M_b + 1)][3] gradient of getCost() in the waypoints, both ends of every trajectory included
@@ -1432,6 +1484,22 @@ class TrajOptimizer:
                                                  limits=limits, clearance=clearance, swarm=swarm, **params)
         self._start = start
         return bool(np.all(self.status == _lib.UAVQP_SOLVED))
+
+    def getSeparationCertificate(self, depth=2, d_req=1.0, **clock):
+        """Certified separation between the vehicles of each swarm set with setSwarm(), at the stored coefficients, durations and departures,
+        for EVERY t of the clock window (uavqp_separation_certificate_host; after solve() or optimizeSwarm()): the hard test that the
+        sampled min_sep is not.  clock: n_cells, clock_start, dt, downwash of uavqp_separation_params that differ from the defaults.  Returns
+        a dict: lower, upper [n_traj], where [n_traj][4] ({partner of lower, leaf of lower, partner of upper, witness index of upper}),
+        verdict [n_traj], group_verdict [n_groups] (the int32 words) and, per trajectory, the boolean masks certified (>= d_req for ALL t of
+        the window), violated (< d_req at the witness), undecided, and moving (still under way at the end of the window)."""
+        if self._ctx is None or self._coef.size != 3 * 2 * self._r * int(self._so[-1]) or self.status.size != self._so.size - 1:
+            raise _lib.UavqpError("getSeparationCertificate: no solved coefficients (call solve() or an optimiser first)")
+        lower, upper, where, verdict, group_verdict = self._ctx.separation_certificate(
+            self._r, self._so, self._T, self._coef, group_offsets=self._groups, start=self._start, status=self.status, depth=depth, d_req=d_req,
+            **clock)
+        c, v = verdict & _lib.UAVQP_SEPARATION_CERTIFIED != 0, verdict & _lib.UAVQP_SEPARATION_VIOLATED != 0
+        return dict(lower=lower, upper=upper, where=where, verdict=verdict, group_verdict=group_verdict, certified=c, violated=v,
+                    undecided=~c & ~v & (self.status == _lib.UAVQP_SOLVED), moving=verdict & _lib.UAVQP_SEPARATION_MOVING != 0)
 
     def getSwarmStart(self):
         """[n_traj] the departures of setSwarm(), as optimizeSwarm() left them (None: all at 0)."""
