@@ -77,10 +77,12 @@ def _sentinels(t):
     return O._bits(t) == np.float64(O.COEFF_FILL).view(np.int64)
 
 
-def _rotation(ctx, planner, r, M, n, tile, lanes, F, solves, sets):
+def _rotation(ctx, planner, r, M, n, tile, lanes, F, solves, sets, has_group=None):
     """`solves` solves over `sets` buffer sets, each with a status array of its own except set 1, which has none; set 0 carries a
-    non-positive duration."""
+    non-positive duration.  has_group: is (r, M) in the group list of this tile (default: HAS_GROUP).  Returns the eager buffers (bitwise
+    the replayed ones) and the launches of the replay."""
     import uav_motion_planning_amd as U
+    has_group = HAS_GROUP[(r, M, tile)] if has_group is None else has_group
 
     def make():
         bufs = {}
@@ -95,7 +97,7 @@ def _rotation(ctx, planner, r, M, n, tile, lanes, F, solves, sets):
     sizes = sorted(len(g) for g in launches)
     print(f"r={r} M={M} n={n} tile={tile} lanes={lanes} F={F}: {solves} solves over {sets} sets -> launches {launches}")
     assert sizes[-1] <= F
-    if F == 1 or not HAS_GROUP[(r, M, tile)]:
+    if F == 1 or not has_group:
         assert sizes[-1] == 1
     elif lanes == 1:
         assert sizes[-1] == min(F, sets, solves)                 # a lane meets a set again after `sets` solves
@@ -114,6 +116,7 @@ def _rotation(ctx, planner, r, M, n, tile, lanes, F, solves, sets):
         else:
             assert st is None or np.all(st == U.UAVQP_SOLVED)
             assert not np.any(left)
+    return eager, launches
 
 
 @pytest.mark.parametrize("r,M", RM)

@@ -8,6 +8,8 @@ import pytest
 from uav_motion_planning_amd import UAVQP_INVALID_INPUT, UAVQP_SOLVED
 from uav_motion_planning_amd import workloads as W
 
+from twisted_instances import has_twisted      # the (r, M) lists of csrc/kernel_instances.h
+
 pytestmark = pytest.mark.gpu
 
 
@@ -39,8 +41,8 @@ def test_uniform_batch_vs_oracle(gpu_ctx, oracle, r, M, time_mode, variant):
     """variant 1 = generic lane-per-trajectory kernel, 0 = auto (register-resident twisted kernel where
     an (r, M) instantiation exists).  n = 45 leaves a partial 32-trajectory tile."""
     n = 45
-    if variant >= 4 and (M < 2 or M > 12 or M == 11):
-        pytest.skip("no specialised instantiation for this M")
+    if variant >= 4 and not has_twisted(r, M):
+        pytest.skip("no specialised instantiation for this (r, M)")
     b = W.uniform_batch(100 + M, n, M, r, time_mode=time_mode)
     gpu_ctx.set_variant(variant)
     got, st = gpu_ctx.solve_batch_host(r, None, b["waypoints"], b["times"], b["bc"], uniform_segments=M)
@@ -97,7 +99,7 @@ def test_randomised_shapes_and_variants_vs_oracle(gpu_ctx, oracle):
             M = int(rng.integers(1, 18))
             b = W.uniform_batch(draw, n, M, r, time_mode=str(rng.choice(["reference", "distance", "wide"])), seed=2000 + draw)
             b["bc"] = rng.uniform(-2.0, 2.0, size=b["bc"].shape)       # all boundary derivatives non-zero
-            gpu_ctx.set_variant(int(rng.choice([0, 1, 2, 4, 8, 16, 32])) if (2 <= M <= 12 and M != 11) else int(rng.choice([0, 1])))
+            gpu_ctx.set_variant(int(rng.choice([0, 1, 2, 4, 8, 16, 32])) if has_twisted(r, M) else int(rng.choice([0, 1])))
             got, st = gpu_ctx.solve_batch_host(r, None, b["waypoints"], b["times"], b["bc"], uniform_segments=M)
             gpu_ctx.set_variant(0)
         ref, _ = oracle.solve_exact_batch(r, b["seg_offsets"], np.asarray(b["waypoints"]).reshape(-1, 3),

@@ -105,9 +105,13 @@ def _sentinels(t):
     return O._bits(t) == np.float64(O.COEFF_FILL).view(np.int64)
 
 
-def _rotation(ctx, host_rules, r, M, n, lanes, F, solves, sets):
+def _rotation(ctx, host_rules, r, M, n, lanes, F, solves, sets, has_group=None, has_group8=None, report=None):
+    """has_group / has_group8: is (r, M) in the tile-4 group list / the eight-per-wave list (default: HAS_GROUP8 for both -- the two
+    lists of csrc/kernel_instances.h are one); report: a dict that receives the launches and their kernels."""
     import uav_motion_planning_amd as U
     plan, choose = host_rules
+    has_group8 = HAS_GROUP8[(r, M)] if has_group8 is None else has_group8
+    has_group = has_group8 if has_group is None else has_group
     captured = []
 
     def enqueue(c, b):
@@ -126,17 +130,19 @@ def _rotation(ctx, host_rules, r, M, n, lanes, F, solves, sets):
     for g, k in zip(launches, kernels):
         if len(g) == 1:
             assert k == AS_CAPTURED
-        elif n % 8 == 0 and HAS_GROUP8[(r, M)]:
+        elif n % 8 == 0 and has_group8:
             assert k == EIGHT_PER_WAVE
         else:
             assert k == OWN_TILE                                   # n = 12: the 16-lane group kernel, as before
-    if not HAS_GROUP8[(r, M)]:
+    if report is not None:
+        report.update(launches=launches, kernels=kernels)
+    if not has_group:
         assert all(len(g) == 1 for g in launches)
     elif lanes == 1:
         assert max(len(g) for g in launches) == min(F, sets, solves)   # a lane meets a set again after `sets` solves
-        assert (EIGHT_PER_WAVE in kernels) == (n % 8 == 0)              # the replay checked above ran the new kernel / did not
+        assert (EIGHT_PER_WAVE in kernels) == (n % 8 == 0 and has_group8)   # the replay checked above ran the new kernel / did not
     elif solves > lanes:
-        assert max(len(g) for g in launches) >= 2 and (EIGHT_PER_WAVE in kernels) == (n % 8 == 0)
+        assert max(len(g) for g in launches) >= 2 and (EIGHT_PER_WAVE in kernels) == (n % 8 == 0 and has_group8)
     # the invalid durations of set 0 show in set 0's statuses and nowhere else; their trajectories' rows are the only ones never written
     per_traj = 3 * 2 * r * M
     bad = [t for t, _ in _bad(n, M)]
