@@ -47,8 +47,9 @@
 #define UAVQP_INSTANCES_TWISTED3_GROUP UAVQP_GROUP_PAIRS3_T4(UAVQP_TWISTED_GROUP_T4) UAVQP_GROUP_PAIRS3_T8(UAVQP_TWISTED_GROUP_T8)
 #define UAVQP_INSTANCES_TWISTED4_GROUP UAVQP_GROUP_PAIRS4_T4(UAVQP_TWISTED_GROUP_T4) UAVQP_GROUP_PAIRS4_T8(UAVQP_TWISTED_GROUP_T8)
 // and the group of tile-4 solves with eight trajectories per wave (solve_twisted_group8_kernel; k_twisted3_group8.hip / k_twisted4_group8.hip):
-// every shape of the tile-4 group lists -- all of them compile without scratch and fit two waves to a SIMD (at most 256 VGPRs;
-// tests/test_twisted_group8_resources.py reads the counts from a cross-compile, docs/measurement_log.md tables them).
+// every shape of the tile-4 group lists -- all of them compile without scratch and fit THREE waves to a SIMD (at most 168 VGPRs, at
+// most a twelfth of a CU's LDS; tests/test_twisted_group8_three_waves.py reads the counts from a cross-compile, docs/measurement_log.md
+// tables them).
 #define UAVQP_GROUP8_PAIRS4(X) UAVQP_GROUP_PAIRS4_T4(X)
 #define UAVQP_GROUP8_PAIRS3(X) UAVQP_GROUP_PAIRS3_T4(X)
 #define UAVQP_TWISTED_GROUP8(R_, M_) UAVQP_INST __global__ void uavqp::solve_twisted_group8_kernel<R_, M_>(UAVQP_TWISTED_GROUP8_SIG);

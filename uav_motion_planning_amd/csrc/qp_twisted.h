@@ -66,7 +66,16 @@ struct TwistedCfg {
     static constexpr int OUT_D = LPT >= 8 ? (ROWS8 + 16) * RS8 + 16 : ((LPT == 2 && !ALIAS) ? STAGE_D : 2);
     // solve_twisted_group8_kernel (eight trajectories per wave, both segments of a step per lane pair): six blocks of 16 rows and 16 rows
     // behind them for the writes of the idle pairs, laid out by qp_twisted_map8.h.
-    static constexpr int OUT2_D = TWMAP8_STAGE_DOUBLES;
+    // Three waves per SIMD are twelve workgroups per CU, nominally a twelfth of its 160 KiB of LDS each.  Where the input tile and the
+    // whole staging area are more than that ((3, 16) alone: 14336 bytes) the idle pairs do not write and their 16 rows are not allocated
+    // (13056 bytes): the six blocks end below TWMAP8_IDLE_BASE, and every other shape keeps its unpredicated writes.
+    // NOMINALLY: the figure counts bytes as declared.  The granule in which the hardware allocates LDS to a workgroup was not
+    // established here; if it is the 1280 bytes (320 dwords) that 160 KiB over a 7-bit block count suggest, 13056 and (3, 12)'s 13312
+    // both round to 14080 and a CU holds eleven such workgroups (ten of 14336), twelve only up to 12800 bytes -- (4, 8) has 12672.
+    // What this case buys (3, 16) is then the eleventh workgroup, not the twelfth; no timing tells the two apart (measurement log).
+    static constexpr bool IDLE_ROWS2 = (IN_D + TWMAP8_STAGE_DOUBLES) * 8 * 12 <= 160 * 1024;
+    static constexpr int OUT2_D = IDLE_ROWS2 ? TWMAP8_STAGE_DOUBLES : TWMAP8_IDLE_BASE;
+    static_assert(twmap8_row_addr(TWMAP8_PIECES - 1, 15) + TWMAP8_ROW_STRIDE <= TWMAP8_IDLE_BASE, "the blocks end in front of the idle rows");
     static_assert(RS8 == TWMAP8_ROW_STRIDE, "one row stride for the latency shapes");
     static_assert(!ALIAS || STAGE_D <= IN_D, "aliased staging rows must fit the input buffer");
     static_assert(WP_D % 2 == 0 && T_D % 2 == 0 && BC_D % 2 == 0, "tile arrays must be whole 16-B pairs");
@@ -154,6 +163,12 @@ __global__ __launch_bounds__(64, 1) void solve_twisted_group_kernel(const Twiste
 // shape's arithmetic (qp_twisted_body.h, EMIT2: segment_coeffs on the reloaded duration, not the 8-lane shape's kept inverse powers):
 // per (trajectory, axis, side, segment) the operations of solve_twisted_kernel<R, M, 4, 16, true>, so a replay stays bitwise equal to
 // eager order.  Grid (n_traj / 8, members), block 64; the copy-out map is qp_twisted_map8.h.
+// Every instantiation fits three waves per SIMD -- at most 168 VGPRs, no scratch, in declared bytes at most a twelfth of a CU's LDS
+// (tests/test_twisted_group8_three_waves.py; TwistedCfg::IDLE_ROWS2 on the allocation granule) -- since the copy-out decode starts from an opaque copy of the lane index and is computed
+// behind the elimination instead of being hoisted in front of the load wait (qp_twisted_body.h, EMIT2).  VGPRs, waves per SIMD:
+//   r = 4:  M = 2  62, 4   3  130, 3   4  98, 4   5  152, 3   6  126, 4   8  156, 3                        (before: 6  156, 3   8  182, 2)
+//   r = 3:  M = 2  52, 4   3  86, 4   4  66, 4   5  97, 4   6  84, 4   7  108, 4   8  96, 4   10  110, 3 and 12  124, 3 (by LDS)   16  154, 3
+//                                                                                                          (before: 16  226, 2)
 #define UAVQP_TWISTED_GROUP8_SIG const uavqp::TwistedGroupArgs
 template <int R, int M>
 __global__ __launch_bounds__(64, 1) void solve_twisted_group8_kernel(const TwistedGroupArgs group) {

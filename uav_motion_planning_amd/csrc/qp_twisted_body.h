@@ -333,7 +333,15 @@
             // not depend on the step or the block is computed once in front of the loop; twmap8_piece() is the same composition as ONE
             // function, and it is that function the CPU test walks -- the kernel's own composition (c_off + (axis * M + segment) * NC * 8,
             // keep) is covered by the bitwise GPU tests only (tests/test_gpu_twisted_group8.py).  Keep the two in step.
-            const int c_rest = lane >> 2, c_col = lane & 3;
+            // The decode starts from an OPAQUE copy of the lane index.  It depends on the lane alone, so with the hidden trip count
+            // (one_trip above) all of it -- a dozen dwords per lane: the keeps, the offsets, the row slot -- was hoisted in front of
+            // the load wait and stayed live across the whole elimination, where the register peak is: 182 VGPRs for (4, 8), 226 for
+            // (3, 16), two waves per SIMD.  A fused launch fills its SIMDs, so what counts is how many waves fit, not what one wave
+            // has in front of its wait: behind the elimination the same values cost ~25 instructions and no register at the peak
+            // (156 / 154 VGPRs: three waves; docs/measurement_log.md, 2026-10-21).  The eager kernels keep their hoisted set-up.
+            int lane_e = lane;
+            asm volatile("" : "+v"(lane_e));
+            const int c_rest = lane_e >> 2, c_col = lane_e & 3;
             const int c_R = twmap_rest_side<2>(c_rest), c_sub = twmap_rest_sub<2>(c_rest), c_tl4 = twmap_rest_traj<2>(c_rest);
             const int c_m = c_R ? mR : mL;
             bool c_keep[2];
@@ -345,12 +353,12 @@
                 c_off[hf] = (unsigned)(((c_tl * 3 * M) * NC + 2 * c_col) * 8);
             }
             const int c_lds = c_rest * RS + 2 * c_col;
-            // own rows: one per sub; the idle pairs write behind the blocks
+            // own rows: one per sub; the idle pairs write behind the blocks (or, where those rows are not allocated, not at all)
             int my_lds[2];
 #pragma unroll
             for (int sb = 0; sb < 2; ++sb)
                 my_lds[sb] = axl < 3 ? row_addr(twmap8_block(tlc, axl), twmap8_rest(tlc, sb, isR))
-                                     : twmap8_idle_addr((lane >> 3) * 2 + isR);
+                                     : (C::IDLE_ROWS2 ? twmap8_idle_addr((lane >> 3) * 2 + isR) : 0);
             auto flush = [&](int sp) {   // copy-out of step sp: NIT LDS reads, NIT stores
                 // (every row is read, also one nobody wrote in this step: where 2 sp + 1 == mL the sub-1 rows hold the previous step's
                 //  chunks -- or, for M = 2, whatever LDS held at wave start.  Those pieces are never stored: jv < c_m below is false for
@@ -409,8 +417,9 @@
                 }
 #pragma unroll
                 for (int sb = 0; sb < 2; ++sb) {
-                    if (twmap_own_segment<2>(s, sb) < mL) {
-                        // (idle pairs and lanes without a segment in this sub-step write too -- rows / chunks that are never copied out)
+                    if (twmap_own_segment<2>(s, sb) < mL && (C::IDLE_ROWS2 || axl < 3)) {
+                        // (lanes without a segment in this sub-step write too, and so do the idle pairs where their rows exist
+                        //  (C::IDLE_ROWS2) -- rows / chunks that are never copied out; where they do not exist the idle pairs are masked off)
                         double* so = s_out + my_lds[sb];
 #pragma unroll
                         for (int k = 0; k < NC; k += 2) *reinterpret_cast<double2*>(so + k) = make_double2(c8[sb][k], c8[sb][k + 1]);

@@ -36,7 +36,8 @@ UAVQP_MAP_HD constexpr int twmap8_row(int tl, int axis, int side, int sub) { ret
 // lanes are two trajectories of one half x three axes x two sides; their rows of one sub start 0 / 4 quads (trajectory) + 0 / 15 (sub 0)
 // or 0 / 5 (sub 1) quads (side) apart, modulo the 16 quads of the 64 banks, so with the blocks of the three axes shifted by 0 / 2 / 8
 // quads the twelve b128 writes start in twelve different bank quads.  The second half lies 10 quads further on; every block starts
-// clear of the last row of the block in front, and the 16 rows behind the blocks take the writes of the idle lane pairs.
+// clear of the last row of the block in front, and the 16 rows behind the blocks take the writes of the idle lane pairs
+// (a kernel whose idle pairs do not write allocates TWMAP8_IDLE_BASE doubles only: qp_twisted.h, TwistedCfg::IDLE_ROWS2).
 static constexpr int TWMAP8_ROW_STRIDE = 10, TWMAP8_ROW_DOUBLES = 8;
 UAVQP_MAP_HD constexpr int twmap8_block_base(int block) {
     return block * 16 * TWMAP8_ROW_STRIDE + twmap8_block_half(block) * 20 + (twmap8_block_axis(block) == 0 ? 0 : (twmap8_block_axis(block) == 1 ? 4 : 16));

@@ -792,11 +792,11 @@ struct CapturedGraph {
 // uavqp_solve_batch_device, when nothing in it is independent, or when the runtime refuses a step: the caller keeps the captured graph.
 // Within a lane, solves of one shape that follow each other and touch disjoint buffers become ONE launch of the group kernel
 // (uavqp_capture.h: fuse_groups; qp_twisted.h: solve_twisted_group_kernel) -- also where the replay stays on one lane: up to `fuse` of
-// them where that names a count (1..8), and with `fuse` 0 as many as `fuse_waves` waves per launch hold in the kernel their group runs
-// (uavqp_capture.h: fuse_cap, member_waves).
+// them where that names a count (1..8), and with `fuse` 0 as many as a budget of waves per launch holds in the kernel their group runs:
+// `fuse_waves_named` where UAVQP_CAPTURE_FUSE_WAVES names one, else that kernel's own default (uavqp_capture.h: group_cap, fuse_budget, fuse_cap, member_waves).
 // (Measured: ONE graph with parallel branches replays slower than the captured chain -- the runtime leaves its single-queue fast path --
 //  so every lane of a stage is a chain graph of its own: docs/measurement_log.md.)
-static bool rebuild_captured(uavqp_ctx* ctx, hipGraph_t captured, int lanes, int nodes_per_lane, int fuse, int fuse_waves, CapturedGraph& out) {
+static bool rebuild_captured(uavqp_ctx* ctx, hipGraph_t captured, int lanes, int nodes_per_lane, int fuse, int fuse_waves_named, CapturedGraph& out) {
     static_assert(uavqp::GROUP_MAX == uavqp_capture::FUSE_MAX, "a group's pointer sets travel in one kernarg struct");
     const size_t n = ctx->cap_launch.size();
     if (lanes < 1) lanes = 1;
@@ -814,7 +814,7 @@ static bool rebuild_captured(uavqp_ctx* ctx, hipGraph_t captured, int lanes, int
         uavqp_capture::Shape& sh = shape[k];
         sh.fn = l.fn; sh.grid = l.grid.x; sh.block = l.block.x; sh.lds_bytes = l.lds_bytes; sh.n_traj = l.args.n_traj;
         sh.one = l.fn && l.group_fn && l.grid.y == 1 && l.grid.z == 1;   // (one kernel function: one group kernel)
-        if (fuse < 1) cap[k] = uavqp_capture::fuse_cap(fuse_waves, uavqp_capture::member_waves(l.tile, sh.one, sh.n_traj, sh.grid, l.group8_fn != nullptr));
+        if (fuse < 1) cap[k] = uavqp_capture::group_cap(fuse, fuse_waves_named, l.tile, sh.one, sh.n_traj, sh.grid, l.group8_fn != nullptr);
     }
     if (n > uavqp_capture::NODES_MAX) return false;
     const std::vector<char> status_dead = uavqp_capture::dead_status_stores(ctx->cap_rec);
@@ -896,12 +896,12 @@ extern "C" int uavqp_capture_end(uavqp_ctx* ctx, void** out_graph_exec) {
     // UAVQP_CAPTURE_LANES = 1..8 (A/B runs; 1 = replay the chain as captured; not set: 2, uavqp_capture.h: REPLAY_LANES_DEFAULT).  GPU_MAX_HW_QUEUES is only read: a process given fewer
     // than 4 hardware queues keeps the chain.  UAVQP_CAPTURE_LANE_NODES: the launches a stage must have per lane (default 16).
     // UAVQP_CAPTURE_FUSE = 1..8: the most independent solves of one shape a launch of the replay carries, for every group (1 = one launch per solve; uavqp_capture.h: fuse_groups).
-    // Not set: as many as UAVQP_CAPTURE_FUSE_WAVES (a positive integer; default FUSE_WAVES_DEFAULT) waves per launch hold in the kernel the group runs, 2 to 8 (uavqp_capture.h: fuse_cap).
+    // Not set: as many as UAVQP_CAPTURE_FUSE_WAVES (a positive integer, for every kernel; not set: FUSE_WAVES_EIGHT_PER_WAVE_DEFAULT for the eight-per-wave kernel, FUSE_WAVES_DEFAULT for every other) waves per launch hold in the kernel the group runs, 2 to 8 (uavqp_capture.h: group_cap).
     const uavqp_capture::Knobs knobs = uavqp_capture::knobs_from_environment();
     const int lanes = ctx->capturing ? knobs.lanes : 1;
     CapturedGraph* cg = new (std::nothrow) CapturedGraph();
     if (!cg) { (void)hipGraphDestroy(graph); return UAVQP_ERR_ALLOC; }
-    if (!rebuild_captured(ctx, graph, lanes, knobs.nodes_per_lane, ctx->capturing ? knobs.fuse_named : 1, knobs.fuse_waves, *cg)) {
+    if (!rebuild_captured(ctx, graph, lanes, knobs.nodes_per_lane, ctx->capturing ? knobs.fuse_named : 1, knobs.fuse_waves_named, *cg)) {
         (void)hipGetLastError();
         delete cg;
         cg = new (std::nothrow) CapturedGraph();

@@ -6,7 +6,7 @@
 // (lane of node k: k % lanes), kept with their results as the reference the conflict rules are pinned against.
 // fuse_groups then cuts every lane into groups of independent solves of one shape, each replayed as ONE launch.
 // Host-only: byte ranges and indices, no HIP type -- compiles without the runtime (tests/cpp/test_capture_deps.cpp, test_capture_lanes.cpp,
-// test_capture_fuse.cpp, test_capture_fuse_waves.cpp).
+// test_capture_fuse.cpp, test_capture_fuse_waves.cpp, test_capture_kernel_budget.cpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -246,7 +246,7 @@ static inline int replay_lanes_from_env(const char* lanes_env, const char* hw_qu
 // ---- Groups: independent solves of one shape that follow each other in a lane are replayed as ONE launch (qp_twisted.h:
 // solve_twisted_group_kernel, grid (n_tiles, members)).  A replayed small-batch solve is bound by its launch -- the kernel boundary and the
 // dispatch ramp of its grid cost more than its waves live (docs/measurement_log.md, 2026-10-20) -- so a lane pays one boundary per group
-// instead of one per solve, and the waves of up to three members share a SIMD.  fuse_groups runs AFTER lay_out and changes nothing of it.
+// instead of one per solve, and the waves of several members share a SIMD (at least three of the eight-per-wave kernel: qp_twisted.h).  fuse_groups runs AFTER lay_out and changes nothing of it.
 //
 // What a launch is, as far as grouping goes: two launches with equal keys run the same kernel over grids of the same shape.
 struct Shape {
@@ -260,7 +260,8 @@ static inline bool same_shape(const Shape& a, const Shape& b) {
 }
 // UAVQP_CAPTURE_FUSE (1..8): the most solves one launch of a replay carries, for every group; 1 = every solve its own launch.
 // Not set (or anything else): the cap of a group follows from a BUDGET OF WAVES per launch, UAVQP_CAPTURE_FUSE_WAVES (a positive
-// integer, anything else: FUSE_WAVES_DEFAULT), and from the waves one member adds in the kernel the group will run (member_waves):
+// integer, for every kernel; anything else: the default of the kernel the group will run -- FUSE_WAVES_EIGHT_PER_WAVE_DEFAULT for the
+// eight-per-wave kernel, FUSE_WAVES_DEFAULT for every other: fuse_budget), and from the waves one member adds in that kernel (member_waves):
 //   fuse_cap = min(FUSE_MAX, max(FUSE_DEFAULT, budget / waves per member)).
 // Why waves and not solves.  More members per launch replay faster at 200 and at 20 steps, but launches of 4096 and 8192 waves from two
 // lanes compete for the wave slots, and then a two-lane replay depends on which hardware queues the runtime gave the two streams: with
@@ -279,6 +280,12 @@ static inline bool same_shape(const Shape& a, const Shape& b) {
 static constexpr int FUSE_MAX = 8;             // == uavqp::GROUP_MAX (qp_twisted.h): the pointer sets one kernarg struct holds
 static constexpr int FUSE_DEFAULT = 2;
 static constexpr int FUSE_WAVES_DEFAULT = 2048;
+// The eight-per-wave kernel has a default budget of its own, used where UAVQP_CAPTURE_FUSE_WAVES names none (fuse_budget): the
+// placement dependence that holds FUSE_WAVES_DEFAULT at 2048 was the 16-lane group kernel's.  Measured on MI355X among 2048, 3072 and
+// 4096 on the kernel that fits three waves per SIMD, it stays 2048: all three were inside the plain / communication-library / plain
+// bound, 4096 was 2 % ahead on the headline shape (less than the run-to-run range) and made 4096 x (r = 3, M = 16) 8-18 % slower.
+// Triples, runs and the shapes taken apart: docs/measurement_log.md, 2026-10-21, the entry on three waves per SIMD.
+static constexpr int FUSE_WAVES_EIGHT_PER_WAVE_DEFAULT = 2048;
 static inline int fuse_from_env(const char* env) {
     const int v = env && *env ? std::atoi(env) : 0;
     return v >= 1 && v <= FUSE_MAX ? v : FUSE_DEFAULT;
@@ -288,11 +295,17 @@ static inline int fuse_named_from_env(const char* env) {
     const int v = env && *env ? std::atoi(env) : 0;
     return v >= 1 && v <= FUSE_MAX ? v : 0;
 }
-static inline int fuse_waves_from_env(const char* env) {
-    if (!env || !*env) return FUSE_WAVES_DEFAULT;
+// The budget UAVQP_CAPTURE_FUSE_WAVES names (a positive integer that fits an int, nothing before or behind it), or 0 where it names
+// none and every kernel has the default of its own (fuse_budget, below).
+static inline int fuse_waves_named_from_env(const char* env) {
+    if (!env || !*env) return 0;
     char* end = nullptr;
     const long long v = std::strtoll(env, &end, 10);   // (saturates on overflow: out of range below)
-    return *end == '\0' && env[0] >= '0' && env[0] <= '9' && v >= 1 && v <= 2147483647LL ? (int)v : FUSE_WAVES_DEFAULT;
+    return *end == '\0' && env[0] >= '0' && env[0] <= '9' && v >= 1 && v <= 2147483647LL ? (int)v : 0;
+}
+static inline int fuse_waves_from_env(const char* env) {
+    const int v = fuse_waves_named_from_env(env);
+    return v ? v : FUSE_WAVES_DEFAULT;
 }
 static inline int fuse_cap(int budget, int waves_per_member) {
     if (budget <= 0 || waves_per_member <= 0) return FUSE_DEFAULT;
@@ -377,12 +390,26 @@ static inline int member_waves(int tile, bool one, int n_traj, unsigned grid, bo
     return group_kernel_choice(FUSE_DEFAULT, tile, one, n_traj, has_group8) == GROUP_EIGHT_PER_WAVE ? n_traj / 8 : (int)grid;
 }
 
+// The budget of waves a group of launches of this shape is cut by: the one UAVQP_CAPTURE_FUSE_WAVES names (`waves_named` > 0:
+// fuse_waves_named_from_env), for every kernel; where it names none, the default of the kernel the group runs.
+static inline int fuse_budget(int waves_named, int tile, bool one, int n_traj, bool has_group8) {
+    if (waves_named > 0) return waves_named;
+    return group_kernel_choice(FUSE_DEFAULT, tile, one, n_traj, has_group8) == GROUP_EIGHT_PER_WAVE ? FUSE_WAVES_EIGHT_PER_WAVE_DEFAULT : FUSE_WAVES_DEFAULT;
+}
+// The cap of a group whose first member is a launch of this shape, as rebuild_captured gives it to fuse_groups: the count
+// UAVQP_CAPTURE_FUSE names (`fuse_named` 1..8) overrides everything; otherwise the budget over the waves of a member.
+static inline int group_cap(int fuse_named, int waves_named, int tile, bool one, int n_traj, unsigned grid, bool has_group8) {
+    if (fuse_named >= 1) return fuse_named < FUSE_MAX ? fuse_named : FUSE_MAX;
+    return fuse_cap(fuse_budget(waves_named, tile, one, n_traj, has_group8), member_waves(tile, one, n_traj, grid, has_group8));
+}
+
 // The knobs as the process environment has them NOW: read when a capture ends (uavqp_capture_end), never on a launch path.
-// fuse_named: the count UAVQP_CAPTURE_FUSE names, 0 where the budget fuse_waves decides (fuse_named_from_env).
-struct Knobs { int lanes, nodes_per_lane, fuse_named, fuse_waves; };
+// fuse_named: the count UAVQP_CAPTURE_FUSE names, 0 where a budget of waves decides (fuse_named_from_env).
+// fuse_waves_named: the budget UAVQP_CAPTURE_FUSE_WAVES names, 0 where every kernel has its own default (fuse_waves_named_from_env).
+struct Knobs { int lanes, nodes_per_lane, fuse_named, fuse_waves_named; };
 static inline Knobs knobs_from_environment() {
     return Knobs{replay_lanes_from_env(std::getenv("UAVQP_CAPTURE_LANES"), std::getenv("GPU_MAX_HW_QUEUES")), lane_nodes_from_env(std::getenv("UAVQP_CAPTURE_LANE_NODES")),
-                 fuse_named_from_env(std::getenv("UAVQP_CAPTURE_FUSE")), fuse_waves_from_env(std::getenv("UAVQP_CAPTURE_FUSE_WAVES"))};
+                 fuse_named_from_env(std::getenv("UAVQP_CAPTURE_FUSE")), fuse_waves_named_from_env(std::getenv("UAVQP_CAPTURE_FUSE_WAVES"))};
 }
 
 }  // namespace uavqp_capture
