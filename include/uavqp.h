@@ -1076,7 +1076,8 @@ int uavqp_clearance_certificate_host(uavqp_ctx* ctx, int r, int n_traj, int unif
  * offsets with n_groups != 1; from the _host entry also group offsets that do not ascend from 0 to n_traj or a swarm larger than
  * UAVQP_SWARM_MAX_VEHICLES.
  * The optimiser that uses the penalty (one accept / reject per SWARM): uavqp_swarm_optimize_device below.
- * Out of scope: moving or non-cooperative obstacles, a swarm sharded over several GPUs. */
+ * Out of scope: a swarm sharded over several GPUs.  Moving or non-cooperative obstacles (trajectories that are not this batch's to move)
+ * are the business of uavqp_moving_penalty_device below. */
 #define UAVQP_SWARM_MAX_VEHICLES 128
 typedef struct uavqp_swarm_params {
     int32_t struct_size;
@@ -1164,7 +1165,8 @@ int uavqp_swarm_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segm
  * uavqp_ellipsoid_check_* (collisions); separation is reported by d_min_sep_out on the swarm's clock samples only.
  * Between the samples it is BOUNDED by uavqp_separation_certificate_* below, the hard test of the separation.
  * Out of scope: quasi-Newton directions per swarm, capture into a graph, corridor and general-rows solves, a swarm sharded over several
- * GPUs. */
+ * GPUs.  Moving or non-cooperative obstacles: uavqp_moving_optimize_device below replans ONE vehicle at a time against the tracks of
+ * the others, the decentralised counterpart of this entry. */
 typedef struct uavqp_swarm_opt_params {
     int32_t struct_size;
     int32_t max_iters;          /* trials per swarm (default 32) */
@@ -1250,7 +1252,10 @@ int uavqp_swarm_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_seg
  * without offsets, n_groups < 0, NULL group offsets with n_groups != 1; from the _host entry also group offsets that do not ascend from 0
  * to n_traj or a swarm larger than UAVQP_SWARM_MAX_VEHICLES.
  * Out of scope: splitting a straddling leaf at the pair's merged knots (without it a straddling leaf falls back to boxes); a degree-2n
- * squared-distance polynomial per pair; adaptive subdivision; non-cooperative obstacles; wiring the verdict into uavqp_swarm_optimize_*. */
+ * squared-distance polynomial per pair; adaptive subdivision; non-cooperative obstacles; wiring the verdict into uavqp_swarm_optimize_*.
+ * Against obstacle tracks (uavqp_moving_penalty_device below) there is no certificate of its own yet: until there is, this entry on a batch
+ * that concatenates a vehicle with its obstacle tracks as ONE group bounds the vehicle's separation from them for every t; it takes no
+ * radii into account. */
 #define UAVQP_SEPARATION_CERTIFIED 1   /* lower >= d_req: holds for ALL t of the window */
 #define UAVQP_SEPARATION_VIOLATED 2    /* upper <  d_req: broken at the witness */
 #define UAVQP_SEPARATION_MOVING 4      /* still under way at the end of the window */
@@ -1274,6 +1279,126 @@ int uavqp_separation_certificate_host(uavqp_ctx* ctx, int r, int n_traj, int uni
                                       const double* coeff, const int32_t* status, int n_groups, const int32_t* group_offsets,
                                       const double* start, const uavqp_separation_params* params, double* lower, double* upper,
                                       int32_t* where, int32_t* verdict, int32_t* group_verdict);
+
+/* Moving-obstacle penalty: a trajectory against obstacles that MOVE and are not this batch's to move -- the committed trajectories the
+ * other vehicles of a decentralised fleet have broadcast, a predicted pedestrian, another aircraft (no reference counterpart; the term is
+ * that of EGO-Swarm, where each vehicle replans on its own against the trajectories of the others).  The shape of
+ * uavqp_attitude_penalty_device, with its gradients in the coefficients, the durations and the departure.
+ * Obstacle tracks.  An obstacle is a trajectory in the library's own format: the SAME r as the batch, coefficients in the layout of coeff,
+ * durations, and a start on the clock.  A committed trajectory is handed over as it is; a constant-velocity or constant-acceleration
+ * prediction is a one-segment track whose higher coefficients are zero.  uavqp_moving_obstacles describes them; its pointers are device
+ * pointers for the _device entries and host pointers for the _host entries:
+ *   n_obs, uniform_segments, seg_offsets, times, coeff   the obstacle batch, described as a trajectory batch is everywhere else
+ *   start  [n_obs] the departure of each obstacle on the clock (NULL: zeros);  radius [n_obs] finite, >= 0 (NULL: zeros)
+ *   n_sets, set_offsets [n_sets + 1] int32 ascending from 0 to n_obs: set k is the obstacles [so[k], so[k+1]); no cap on a set's size, an
+ *          empty set is allowed.  set_offsets NULL with n_sets == 1: the whole obstacle batch is set 0.
+ *   traj_set [n_traj] int32: the set trajectory b avoids, -1 for none; NULL with n_sets == 1: every trajectory avoids set 0
+ *   traj_start [n_traj]: the departure of each trajectory of the batch on the same clock (NULL: zeros)
+ * Offsets and traj_set are trusted on the device, as d_seg_offsets is; the _host entries validate that the set offsets ascend from 0 to
+ * n_obs, that traj_set lies in [-1, n_sets), the radii, and the CSR offsets of the obstacle batch.
+ * Samples.  For trajectory b with departure S = traj_start[b]: the clock knots are the DOUBLES K_0 = S, K_{m+1} = fl(K_m + T_m) (the
+ * convention of uavqp_separation_certificate_device); sample s = 0..K of segment m is at local time t = tau_s T_m, tau_s = s / K,
+ * K = samples_per_seg, at clock time t_abs = fma(tau_s, T_m, K_m); the trapezoid weights om_s are those of uavqp_limit_penalty_device.
+ * Obstacle o at t_abs: exactly the position rule of uavqp_swarm_penalty_device at u = t_abs - start_o (u < 0: it waits, segment 0 at local
+ * time 0; otherwise the segment rule of uavqp_eval_batch_device; arrived: last segment at T_{M-1}, with the cap on the last segment).  Its
+ * velocity o'(t_abs) is that of the located segment, and zero while the obstacle is held (waiting or arrived).
+ * Term.  delta = q(t) - o(t_abs), D_o = d_safe + radius_o, rho2 = (dx^2 + dy^2 + (dz / downwash)^2) / D_o^2, x_o = max(0, 1 - rho2):
+ *       phi = weight sum_{o in set} x_o^3                     Phi = sum_m (T_m / K) sum_s om_s phi
+ *       e_o = -6 weight x_o^2 / D_o^2 diag(1, 1, 1 / downwash^2) delta
+ *       G   = sum_o e_o                    (dphi/dq)
+ *       Gt  = -sum_o e_o . o'(t_abs)       (dphi/dt_abs)
+ *       Q_m = sum_s om_s Gt
+ *   d_penalty     [n_traj] Phi
+ *   d_grad_coeff  layout of coeff: grad_coeff[axis][m][n] = (T_m / K) sum_s om_s G[axis] t^n, at FIXED durations
+ *   d_grad_times  [sum_b M_b]: the EXPLICIT dPhi/dT_l at FIXED coefficients
+ *                 = Phi_l / T_l + (T_l / K) sum_s om_s tau_s (G . v(t) + Gt) + sum_{m > l} (T_m / K) Q_m
+ *                 (the last term is what no other penalty has: a later segment's samples move on the clock with every earlier duration)
+ *   d_grad_start  [n_traj]: dPhi/dS = sum_m (T_m / K) Q_m -- already the total gradient, the coefficients do not depend on the departure
+ *   d_min_gap     [n_traj]: the smallest sqrt(dx^2 + dy^2 + (dz / downwash)^2) - radius_o over the samples and the obstacles of the set;
+ *                 INFINITY for a trajectory without an obstacle
+ *   d_nearest     [n_traj] int32: the index in the obstacle batch of the obstacle that attains d_min_gap, -1 when there is none; a tie
+ *                 goes to the smaller index
+ * Each output may be NULL (all NULL: UAVQP_OK, nothing done).  As with every other penalty the TOTAL gradients in durations, waypoints and
+ * boundary derivatives are d_grad_times + uavqp_solve_backward_device(g = d_grad_coeff).
+ * A trajectory that is not UAVQP_SOLVED (d_status NULL: all are), has M < 1, has set -1 or an empty set gets zeros, INFINITY and -1.
+ * weight == 0: zeros, d_min_gap and d_nearest still reported.  Every output element is written exactly once, zeros included.  No
+ * floating-point atomics; the order of every addition is fixed by sample, obstacle and segment indices alone (the sum over later segments
+ * runs from the LAST segment down): the same bytes run to run, for any grid, and for a trajectory alone or in the middle of a batch.
+ * One launch, asynchronous on the ctx stream, no allocation, no workspace, no read-back.
+ * WHAT THE RESULT IS: a SOFT penalty on SAMPLES.  d_min_gap is the check afterwards, on the samples only; between them nothing is bounded
+ * (a certificate against obstacle tracks: see the note at uavqp_separation_certificate_device).  The obstacle's position is not smooth in
+ * t_abs where it departs or arrives with a non-zero velocity; the gradient is that of the piece the sample lies in.
+ * UAVQP_ERR_INVALID_ARG: r not 3 / 4, a negative count, a wrong struct_size of either struct, samples_per_seg < 1, d_safe not finite or
+ * <= 0, downwash not finite or < 1, weight not finite or < 0, NULL times / coeff, ragged without offsets, NULL obstacles, n_obs < 0, a
+ * negative uniform_segments of the obstacles, NULL obstacle times / coeff with n_obs > 0, ragged obstacles without offsets, n_sets < 0,
+ * NULL set_offsets or NULL traj_set with n_sets != 1; from the _host entry also set offsets that do not ascend from 0 to n_obs, a traj_set
+ * outside [-1, n_sets), a radius that is negative or not finite, obstacle offsets that do not ascend from 0.
+ * Out of scope: departures as optimisation variables, obstacles that appear or vanish inside a window, a per-obstacle cull, a
+ * certificate of its own, wiring into uavqp_swarm_optimize_* or the corridor pipeline. */
+typedef struct uavqp_moving_params {
+    int32_t struct_size;
+    int32_t samples_per_seg;   /* K: K + 1 sample points per segment (default 8) */
+    double d_safe;             /* m: gap to an obstacle's surface below which it is penalised, finite, > 0 (default 1.0) */
+    double downwash;           /* >= 1: vertical separations count divided by this (default 1.0) */
+    double weight;             /* >= 0 (default 1e3) */
+} uavqp_moving_params;
+typedef struct uavqp_moving_obstacles {
+    int32_t struct_size;
+    int32_t n_obs;
+    int32_t uniform_segments;      /* of the obstacle batch; 0: ragged, seg_offsets [n_obs + 1] */
+    int32_t n_sets;
+    const int32_t* seg_offsets;
+    const double* times;
+    const double* coeff;
+    const double* start;           /* [n_obs] or NULL: zeros */
+    const double* radius;          /* [n_obs] or NULL: zeros */
+    const int32_t* set_offsets;    /* [n_sets + 1], or NULL with n_sets == 1 */
+    const int32_t* traj_set;       /* [n_traj], or NULL with n_sets == 1 */
+    const double* traj_start;      /* [n_traj] or NULL: zeros */
+} uavqp_moving_obstacles;
+void uavqp_default_moving_params(uavqp_moving_params* out);   /* callable without a device */
+int uavqp_moving_penalty_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
+                                const double* d_coeff, const int32_t* d_status, const uavqp_moving_obstacles* obstacles,
+                                const uavqp_moving_params* params, double* d_penalty, double* d_grad_coeff, double* d_grad_times,
+                                double* d_grad_start, double* d_min_gap, int32_t* d_nearest);
+/* The same from HOST pointers, those inside `obstacles` included (H2D copy, run, D2H copy, synchronous). */
+int uavqp_moving_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
+                              const double* coeff, const int32_t* status, const uavqp_moving_obstacles* obstacles,
+                              const uavqp_moving_params* params, double* penalty, double* grad_coeff, double* grad_times, double* grad_start,
+                              double* min_gap, int32_t* nearest);
+
+/* uavqp_attitude_optimize_device with the moving-obstacle penalty inside the objective: per trajectory
+ *       minimise  f(p, T) = [the objective of uavqp_attitude_optimize_device] + Phi_moving(c*(p, T), T)
+ * Phi_moving exactly the formula of uavqp_moving_penalty_device with `obstacles` and `moving`.  Variables, bounds, directions, the ONE
+ * accept / reject per trajectory and trial, the arguments, the outputs and the parameters are those of uavqp_attitude_optimize_device;
+ * `attitude` may be NULL here: no attitude term (d_attitude_peak_out is then not written).  Departures (traj_start) are FIXED.
+ * Sequencing: one more accumulating launch per trial, behind the attitude launch and before the ONE backward pass -- at most six
+ * launches per trial, none that depends on the data, nothing read back.  d_objective_out holds f INCLUDING Phi_moving.  With
+ * moving->weight == 0, or no trajectory that can have an obstacle (n_obs == 0 or n_sets == 0), that launch is skipped and every shared
+ * output equals uavqp_attitude_optimize_device byte for byte -- with attitude NULL as well, uavqp_spacetime_lbfgs_device.
+ *   d_min_gap_out [n_traj], d_nearest_out [n_traj] int32 (each may be NULL): d_min_gap / d_nearest of uavqp_moving_penalty_device at what
+ *                 is handed back
+ * WHAT THE RESULT IS: as for uavqp_spacetime_lbfgs_device, a local minimum of a piecewise smooth f with soft penalties; d_min_gap_out says
+ * how close the result still comes, on the samples.
+ * UAVQP_ERR_INVALID_ARG: what uavqp_attitude_optimize_device refuses (a NULL attitude excepted) and what uavqp_moving_penalty_device
+ * refuses in `obstacles` and `moving`.
+ * Out of scope: as uavqp_moving_penalty_device and uavqp_spacetime_lbfgs_device. */
+int uavqp_moving_optimize_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                                 const int32_t* d_seg_offsets, double* d_waypoints, double* d_times, const double* d_bc,
+                                 const uavqp_esdf* esdf, const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
+                                 const uavqp_attitude_params* attitude, const uavqp_moving_obstacles* obstacles,
+                                 const uavqp_moving_params* moving, const uavqp_spacetime_lbfgs_params* params, double* d_coeff_out,
+                                 int32_t* d_status_out, double* d_objective_out, int32_t* d_accepted_out, double* d_peak_out,
+                                 double* d_min_dist_out, int32_t* d_outside_out, double* d_attitude_peak_out, double* d_min_gap_out,
+                                 int32_t* d_nearest_out);
+/* The same from HOST pointers, those inside `obstacles` included, as uavqp_attitude_optimize_host. */
+int uavqp_moving_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                               double* waypoints, double* times, const double* bc, const uavqp_esdf* esdf, const uavqp_limit_params* limits,
+                               const uavqp_clearance_params* clearance, const uavqp_attitude_params* attitude,
+                               const uavqp_moving_obstacles* obstacles, const uavqp_moving_params* moving,
+                               const uavqp_spacetime_lbfgs_params* params, double* coeff_out, int32_t* status_out, double* objective_out,
+                               int32_t* accepted_out, double* peak_out, double* min_dist_out, int32_t* outside_out, double* attitude_peak_out,
+                               double* min_gap_out, int32_t* nearest_out);
 
 /* Batched evaluation of solved trajectories on a uniform time grid.
  * Replaces, for a whole batch, PolyTraj::evaluatePos / evaluateVel / evaluateAcc

@@ -101,6 +101,11 @@ SYMBOLS = (
     "uavqp_default_separation_params",
     "uavqp_separation_certificate_device",
     "uavqp_separation_certificate_host",
+    "uavqp_default_moving_params",
+    "uavqp_moving_penalty_device",
+    "uavqp_moving_penalty_host",
+    "uavqp_moving_optimize_device",
+    "uavqp_moving_optimize_host",
     "uavqp_eval_batch_device",
     "uavqp_traj_length_device",
     "uavqp_ellipsoid_check_device",
@@ -258,6 +263,19 @@ UAVQP_SEPARATION_VIOLATED = 2
 UAVQP_SEPARATION_MOVING = 4
 
 
+class MovingParams(ctypes.Structure):
+    """uavqp_moving_params of include/uavqp.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("samples_per_seg", ctypes.c_int32), ("d_safe", ctypes.c_double), ("downwash", ctypes.c_double),
+                ("weight", ctypes.c_double)]
+
+
+class MovingObstacles(ctypes.Structure):
+    """uavqp_moving_obstacles of include/uavqp.h: the pointers are device pointers for the _device entries, host pointers for the _host ones."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("n_obs", ctypes.c_int32), ("uniform_segments", ctypes.c_int32), ("n_sets", ctypes.c_int32),
+                ("seg_offsets", ctypes.c_void_p), ("times", ctypes.c_void_p), ("coeff", ctypes.c_void_p), ("start", ctypes.c_void_p),
+                ("radius", ctypes.c_void_p), ("set_offsets", ctypes.c_void_p), ("traj_set", ctypes.c_void_p), ("traj_start", ctypes.c_void_p)]
+
+
 def build(force=False):
     """Compile csrc/*.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
     csrc = os.path.join(_PKG, "csrc")
@@ -387,6 +405,20 @@ def lib():
     L.uavqp_default_separation_params.restype = None
     L.uavqp_separation_certificate_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, i32, ip, dp, ctypes.POINTER(SeparationParams), dp, dp, ip, ip, ip]
     L.uavqp_separation_certificate_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, i32, ip, dp, ctypes.POINTER(SeparationParams), dp, dp, ip, ip, ip]
+    L.uavqp_default_moving_params.argtypes = [ctypes.POINTER(MovingParams)]
+    L.uavqp_default_moving_params.restype = None
+    L.uavqp_moving_penalty_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, ctypes.POINTER(MovingObstacles), ctypes.POINTER(MovingParams),
+                                              dp, dp, dp, dp, dp, ip]
+    L.uavqp_moving_penalty_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, ctypes.POINTER(MovingObstacles), ctypes.POINTER(MovingParams),
+                                            dp, dp, dp, dp, dp, ip]
+    L.uavqp_moving_optimize_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(LimitParams),
+                                               ctypes.POINTER(ClearanceParams), ctypes.POINTER(AttitudeParams), ctypes.POINTER(MovingObstacles),
+                                               ctypes.POINTER(MovingParams), ctypes.POINTER(SpacetimeLbfgsParams), dp, ip, dp, ip, dp, dp, ip, dp,
+                                               dp, ip]
+    L.uavqp_moving_optimize_host.argtypes = [vp, i32, i32, i32, i32, ip, dp, dp, dp, vp, ctypes.POINTER(LimitParams),
+                                             ctypes.POINTER(ClearanceParams), ctypes.POINTER(AttitudeParams), ctypes.POINTER(MovingObstacles),
+                                             ctypes.POINTER(MovingParams), ctypes.POINTER(SpacetimeLbfgsParams), dp, ip, dp, ip, dp, dp, ip, dp,
+                                             dp, ip]
     L.uavqp_default_swarm_opt_params.argtypes = [ctypes.POINTER(SwarmOptParams)]
     L.uavqp_default_swarm_opt_params.restype = None
     L.uavqp_swarm_optimize_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, i32, ip, dp, vp, ctypes.POINTER(LimitParams),

@@ -316,6 +316,57 @@ def _swarm_function():
     return _Swarm
 
 
+_Moving = None
+
+
+def _moving_function():
+    global _Moving
+    if _Moving is not None:
+        return _Moving
+    import torch
+
+    class MovingPenalty(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, coeff, times, traj_start, ctx, r, obstacles, seg_offsets, uniform_segments, status, params):
+            for name, t in (("coeff", coeff), ("times", times), ("traj_start", traj_start)):
+                if t is not None and (t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous()):
+                    raise ValueError(f"moving_penalty: {name} must be a contiguous float64 tensor on the GPU")
+            total = times.numel()
+            n_traj = total // uniform_segments if uniform_segments > 0 else seg_offsets.numel() - 1
+            if coeff.numel() != 3 * 2 * r * total:
+                raise ValueError("moving_penalty: coeff must hold 3 * 2r doubles per segment")
+            if traj_start is not None and traj_start.numel() != n_traj:
+                raise ValueError("moving_penalty: traj_start must hold one departure time per trajectory")
+            phi = torch.empty(n_traj, dtype=torch.float64, device=times.device)
+            g_c = torch.empty_like(coeff)
+            g_t = torch.empty_like(times)
+            g_s = torch.empty(n_traj, dtype=torch.float64, device=times.device)
+            ctx.set_stream(torch.cuda.current_stream(times.device).cuda_stream)
+            obs = dict(obstacles, traj_start=None if traj_start is None else traj_start.detach())
+            ctx.moving_penalty_device(r, n_traj, uniform_segments, seg_offsets, times.detach(), coeff.detach(), obs, status=status, penalty=phi,
+                                      grad_coeff=g_c, grad_times=g_t, grad_start=g_s, **params)
+            if uniform_segments > 0:
+                counts = torch.full((n_traj,), uniform_segments, dtype=torch.int64, device=times.device)
+            else:
+                counts = (seg_offsets[1:] - seg_offsets[:-1]).to(torch.int64)
+            fctx.save_for_backward(g_c, g_t, g_s, counts)
+            fctx.nc = 3 * 2 * r
+            return phi
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable   # the gradients come from a raw kernel: no second derivative through them
+        def backward(fctx, grad_phi):
+            g_c, g_t, g_s, counts = fctx.saved_tensors
+            need_c, need_t, need_s = fctx.needs_input_grad[:3]
+            out_c = g_c * torch.repeat_interleave(grad_phi, counts * fctx.nc) if need_c else None
+            out_t = g_t * torch.repeat_interleave(grad_phi, counts) if need_t else None
+            out_s = g_s * grad_phi if need_s else None
+            return out_c, out_t, out_s, None, None, None, None, None, None, None
+
+    _Moving = MovingPenalty
+    return _Moving
+
+
 def solve_batch(ctx, r, waypoints, times, bc, seg_offsets=None, uniform_segments=0, max_segments=0, check_status=False, return_status=False):
     """Differentiable uavqp_solve_batch_device.  ctx: a Context on the tensors' device.  waypoints [sum (M_b + 1)][3], times [sum M_b],
     bc [n_traj][2][r-1][3]; seg_offsets: int32 device tensor [n_traj + 1] (ragged; max_segments = the longest trajectory, read back from
@@ -381,6 +432,25 @@ def swarm_penalty(ctx, r, coeff, times, group_offsets=None, start=None, seg_offs
     from .traj_optimizer import Context
     Context._swarm_params(params)   # (an unknown field is refused before anything runs)
     return _swarm_function().apply(coeff, times, start, ctx, int(r), group_offsets, seg_offsets, int(uniform_segments), status, dict(params))
+
+
+def moving_penalty(ctx, r, coeff, times, obstacles, traj_start=None, seg_offsets=None, uniform_segments=0, status=None, **params):
+    """Differentiable uavqp_moving_penalty_device: the penalty [n_traj] of coeff (layout of solve_batch's result) at the durations `times`
+    [sum M_b] and the departures `traj_start` [n_traj] (None: all zero, not differentiated) against the MOVING obstacle tracks
+    `obstacles`: the dict Context.moving_penalty_device takes (n_obs, uniform_segments, n_sets and the device tensors seg_offsets, times,
+    coeff, start, radius, set_offsets, traj_set), without traj_start.  params: fields of uavqp_moving_params that differ from the defaults
+    (samples_per_seg, d_safe, downwash, weight).  status: optional int32 status tensor of the solve.  Differentiable in coeff, times and
+    traj_start, not in the obstacles.  The gradient in `times` is the explicit part; with coeff = solve_batch(..., times, ...) torch adds
+    the part through the solve, and waypoints.grad / bc.grad come from the same backward pass."""
+    if uniform_segments <= 0 and seg_offsets is None:
+        raise ValueError("moving_penalty: ragged batches need seg_offsets")
+    if "traj_start" in obstacles:
+        raise ValueError("moving_penalty: traj_start is an argument of its own")
+    from .traj_optimizer import Context
+    Context._moving_params(params)   # (an unknown field is refused before anything runs)
+    Context._moving_obstacles(obstacles)
+    return _moving_function().apply(coeff, times, traj_start, ctx, int(r), dict(obstacles), seg_offsets, int(uniform_segments), status,
+                                    dict(params))
 
 
 def flight_penalty(ctx, r, coeff, times, esdf, seg_offsets=None, uniform_segments=0, status=None, limits=None, clearance=None):

@@ -428,6 +428,98 @@ class TrajOptimizer {
         return phi;
     }
     const std::vector<double>& attitudePeak() const { return attitude_peak_; }
+    // The moving obstacles the trajectories avoid (include/uavqp.h uavqp_moving_obstacles, host pointers; the arrays are COPIED): tracks in
+    // the library's own format and this optimiser's order -- obstacles.times / coeff / seg_offsets or uniform_segments -- with their
+    // departures and radii, the sets, the set each trajectory avoids and the trajectories' own departures.  nullptr removes them.
+    // false: the struct is refused (its size, a negative count, a missing array) and nothing is stored.
+    bool setMovingObstacles(const uavqp_moving_obstacles* obstacles) {
+        moving_ = MovingStore();
+        if (!obstacles) return true;
+        const uavqp_moving_obstacles& o = *obstacles;
+        if (o.struct_size != static_cast<int32_t>(sizeof(uavqp_moving_obstacles)) || o.n_obs < 0 || o.uniform_segments < 0 || o.n_sets < 0) return false;
+        if (o.n_obs > 0 && (!o.times || !o.coeff || (o.uniform_segments == 0 && !o.seg_offsets))) return false;
+        if (o.n_sets != 1 && (!o.set_offsets || !o.traj_set)) return false;
+        if ((o.traj_set || o.traj_start) && n_traj_ <= 0) return false;   // (their length is the batch's: setWaypoints first)
+        MovingStore m;
+        size_t total = static_cast<size_t>(o.uniform_segments) * o.n_obs;
+        if (o.n_obs > 0 && o.uniform_segments == 0) {
+            m.seg_offsets.assign(o.seg_offsets, o.seg_offsets + o.n_obs + 1);
+            if (m.seg_offsets[o.n_obs] < 0) return false;
+            total = static_cast<size_t>(m.seg_offsets[o.n_obs]);
+        }
+        if (o.n_obs > 0) {
+            m.times.assign(o.times, o.times + total);
+            m.coeff.assign(o.coeff, o.coeff + static_cast<size_t>(3) * 2 * order_ * total);
+            if (o.start) m.start.assign(o.start, o.start + o.n_obs);
+            if (o.radius) m.radius.assign(o.radius, o.radius + o.n_obs);
+        }
+        if (o.set_offsets) m.set_offsets.assign(o.set_offsets, o.set_offsets + o.n_sets + 1);
+        if (o.traj_set) m.traj_set.assign(o.traj_set, o.traj_set + n_traj_);
+        if (o.traj_start) m.traj_start.assign(o.traj_start, o.traj_start + n_traj_);
+        m.n_obs = o.n_obs; m.uniform_segments = o.uniform_segments; m.n_sets = o.n_sets; m.set = true;
+        moving_ = m;
+        return true;
+    }
+    // Penalty per trajectory against the obstacles of setMovingObstacles at the stored coefficients and durations (after solve() or an
+    // optimiser; uavqp_moving_penalty_host); fills minGap() / nearestObstacle().  A trajectory that did not solve carries zero.  Empty on
+    // failure.
+    std::vector<double> getMovingPenalty(const uavqp_moving_params& moving) {
+        std::vector<double> phi;
+        if (!moving_.set || n_traj_ <= 0 || !ctx_ || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_]) ||
+            coef_.size() != static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_] || status_.size() != static_cast<size_t>(n_traj_))
+            return phi;
+        phi.assign(n_traj_, 0.0);
+        min_gap_.assign(n_traj_, 0.0);
+        nearest_.assign(n_traj_, -1);
+        const uavqp_moving_obstacles o = moving_.view();
+        if (uavqp_moving_penalty_host(ctx_, order_, n_traj_, 0, seg_offsets_.data(), T_.data(), coef_.data(), status_.data(), &o, &moving,
+                                      phi.data(), nullptr, nullptr, nullptr, min_gap_.data(), nearest_.data()) != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            phi.clear();
+        }
+        return phi;
+    }
+    // optimizeTrajectoryAttitude with the penalty against the obstacles of setMovingObstacles inside the objective (include/uavqp.h
+    // uavqp_moving_optimize_host): the same bounds, the same members filled, and minGap() / nearestObstacle() at the result.  attitude null:
+    // NO attitude term.  The penalty is soft: minGap() is the check afterwards, on the samples.  params: null =
+    // uavqp_default_spacetime_lbfgs_params.
+    template <class Map>
+    bool optimizeTrajectoryMoving(const Map& map, const uavqp_limit_params& limits, const uavqp_clearance_params& clearance,
+                                  const uavqp_attitude_params* attitude, const uavqp_moving_params& moving,
+                                  const uavqp_spacetime_lbfgs_params* params = nullptr) {
+        if (!moving_.set || n_traj_ <= 0 || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_])) return false;
+        if (!lo_.empty() || rows_k_ > 0) {
+            std::cout << "solver solve failed! (optimizeTrajectoryMoving: corridor and general-rows problems are out of scope)" << std::endl;
+            return false;
+        }
+        if (!ensureContext()) return false;
+        if (bc_.empty()) bc_.assign(static_cast<size_t>(n_traj_) * 2 * (order_ - 1) * 3, 0.0);
+        uavqp_spacetime_lbfgs_params pp;
+        if (params) pp = *params; else uavqp_default_spacetime_lbfgs_params(&pp);
+        coef_.assign(static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_], 0.0);
+        status_.assign(n_traj_, 0);
+        objective_.assign(static_cast<size_t>(2) * n_traj_, 0.0);
+        accepted_.assign(n_traj_, 0);
+        peak_.assign(static_cast<size_t>(2) * n_traj_, 0.0);
+        min_dist_.assign(n_traj_, 0.0);
+        outside_.assign(n_traj_, 0);
+        attitude_peak_.assign(static_cast<size_t>(4) * n_traj_, 0.0);
+        min_gap_.assign(n_traj_, 0.0);
+        nearest_.assign(n_traj_, -1);
+        const uavqp_moving_obstacles o = moving_.view();
+        const int rc = uavqp_moving_optimize_host(ctx_, order_, n_traj_, 0, 0, seg_offsets_.data(), wp_.data(), T_.data(), bc_.data(), map.handle(),
+                                                  &limits, &clearance, attitude, &o, &moving, &pp, coef_.data(), status_.data(), objective_.data(),
+                                                  accepted_.data(), peak_.data(), min_dist_.data(), outside_.data(), attitude_peak_.data(),
+                                                  min_gap_.data(), nearest_.data());
+        if (rc != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            return false;
+        }
+        for (int32_t s : status_) if (s != UAVQP_SOLVED) return false;
+        return true;
+    }
+    const std::vector<double>& minGap() const { return min_gap_; }
+    const std::vector<int32_t>& nearestObstacle() const { return nearest_; }
     // Certified bounds of the stored coefficients at the stored durations over WHOLE segments (after solve() or an optimiser;
     // uavqp_envelope_host): the verdict word per trajectory (bit 2k certified for all t, bit 2k + 1 violated, UAVQP_ENVELOPE_* of
     // include/uavqp.h), and envelopeRange() [sum M][4][3][4], envelopeNorm() [sum M][5][4], envelopePeak() [n_traj][5][4],
@@ -795,6 +887,30 @@ class TrajOptimizer {
     std::vector<int32_t> accepted_;
     std::vector<double> separation_lower_, separation_upper_;
     std::vector<int32_t> separation_where_, separation_group_verdict_;
+    // setMovingObstacles: copies of the arrays of a uavqp_moving_obstacles (empty = that pointer is NULL)
+    struct MovingStore {
+        bool set = false;
+        int32_t n_obs = 0, uniform_segments = 0, n_sets = 0;
+        std::vector<int32_t> seg_offsets, set_offsets, traj_set;
+        std::vector<double> times, coeff, start, radius, traj_start;
+        uavqp_moving_obstacles view() const {
+            uavqp_moving_obstacles o;
+            o.struct_size = static_cast<int32_t>(sizeof(uavqp_moving_obstacles));
+            o.n_obs = n_obs; o.uniform_segments = uniform_segments; o.n_sets = n_sets;
+            o.seg_offsets = seg_offsets.empty() ? nullptr : seg_offsets.data();
+            o.times = times.empty() ? nullptr : times.data();
+            o.coeff = coeff.empty() ? nullptr : coeff.data();
+            o.start = start.empty() ? nullptr : start.data();
+            o.radius = radius.empty() ? nullptr : radius.data();
+            o.set_offsets = set_offsets.empty() ? nullptr : set_offsets.data();
+            o.traj_set = traj_set.empty() ? nullptr : traj_set.data();
+            o.traj_start = traj_start.empty() ? nullptr : traj_start.data();
+            return o;
+        }
+    };
+    MovingStore moving_;
+    std::vector<double> min_gap_;
+    std::vector<int32_t> nearest_;
     std::vector<int32_t> groups_;   // setSwarm: empty = the whole batch is one swarm
     std::vector<double> start_;     // setSwarm: empty = every vehicle departs at 0
     int rows_k_ = 0;

@@ -188,6 +188,12 @@ static inline bool uavqp_twisted_group_exists(int r, int M, int tile) {
     UAVQP_INST __global__ void uavqp::attitude_penalty_kernel<R_, true>(uavqp::AttitudeArgs);
 #define UAVQP_INSTANCES_ATTITUDE UAVQP_ATTITUDE_R(3) UAVQP_ATTITUDE_R(4)
 
+// ---- qp_moving.h: penalty against moving obstacle tracks with its gradients, and the variant that ADDS them to the flight penalty's
+#define UAVQP_MOVING_R(R_)                                                                   \
+    UAVQP_INST __global__ void uavqp::moving_penalty_kernel<R_, false>(uavqp::MovingArgs);      \
+    UAVQP_INST __global__ void uavqp::moving_penalty_kernel<R_, true>(uavqp::MovingArgs);
+#define UAVQP_INSTANCES_MOVING UAVQP_MOVING_R(3) UAVQP_MOVING_R(4)
+
 // ---- qp_envelope.h: certified bounds of position, velocity, acceleration, jerk, thrust and tilt over whole segments
 #define UAVQP_ENVELOPE_R(R_) UAVQP_INST __global__ void uavqp::envelope_kernel<R_>(uavqp::EnvelopeArgs);
 #define UAVQP_INSTANCES_ENVELOPE UAVQP_ENVELOPE_R(3) UAVQP_ENVELOPE_R(4)

@@ -41,6 +41,7 @@
 #include "qp_swarm.h"
 #include "qp_swarm_opt.h"
 #include "qp_attitude.h"
+#include "qp_moving.h"
 #include "qp_envelope.h"
 #include "qp_clearance_cert.h"
 #include "qp_separation_cert.h"
@@ -82,6 +83,7 @@ UAVQP_INSTANCES_SPACETIME_LBFGS
 UAVQP_INSTANCES_SWARM
 UAVQP_INSTANCES_SWARM_OPT
 UAVQP_INSTANCES_ATTITUDE
+UAVQP_INSTANCES_MOVING
 UAVQP_INSTANCES_ENVELOPE
 UAVQP_INSTANCES_CLEARANCE_CERT
 UAVQP_INSTANCES_SEPARATION_CERT
@@ -2015,6 +2017,11 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
 // Attitude penalty: specific thrust, tilt and body rate of the vehicle that flies the trajectory
 // ===================================================================================================
 #include "uavqp_attitude.h"
+
+// ===================================================================================================
+// Moving-obstacle penalty: a trajectory against tracks that are not the batch's to move
+// ===================================================================================================
+#include "uavqp_moving.h"
 
 // ===================================================================================================
 // Certified continuous-time bounds (Bernstein enclosure) of solved trajectories and the verdict against limits

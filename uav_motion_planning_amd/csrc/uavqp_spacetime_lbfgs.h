@@ -1,6 +1,7 @@
-// uavqp_spacetime_lbfgs.h -- host side of uavqp_spacetime_lbfgs_device / _host and uavqp_attitude_optimize_device / _host (include/uavqp.h):
-// included by uavqp.hip behind uavqp_spacetime.h, whose parameter checks, penalty launch and sequencing it shares, and uavqp_attitude.h.  Kernel: qp_spacetime_lbfgs.h (translation unit
-// k_spacetime_lbfgs.hip).
+// uavqp_spacetime_lbfgs.h -- host side of uavqp_spacetime_lbfgs_device / _host, uavqp_attitude_optimize_device / _host and
+// uavqp_moving_optimize_device / _host (include/uavqp.h):
+// included by uavqp.hip behind uavqp_spacetime.h, whose parameter checks, penalty launch and sequencing it shares, uavqp_attitude.h and
+// uavqp_moving.h.  Kernel: qp_spacetime_lbfgs.h (translation unit k_spacetime_lbfgs.hip).
 //
 // The launch sequence is that of uavqp_spacetime_optimize_device with the other step kernel: NO data-dependent control flow on the host, the
 // number of launches is fixed by max_iters, every decision (accept / reject, which pairs are kept, quasi-Newton or gradient direction, a
@@ -8,7 +9,8 @@
 //     anchor copy -> clamp -> solve(waypoints, times) -> flight penalty -> backward -> step<INIT>
 //       -> max_iters x { solve(trial waypoints, trial durations) -> flight penalty -> backward -> step<ITER> }
 //       -> solve(waypoints, times) -> flight penalty (peak / min_dist / outside only)
-// Four launches per iteration; with the attitude penalty (uavqp_attitude_optimize_device) one more after every flight penalty of the loop.
+// Four launches per iteration; with the attitude penalty (uavqp_attitude_optimize_device) one more after every flight penalty of the loop,
+// with the moving-obstacle penalty (uavqp_moving_optimize_device) one more behind that: six at the most.
 #pragma once
 
 extern "C" void uavqp_default_spacetime_lbfgs_params(uavqp_spacetime_lbfgs_params* p) {
@@ -45,21 +47,27 @@ static bool spacetime_lbfgs_params_valid(const uavqp_spacetime_lbfgs_params* p) 
 
 // The sequence above for both entries.  attitude null (uavqp_spacetime_lbfgs_device): exactly those launches.  attitude with a positive
 // weight (uavqp_attitude_optimize_device): the accumulating attitude penalty (qp_attitude.h) is enqueued between the flight penalty and the
-// backward pass, so the step kernel reads the summed phi and the summed partial gradients -- five launches per iteration.
+// backward pass, so the step kernel reads the summed phi and the summed partial gradients -- five launches per iteration.  obstacles and
+// moving (uavqp_moving_optimize_device; both or neither) with a positive weight and an obstacle to avoid: the accumulating moving-obstacle
+// penalty (qp_moving.h) follows the attitude launch in the same way, and its min_gap / nearest are taken at what is handed back.
 static int spacetime_lbfgs_run(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
                                const int32_t* d_seg_offsets, double* d_waypoints, double* d_times, const double* d_bc, const uavqp_esdf* esdf,
                                const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
                                const uavqp_spacetime_lbfgs_params* params, double* d_coeff_out, int32_t* d_status_out, double* d_objective_out,
                                int32_t* d_accepted_out, double* d_peak_out, double* d_min_dist_out, int32_t* d_outside_out,
-                               const uavqp_attitude_params* attitude, double* d_attitude_peak_out) {
+                               const uavqp_attitude_params* attitude, double* d_attitude_peak_out,
+                               const uavqp_moving_obstacles* obstacles = nullptr, const uavqp_moving_params* moving = nullptr,
+                               double* d_min_gap_out = nullptr, int32_t* d_nearest_out = nullptr) {
     bool run;
     int rc = descent_args_check(ctx, r, n_traj, 1, uniform_segments, max_segments, total_segments, d_seg_offsets,
                                 d_waypoints && d_times && d_bc && d_coeff_out && d_objective_out, true, [&] {
                                     return spacetime_lbfgs_params_valid(params) && flight_params_valid(ctx, esdf, limits, clearance) &&
-                                           (!attitude || attitude_params_valid(attitude));
+                                           (!attitude || attitude_params_valid(attitude)) &&
+                                           (!moving || (moving_params_valid(moving) && moving_obstacles_valid(obstacles)));
                                 }, &run);
     if (!run) return rc;
     const bool with_attitude = attitude && attitude_any_weight(*attitude);
+    const bool with_moving = moving && moving->weight > 0.0 && !moving_nothing_to_avoid(*obstacles);
     const uavqp_spacetime_lbfgs_params P = *params;
     const size_t n = (size_t)n_traj, tot = (size_t)total_segments;
     const size_t slots = P.max_iters > 0 ? (size_t)P.memory + 1 : 0;   // (no trial: no pair is ever written)
@@ -87,11 +95,16 @@ static int spacetime_lbfgs_run(uavqp_ctx* ctx, int r, int n_traj, int uniform_se
     q.wp_len = 3 * (tot + n); q.t_len = tot;
     q.memory = P.memory; q.max_backtracks = P.max_backtracks; q.curvature_eps = P.curvature_eps;
     const int grid = topt_grid(ctx, n_traj);
-    // the accumulating attitude penalty between the flight penalty and the backward pass
+    // the accumulating attitude penalty, then the accumulating moving-obstacle penalty, between the flight penalty and the backward pass
     auto attitude_penalty = [&](const DescentPoint& p) -> int {
-        if (!with_attitude) return UAVQP_OK;
-        return attitude_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, j.t_at(p), d_coeff_out, j.status_at(p), *attitude,
-                                        j.at<double>(j.k.ph), j.at<double>(j.k.g), j.at<double>(j.k.ex), nullptr, true);
+        int e = UAVQP_OK;
+        if (with_attitude)
+            e = attitude_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, j.t_at(p), d_coeff_out, j.status_at(p), *attitude,
+                                         j.at<double>(j.k.ph), j.at<double>(j.k.g), j.at<double>(j.k.ex), nullptr, true);
+        if (e == UAVQP_OK && with_moving)
+            e = moving_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, j.t_at(p), d_coeff_out, j.status_at(p), *obstacles, *moving,
+                                       j.at<double>(j.k.ph), j.at<double>(j.k.g), j.at<double>(j.k.ex), nullptr, nullptr, nullptr, true);
+        return e;
     };
     rc = j.anchor_copies(P.max_iters);
     if (rc == UAVQP_OK) rc = time_clamp_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, P.t_min, P.t_max);
@@ -104,6 +117,9 @@ static int spacetime_lbfgs_run(uavqp_ctx* ctx, int r, int n_traj, int uniform_se
     if (rc == UAVQP_OK && attitude && d_attitude_peak_out)
         rc = attitude_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, j.status_final(), *attitude, nullptr,
                                       nullptr, nullptr, d_attitude_peak_out);
+    if (rc == UAVQP_OK && moving && (d_min_gap_out || d_nearest_out))
+        rc = moving_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, j.status_final(), *obstacles, *moving,
+                                    nullptr, nullptr, nullptr, nullptr, d_min_gap_out, d_nearest_out);
     return rc;
 }
 
@@ -170,4 +186,55 @@ extern "C" int uavqp_attitude_optimize_host(uavqp_ctx* ctx, int r, int n_traj, i
     return spacetime_lbfgs_run_host(ctx, r, n_traj, uniform_segments, max_segments, seg_offsets, waypoints, times, bc, esdf, limits, clearance,
                                     params, coeff_out, status_out, objective_out, accepted_out, peak_out, min_dist_out, outside_out, attitude,
                                     attitude_peak_out, "uavqp_attitude_optimize_host");
+}
+
+extern "C" int uavqp_moving_optimize_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
+                                            const int32_t* d_seg_offsets, double* d_waypoints, double* d_times, const double* d_bc,
+                                            const uavqp_esdf* esdf, const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
+                                            const uavqp_attitude_params* attitude, const uavqp_moving_obstacles* obstacles,
+                                            const uavqp_moving_params* moving, const uavqp_spacetime_lbfgs_params* params, double* d_coeff_out,
+                                            int32_t* d_status_out, double* d_objective_out, int32_t* d_accepted_out, double* d_peak_out,
+                                            double* d_min_dist_out, int32_t* d_outside_out, double* d_attitude_peak_out, double* d_min_gap_out,
+                                            int32_t* d_nearest_out) {
+    if (!moving_params_valid(moving) || !moving_obstacles_valid(obstacles)) return UAVQP_ERR_INVALID_ARG;
+    return spacetime_lbfgs_run(ctx, r, n_traj, uniform_segments, max_segments, total_segments, d_seg_offsets, d_waypoints, d_times, d_bc, esdf,
+                               limits, clearance, params, d_coeff_out, d_status_out, d_objective_out, d_accepted_out, d_peak_out, d_min_dist_out,
+                               d_outside_out, attitude, d_attitude_peak_out, obstacles, moving, d_min_gap_out, d_nearest_out);
+}
+
+// the staging of spacetime_lbfgs_run_host with the obstacle arrays and the two further outputs declared on the same Stage
+extern "C" int uavqp_moving_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                                          double* waypoints, double* times, const double* bc, const uavqp_esdf* esdf,
+                                          const uavqp_limit_params* limits, const uavqp_clearance_params* clearance,
+                                          const uavqp_attitude_params* attitude, const uavqp_moving_obstacles* obstacles,
+                                          const uavqp_moving_params* moving, const uavqp_spacetime_lbfgs_params* params, double* coeff_out,
+                                          int32_t* status_out, double* objective_out, int32_t* accepted_out, double* peak_out,
+                                          double* min_dist_out, int32_t* outside_out, double* attitude_peak_out, double* min_gap_out,
+                                          int32_t* nearest_out) {
+    if (!moving_params_valid(moving) || !moving_obstacles_valid(obstacles)) return UAVQP_ERR_INVALID_ARG;
+    if (n_traj < 0) return UAVQP_ERR_INVALID_ARG;
+    BatchShape osh;
+    const int rc = moving_host_check(*obstacles, n_traj, &osh);
+    if (rc != UAVQP_OK) return rc;
+    MovingStage ms;
+    int i_mg = -1, i_nr = -1;
+    return descent_run_host(
+        ctx, r, n_traj, uniform_segments, max_segments, seg_offsets, waypoints, waypoints, times, times, bc,
+        [&] {
+            return spacetime_lbfgs_params_valid(params) && flight_params_valid(ctx, esdf, limits, clearance) &&
+                   (!attitude || attitude_params_valid(attitude));
+        },
+        coeff_out, status_out, objective_out, accepted_out, peak_out, min_dist_out, outside_out, attitude ? attitude_peak_out : nullptr, 4,
+        "uavqp_moving_optimize_host",
+        [&](const DescentStaged& d, const Stage& st) {
+            const uavqp_moving_obstacles dev = ms.device(st, *obstacles);
+            return spacetime_lbfgs_run(ctx, r, n_traj, uniform_segments, d.Mmax, d.total_segments, d.seg_offsets, d.waypoints, d.times, d.bc, esdf,
+                                       limits, clearance, params, d.coeff, d.status, d.objective, d.accepted, d.peak, d.min_dist, d.outside,
+                                       attitude, d.extra, &dev, moving, st.at<double>(i_mg), st.at<int32_t>(i_nr));
+        },
+        [&](Stage& st) {
+            ms.declare(st, *obstacles, r, n_traj, osh);
+            i_mg = min_gap_out ? st.out(min_gap_out, sizeof(double) * (size_t)n_traj) : -1;
+            i_nr = nearest_out ? st.out(nearest_out, sizeof(int32_t) * (size_t)n_traj) : -1;
+        });
 }

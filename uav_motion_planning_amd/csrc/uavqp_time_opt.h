@@ -206,13 +206,14 @@ struct DescentStaged {
 
 // The _host entries of the per-trajectory optimisers: the checks (params_ok: the entry's parameter structs), the staging of the arrays and
 // device(DescentStaged) between stage_begin and stage_end.  waypoints_back / times_back: the same pointer where the entry optimises the
-// array (inout), null where it only reads it.  extra_out: extra_per_traj doubles per trajectory.
-template <class ParamsOk, class Device>
+// array (inout), null where it only reads it.  extra_out: extra_per_traj doubles per trajectory.  more(Stage&): what an entry stages
+// beyond these arrays, declared behind them; its device(DescentStaged, Stage) then finds them on the Stage.
+template <class ParamsOk, class Device, class More>
 static int descent_run_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
                             const double* waypoints, double* waypoints_back, const double* times, double* times_back, const double* bc,
                             ParamsOk&& params_ok, double* coeff_out, int32_t* status_out, double* objective_out, int32_t* accepted_out,
                             double* peak_out, double* min_dist_out, int32_t* outside_out, double* extra_out, size_t extra_per_traj, const char* who,
-                            Device&& device) {
+                            Device&& device, More&& more) {
     if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0) return UAVQP_ERR_INVALID_ARG;
     if (!params_ok()) return UAVQP_ERR_INVALID_ARG;
     if (n_traj == 0) return UAVQP_OK;
@@ -235,13 +236,27 @@ static int descent_run_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segme
     const int i_md = min_dist_out ? st.out(min_dist_out, sizeof(double) * n) : -1;
     const int i_o = outside_out ? st.out(outside_out, sizeof(int32_t) * n) : -1;
     const int i_x = extra_out ? st.out(extra_out, sizeof(double) * extra_per_traj * n) : -1;
+    more(st);
     rc = stage_begin(ctx, st);
     if (rc != UAVQP_OK) return rc;
     rc = device(DescentStaged{sh.Mmax, (int)sh.total_seg, st.at<int32_t>(i_off), st.at<double>(i_wp), st.at<double>(i_t), st.at<double>(i_bc),
                               st.at<double>(i_out), st.at<int32_t>(i_st), st.at<double>(i_obj), st.at<int32_t>(i_acc), st.at<double>(i_pk),
-                              st.at<double>(i_md), st.at<int32_t>(i_o), st.at<double>(i_x)});
+                              st.at<double>(i_md), st.at<int32_t>(i_o), st.at<double>(i_x)},
+                static_cast<const Stage&>(st));
     if (rc != UAVQP_OK) return rc;
     return stage_end(ctx, st, who);
+}
+// (an entry without further arrays)
+template <class ParamsOk, class Device>
+static int descent_run_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,
+                            const double* waypoints, double* waypoints_back, const double* times, double* times_back, const double* bc,
+                            ParamsOk&& params_ok, double* coeff_out, int32_t* status_out, double* objective_out, int32_t* accepted_out,
+                            double* peak_out, double* min_dist_out, int32_t* outside_out, double* extra_out, size_t extra_per_traj, const char* who,
+                            Device&& device) {
+    return descent_run_host(
+        ctx, r, n_traj, uniform_segments, max_segments, seg_offsets, waypoints, waypoints_back, times, times_back, bc, params_ok, coeff_out,
+        status_out, objective_out, accepted_out, peak_out, min_dist_out, outside_out, extra_out, extra_per_traj, who,
+        [&](const DescentStaged& d, const Stage&) { return device(d); }, [](Stage&) {});
 }
 
 static int time_optimize_run_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, const int32_t* seg_offsets,

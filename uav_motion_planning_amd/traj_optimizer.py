@@ -782,6 +782,150 @@ class Context:
         _lib.check(rc, "uavqp_attitude_optimize_host")
         return waypoints, times, coeff, status, objective, accepted, peak, min_dist, outside, attitude_peak
 
+    @staticmethod
+    def _moving_params(params):
+        mp = _lib.MovingParams()
+        _lib.lib().uavqp_default_moving_params(ctypes.byref(mp))
+        for k, v in params.items():
+            if not hasattr(mp, k) or k == "struct_size":
+                raise ValueError(f"unknown uavqp_moving_params field {k!r}")
+            setattr(mp, k, v)
+        return mp
+
+    _MOVING_POINTERS = ("seg_offsets", "times", "coeff", "start", "radius", "set_offsets", "traj_set", "traj_start")
+
+    @classmethod
+    def _moving_obstacles(cls, obstacles):
+        """uavqp_moving_obstacles from a dict: n_obs, uniform_segments (0: ragged), n_sets (default 1) and the arrays of
+        _MOVING_POINTERS (numpy arrays, torch tensors or raw addresses; absent or None: NULL).  The arrays must outlive the call."""
+        mo = _lib.MovingObstacles()
+        mo.struct_size = ctypes.sizeof(_lib.MovingObstacles)
+        for k in obstacles:
+            if k not in cls._MOVING_POINTERS and k not in ("n_obs", "uniform_segments", "n_sets"):
+                raise ValueError(f"unknown uavqp_moving_obstacles field {k!r}")
+        mo.n_obs = int(obstacles.get("n_obs", 0))
+        mo.uniform_segments = int(obstacles.get("uniform_segments", 0))
+        mo.n_sets = int(obstacles.get("n_sets", 1))
+        for k in cls._MOVING_POINTERS:
+            setattr(mo, k, _ptr(obstacles.get(k)))
+        return mo
+
+    @classmethod
+    def _moving_obstacles_host(cls, r, obstacles, n_traj):
+        """The same from host arrays, shapes checked: times [sum Mo], coeff (layout of a batch's coeff), seg_offsets or uniform_segments,
+        start / radius [n_obs], set_offsets [n_sets + 1], traj_set / traj_start [n_traj].  Returns (struct, the arrays it points into)."""
+        for k in obstacles:
+            if k not in cls._MOVING_POINTERS and k not in ("uniform_segments",):
+                raise ValueError(f"unknown moving-obstacle field {k!r}")
+        def arr(k, dt):
+            v = obstacles.get(k)
+            return None if v is None else np.ascontiguousarray(v, dtype=dt).ravel()
+        keep = {k: arr(k, np.int32 if k in ("seg_offsets", "set_offsets", "traj_set") else np.float64) for k in cls._MOVING_POINTERS}
+        uni = int(obstacles.get("uniform_segments", 0))
+        times = keep["times"] if keep["times"] is not None else np.zeros(0)
+        so, n_obs, total, _ = _batch_shape(keep["seg_offsets"], times, uni) if (uni > 0 or keep["seg_offsets"] is not None) else (None, 0, 0, 1)
+        keep["seg_offsets"] = so
+        assert times.size == total and (keep["coeff"] is None or keep["coeff"].size == 3 * 2 * r * total)
+        for k in ("start", "radius"):
+            assert keep[k] is None or keep[k].size == n_obs, k
+        for k in ("traj_set", "traj_start"):
+            assert keep[k] is None or keep[k].size == n_traj, k
+        d = dict(keep, n_obs=n_obs, uniform_segments=uni, n_sets=1 if keep["set_offsets"] is None else keep["set_offsets"].size - 1)
+        return cls._moving_obstacles(d), keep
+
+    def moving_penalty_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, obstacles, status=None, penalty=None,
+                              grad_coeff=None, grad_times=None, grad_start=None, min_gap=None, nearest=None, **params):
+        """uavqp_moving_penalty_device on device buffers: the penalty [n_traj] of solved trajectories against MOVING obstacle tracks, its
+        gradient in the coefficients at fixed durations (layout of coeff), its EXPLICIT gradients in the durations [sum M] and in the
+        departure [n_traj], the smallest sampled gap [n_traj] and the obstacle that attains it [n_traj] int32; each output may be None.
+        obstacles: dict of uavqp_moving_obstacles (n_obs, uniform_segments, n_sets and the device arrays seg_offsets, times, coeff, start,
+        radius, set_offsets, traj_set, traj_start).  params: fields of uavqp_moving_params that differ from uavqp_default_moving_params
+        (samples_per_seg, d_safe, downwash, weight).  Asynchronous."""
+        mp = self._moving_params(params)
+        mo = self._moving_obstacles(obstacles)
+        rc = _lib.lib().uavqp_moving_penalty_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff), _ptr(status),
+                                                    ctypes.byref(mo), ctypes.byref(mp), _ptr(penalty), _ptr(grad_coeff), _ptr(grad_times),
+                                                    _ptr(grad_start), _ptr(min_gap), _ptr(nearest))
+        _lib.check(rc, "uavqp_moving_penalty_device")
+
+    def moving_penalty_host(self, r, seg_offsets, times, coeff, obstacles, uniform_segments=0, status=None, **params):
+        """numpy in / numpy out (synchronous).  obstacles: dict of host arrays (_moving_obstacles_host).  Returns (penalty [n_traj],
+        grad_coeff, grad_times [sum M], grad_start [n_traj], min_gap [n_traj], nearest [n_traj])."""
+        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
+        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total and coeff.size == 3 * 2 * r * total
+        mp = self._moving_params(params)
+        mo, keep = self._moving_obstacles_host(r, obstacles, n_traj)
+        penalty = np.zeros(n_traj, dtype=np.float64)
+        g_c = np.zeros_like(coeff)
+        g_t = np.zeros(total, dtype=np.float64)
+        g_s = np.zeros(n_traj, dtype=np.float64)
+        min_gap = np.zeros(n_traj, dtype=np.float64)
+        nearest = np.zeros(n_traj, dtype=np.int32)
+        rc = _lib.lib().uavqp_moving_penalty_host(self._h, r, n_traj, uniform_segments, _ptr(so), _ptr(times), _ptr(coeff), _ptr(status),
+                                                  ctypes.byref(mo), ctypes.byref(mp), _ptr(penalty), _ptr(g_c), _ptr(g_t), _ptr(g_s),
+                                                  _ptr(min_gap), _ptr(nearest))
+        del keep
+        _lib.check(rc, "uavqp_moving_penalty_host")
+        return penalty, g_c, g_t, g_s, min_gap, nearest
+
+    def moving_optimize_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc, esdf,
+                               obstacles, coeff_out, status_out, objective_out, accepted_out=None, peak_out=None, min_dist_out=None,
+                               outside_out=None, attitude_peak_out=None, min_gap_out=None, nearest_out=None, limits=None, clearance=None,
+                               attitude=None, moving=None, **params):
+        """uavqp_moving_optimize_device on device buffers: attitude_optimize_device with the moving-obstacle penalty inside the objective
+        (objective_out includes it); min_gap_out [n_traj] / nearest_out [n_traj] int32 receive moving_penalty_device's at the result.
+        obstacles as for moving_penalty_device; moving: dict of uavqp_moving_params fields; attitude: dict of uavqp_attitude_params
+        fields, None: NO attitude term; everything else as spacetime_lbfgs_device.  Asynchronous."""
+        pp = self._spacetime_lbfgs_params(params)
+        lp, cp = self._limit_params(limits or {}), self._clearance_params(clearance or {})
+        ap = None if attitude is None else self._attitude_params(attitude)
+        mp, mo = self._moving_params(moving or {}), self._moving_obstacles(obstacles)
+        rc = _lib.lib().uavqp_moving_optimize_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), _ptr(seg_offsets),
+                                                     _ptr(waypoints), _ptr(times), _ptr(bc), getattr(esdf, "handle", esdf), ctypes.byref(lp),
+                                                     ctypes.byref(cp), None if ap is None else ctypes.byref(ap), ctypes.byref(mo),
+                                                     ctypes.byref(mp), ctypes.byref(pp), _ptr(coeff_out), _ptr(status_out), _ptr(objective_out),
+                                                     _ptr(accepted_out), _ptr(peak_out), _ptr(min_dist_out), _ptr(outside_out),
+                                                     _ptr(attitude_peak_out), _ptr(min_gap_out), _ptr(nearest_out))
+        _lib.check(rc, "uavqp_moving_optimize_device")
+
+    def moving_optimize_host(self, r, seg_offsets, waypoints, times, bc, esdf, obstacles, uniform_segments=0, limits=None, clearance=None,
+                             attitude=None, moving=None, **params):
+        """numpy in / numpy out (synchronous; the map stays on the device).  Returns what attitude_optimize_host returns (the attitude
+        peaks are zeros when attitude is None), then min_gap [n_traj] and nearest [n_traj]."""
+        waypoints = np.array(waypoints, dtype=np.float64).reshape(-1, 3)   # copies: the call updates both in place
+        times = np.array(times, dtype=np.float64).ravel()
+        bc = np.ascontiguousarray(bc, dtype=np.float64)
+        so, n_traj, total, mmax = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total
+        assert waypoints.size == 3 * (total + n_traj), "waypoints must hold sum(M_b + 1) xyz rows"
+        assert bc.size == n_traj * 2 * (r - 1) * 3
+        pp = self._spacetime_lbfgs_params(params)
+        lp, cp = self._limit_params(limits or {}), self._clearance_params(clearance or {})
+        ap = None if attitude is None else self._attitude_params(attitude)
+        mp = self._moving_params(moving or {})
+        mo, keep = self._moving_obstacles_host(r, obstacles, n_traj)
+        coeff = np.zeros(3 * 2 * r * total, dtype=np.float64)
+        status = np.zeros(n_traj, dtype=np.int32)
+        objective = np.zeros((n_traj, 2), dtype=np.float64)
+        accepted = np.zeros(n_traj, dtype=np.int32)
+        peak = np.zeros((n_traj, 2), dtype=np.float64)
+        min_dist = np.zeros(n_traj, dtype=np.float64)
+        outside = np.zeros(n_traj, dtype=np.int32)
+        attitude_peak = np.zeros((n_traj, 4), dtype=np.float64)
+        min_gap = np.zeros(n_traj, dtype=np.float64)
+        nearest = np.zeros(n_traj, dtype=np.int32)
+        rc = _lib.lib().uavqp_moving_optimize_host(self._h, r, n_traj, uniform_segments, max(mmax, 1), _ptr(so), _ptr(waypoints), _ptr(times),
+                                                   _ptr(bc), getattr(esdf, "handle", esdf), ctypes.byref(lp), ctypes.byref(cp),
+                                                   None if ap is None else ctypes.byref(ap), ctypes.byref(mo), ctypes.byref(mp),
+                                                   ctypes.byref(pp), _ptr(coeff), _ptr(status), _ptr(objective), _ptr(accepted), _ptr(peak),
+                                                   _ptr(min_dist), _ptr(outside), _ptr(attitude_peak), _ptr(min_gap), _ptr(nearest))
+        del keep
+        _lib.check(rc, "uavqp_moving_optimize_host")
+        return waypoints, times, coeff, status, objective, accepted, peak, min_dist, outside, attitude_peak, min_gap, nearest
+
     def time_optimize_limits_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc,
                                     coeff_out, status_out, objective_out, accepted_out=None, peak_out=None, limits=None, **params):
         """uavqp_time_optimize_limits_device on device buffers: time_optimize_device with the limit penalty inside the objective
@@ -1161,6 +1305,11 @@ class TrajOptimizer:
     optimizeTrajectoryAttitude(esdf, ...)   optimizeTrajectoryLbfgs with the attitude penalty (thrust, tilt, body rate) in the objective
                                      (uavqp_attitude_optimize_host); .attitude_peak [n_traj][4] the sampled peaks at the result
     getAttitudePenalty(...)          [n_traj] attitude penalty of the stored coefficients at the stored durations; fills .attitude_peak
+    setMovingObstacles(times, coeff, ...)   obstacle tracks that are not this batch's to move (uavqp_moving_obstacles): their sets, which
+                                     set each trajectory avoids, the departures on the common clock
+    getMovingPenalty(...)            [n_traj] penalty against those tracks; fills .min_gap and .nearest
+    optimizeTrajectoryMoving(esdf, ...)   optimizeTrajectoryAttitude with that penalty in the objective (uavqp_moving_optimize_host;
+                                     attitude=None: no attitude term); .min_gap / .nearest at the result
     getEnvelope(depth, box, **limits)  certified bounds over whole segments and the certified / violated / undecided masks per limit
     getFlightPenalty(esdf, ...)      [n_traj] limit + clearance penalty of the stored coefficients in one launch
     setSwarm(group_offsets, start_times)   which trajectories fly together (swarm g = trajectories group_offsets[g] .. group_offsets[g + 1];
@@ -1186,12 +1335,15 @@ class TrajOptimizer:
         self._lo = self._hi = None
         self._rows = None
         self._groups = self._start = None
+        self._moving = None
         self._coef = np.zeros(0)
         self.status = np.zeros(0, dtype=np.int32)
         self.iterations = np.zeros(0, dtype=np.int32)
         self.objective = np.zeros((0, 2))
         self.peak = np.zeros((0, 2))
         self.attitude_peak = np.zeros((0, 4))
+        self.min_gap = np.zeros(0)
+        self.nearest = np.zeros(0, dtype=np.int32)
         self.min_dist = np.zeros(0)
         self.outside = np.zeros(0, dtype=np.int32)
 
@@ -1361,6 +1513,63 @@ class TrajOptimizer:
         (self._wp, self._T, self._coef, self.status, self.objective, self.iterations, self.peak, self.min_dist, self.outside,
          self.attitude_peak) = ctx.attitude_optimize_host(self._r, self._so, self._wp, self._T, bc, esdf, limits=limits, clearance=clearance,
                                                           attitude=attitude, **params)
+        return bool(np.all(self.status == _lib.UAVQP_SOLVED))
+
+    def setMovingObstacles(self, times, coeff, seg_offsets=None, uniform_segments=0, start=None, radius=None, set_offsets=None, traj_set=None,
+                           traj_start=None):
+        """The moving obstacles the trajectories avoid (uavqp_moving_obstacles): tracks in the library's own format and the SAME order as
+        this optimiser -- times [sum Mo], coeff in the layout of getCoefficients(), seg_offsets [n_obs + 1] or uniform_segments -- with
+        their departures `start` and radii [n_obs] (None: zeros), the sets set_offsets [n_sets + 1] (None: one set, all of them), the set
+        each trajectory avoids traj_set [n_traj] (-1: none; None with one set: set 0) and the trajectories' own departures traj_start
+        [n_traj] (None: zeros).  times None removes them."""
+        if times is None:
+            self._moving = None
+            return
+        self._moving = dict(times=np.array(times, dtype=np.float64).ravel(), coeff=np.array(coeff, dtype=np.float64).ravel(),
+                            seg_offsets=None if seg_offsets is None else np.array(seg_offsets, dtype=np.int32).ravel(),
+                            uniform_segments=int(uniform_segments),
+                            start=None if start is None else np.array(start, dtype=np.float64).ravel(),
+                            radius=None if radius is None else np.array(radius, dtype=np.float64).ravel(),
+                            set_offsets=None if set_offsets is None else np.array(set_offsets, dtype=np.int32).ravel(),
+                            traj_set=None if traj_set is None else np.array(traj_set, dtype=np.int32).ravel(),
+                            traj_start=None if traj_start is None else np.array(traj_start, dtype=np.float64).ravel())
+
+    def getMovingPenalty(self, **params):
+        """[n_traj] penalty against the obstacles of setMovingObstacles() at the stored coefficients and durations
+        (uavqp_moving_penalty_host; after solve() or an optimiser); params: fields of uavqp_moving_params that differ from the defaults.
+        .min_gap [n_traj] and .nearest [n_traj] are filled with the smallest sampled gap and the obstacle that attains it."""
+        if self._moving is None:
+            raise _lib.UavqpError("getMovingPenalty: no obstacles (call setMovingObstacles() first)")
+        if self._ctx is None or self._coef.size != 3 * 2 * self._r * int(self._so[-1]) or self.status.size != self._so.size - 1:
+            raise _lib.UavqpError("getMovingPenalty: no solved coefficients (call solve() or an optimiser first)")
+        phi, _, _, _, self.min_gap, self.nearest = self._ctx.moving_penalty_host(self._r, self._so, self._T, self._coef, self._moving,
+                                                                                  status=self.status, **params)
+        return phi
+
+    def optimizeTrajectoryMoving(self, esdf, limits=None, clearance=None, attitude=None, moving=None, **params):
+        """optimizeTrajectoryAttitude with the penalty against the obstacles of setMovingObstacles() inside the objective
+        (uavqp_moving_optimize_host): the same bounds and members filled, and .min_gap / .nearest at the result.  attitude None: NO
+        attitude term ({}: its defaults); moving: dict of uavqp_moving_params fields; params: fields of uavqp_spacetime_lbfgs_params (an
+        unknown field of any raises ValueError).  The penalty is soft: check .min_gap (include/uavqp.h)."""
+        if self._lo is not None or self._rows is not None:
+            raise ValueError("optimizeTrajectoryMoving: corridor and general-rows problems are out of scope (include/uavqp.h)")
+        if self._moving is None:
+            raise _lib.UavqpError("optimizeTrajectoryMoving: no obstacles (call setMovingObstacles() first)")
+        Context._spacetime_lbfgs_params(params)   # (an unknown field is refused before anything runs)
+        Context._moving_params(moving or {})
+        if attitude is not None:
+            Context._attitude_params(attitude)
+        if self._wp is None or self._T is None:
+            return False
+        n_traj = self._so.size - 1
+        if self._T.size != int(self._so[-1]):
+            return False
+        bc = self._bc if self._bc is not None else np.zeros((n_traj, 2, self._r - 1, 3))
+        ctx = self.context()
+        (self._wp, self._T, self._coef, self.status, self.objective, self.iterations, self.peak, self.min_dist, self.outside,
+         self.attitude_peak, self.min_gap, self.nearest) = ctx.moving_optimize_host(
+             self._r, self._so, self._wp, self._T, bc, esdf, self._moving, limits=limits, clearance=clearance, attitude=attitude, moving=moving,
+             **params)
         return bool(np.all(self.status == _lib.UAVQP_SOLVED))
 
     def getAttitudePenalty(self, **params):
