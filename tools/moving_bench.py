@@ -8,7 +8,8 @@
    is what the moving-obstacle term costs: one launch per trial, and nothing else.
 2. Device time of one moving-obstacle penalty launch (all six outputs) with 1 and with 8 obstacles per set beside one
    uavqp_limit_penalty_device launch on the same buffers: `--launches` launches between two events after a warm-up, inputs and outputs
-   rotating through enough sets of buffers to exceed the 256 MB last-level cache.
+   rotating through enough sets of buffers to exceed the 256 MB last-level cache.  Beside each, `*_host_enqueue_us`: the host's wall time per
+   launch for enqueuing them (wrapper and C entry, before any synchronise) -- well under the device time, the figure is device-bound.
 
 Shape: 4096 x 8 segments, r = 4 (config 2) in the 200 x 200 x 50 map of tools/waypoint_opt_bench.py.  Obstacles: every trajectory has a
 set of its own of k one-segment tracks at constant velocity (about 1 m/s) that pass within 0.3 m of one of its interior waypoints at
@@ -182,16 +183,21 @@ def main():
             torch.cuda.synchronize()
             a, b_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
+            t0 = time.perf_counter()
             for k in range(args.launches):
                 fn(sets[k % rot])
+            host_us[fn].append(1e6 * (time.perf_counter() - t0) / args.launches)   # what the host took to ENQUEUE a launch
             b_.record()
             torch.cuda.synchronize()
             return 1e3 * a.elapsed_time(b_) / args.launches
-        us = {name: [timed(fn) for _ in range(5)] for name, fn in (("moving_1", moving(1)), ("moving_8", moving(8)), ("limit", limit))}
+        fns = (("moving_1", moving(1)), ("moving_8", moving(8)), ("limit", limit))
+        host_us = {fn: [] for _, fn in fns}
+        us = {name: [timed(fn) for _ in range(5)] for name, fn in fns}
         print(json.dumps(dict(measurement=2, shape=f"config2_{n}x{M}_r{r}", n_traj=n, segments=total, penalised_1=penalised[1],
                               penalised_8=penalised[8], launches=args.launches, buffer_sets=rot, bytes_per_set=one,
                               **{f"{k}_us": statistics.median(v) for k, v in us.items()}, **{f"{k}_us_min": min(v) for k, v in us.items()},
                               **{f"{k}_us_max": max(v) for k, v in us.items()},
+                              **{f"{name}_host_enqueue_us": statistics.median(host_us[fn]) for name, fn in fns},
                               ratio_1_to_limit=statistics.median(us["moving_1"]) / statistics.median(us["limit"]),
                               ratio_8_to_limit=statistics.median(us["moving_8"]) / statistics.median(us["limit"]))))
         m.close()

@@ -660,6 +660,7 @@ static int ensure_mapped(uavqp_ctx* ctx, size_t need) {
 }
 
 #include "uavqp_stage.h"
+#include "uavqp_solved.h"
 
 extern "C" int uavqp_solve_batch_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments,
                                       const int32_t* seg_offsets, const double* waypoints, const double* times,

@@ -19,26 +19,11 @@ static bool envelope_params_valid(const uavqp_envelope_params* p) {
     return true;
 }
 
-// the checks the two entries share; *skip: nothing to do (UAVQP_OK)
-static int envelope_args_check(const uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
-                               const double* coeff, const uavqp_envelope_params* params, const double* box_lo, const double* box_hi,
-                               bool any_output, bool* skip) {
-    *skip = false;
-    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!envelope_params_valid(params)) return UAVQP_ERR_INVALID_ARG;
-    if ((box_lo == nullptr) != (box_hi == nullptr)) return UAVQP_ERR_INVALID_ARG;
-    if (n_traj == 0 || !any_output) { *skip = true; return UAVQP_OK; }
-    if (!times || !coeff || (uniform_segments == 0 && !seg_offsets)) return UAVQP_ERR_INVALID_ARG;
-    return UAVQP_OK;
-}
-
 // (arguments checked by the callers)
-static int envelope_enqueue(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
-                            const double* d_coeff, const int32_t* d_status, const uavqp_envelope_params& P, const double* d_box_lo,
-                            const double* d_box_hi, double* d_range, double* d_norm, double* d_peak, int32_t* d_seg_verdict,
-                            int32_t* d_verdict) {
+static int envelope_enqueue(uavqp_ctx* ctx, const SolvedBatch& B, const uavqp_envelope_params& P, const double* d_box_lo, const double* d_box_hi,
+                            double* d_range, double* d_norm, double* d_peak, int32_t* d_seg_verdict, int32_t* d_verdict) {
     uavqp::EnvelopeArgs a;
-    a.n_traj = n_traj; a.uniform = uniform_segments; a.seg_offsets = d_seg_offsets; a.times = d_times; a.coeff = d_coeff; a.status = d_status;
+    solved_fill(a, B);
     a.box_lo = d_box_lo; a.box_hi = d_box_hi;
     a.range = d_range; a.norm = d_norm; a.peak = d_peak; a.seg_verdict = d_seg_verdict; a.verdict = d_verdict;
     a.depth = P.depth;
@@ -47,45 +32,41 @@ static int envelope_enqueue(uavqp_ctx* ctx, int r, int n_traj, int uniform_segme
     const double cs = std::cos(P.tilt_max);
     a.cos2 = cs * cs;
     a.tilt_on = P.tilt_max > 0.0 ? 1 : 0;
-    const int grid = topt_grid(ctx, n_traj);
-    if (r == 3)
-        hipLaunchKernelGGL(uavqp::envelope_kernel<3>, dim3(grid), dim3(64), 0, ctx->stream, a);
-    else
-        hipLaunchKernelGGL(uavqp::envelope_kernel<4>, dim3(grid), dim3(64), 0, ctx->stream, a);
-    UAVQP_HIP(hipGetLastError());
-    return UAVQP_OK;
+    const int grid = topt_grid(ctx, B.n_traj);
+    return dispatch_r(B.r, [&](auto R) {
+        hipLaunchKernelGGL(uavqp::envelope_kernel<decltype(R)::value>, dim3(grid), dim3(64), 0, ctx->stream, a);
+    });
 }
 
 extern "C" int uavqp_envelope_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
                                      const double* d_times, const double* d_coeff, const int32_t* d_status,
                                      const uavqp_envelope_params* params, const double* d_box_lo, const double* d_box_hi, double* d_range,
                                      double* d_norm, double* d_peak, int32_t* d_seg_verdict, int32_t* d_verdict) {
-    bool skip;
-    const int rc = envelope_args_check(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff, params, d_box_lo, d_box_hi,
-                                       d_range || d_norm || d_peak || d_seg_verdict || d_verdict, &skip);
-    if (rc != UAVQP_OK || skip) return rc;
+    const SolvedBatch B{r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff, d_status};
+    bool run;
+    const int rc = solved_args_check(ctx, B, [&] { return envelope_params_valid(params) && (d_box_lo == nullptr) == (d_box_hi == nullptr); },
+                                     d_range || d_norm || d_peak || d_seg_verdict || d_verdict, &run);
+    if (!run) return rc;
     UAVQP_HIP(hipSetDevice(ctx->device));
-    return envelope_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff, d_status, *params, d_box_lo, d_box_hi, d_range,
-                            d_norm, d_peak, d_seg_verdict, d_verdict);
+    return envelope_enqueue(ctx, B, *params, d_box_lo, d_box_hi, d_range, d_norm, d_peak, d_seg_verdict, d_verdict);
 }
 
 extern "C" int uavqp_envelope_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
                                    const double* coeff, const int32_t* status, const uavqp_envelope_params* params, const double* box_lo,
                                    const double* box_hi, double* range, double* norm, double* peak, int32_t* seg_verdict, int32_t* verdict) {
-    bool skip;
-    int rc = envelope_args_check(ctx, r, n_traj, uniform_segments, seg_offsets, times, coeff, params, box_lo, box_hi,
-                                 range || norm || peak || seg_verdict || verdict, &skip);
-    if (rc != UAVQP_OK || skip) return rc;
+    const SolvedBatch B{r, n_traj, uniform_segments, seg_offsets, times, coeff, status};
+    bool run;
+    int rc = solved_args_check(ctx, B, [&] { return envelope_params_valid(params) && (box_lo == nullptr) == (box_hi == nullptr); },
+                               range || norm || peak || seg_verdict || verdict, &run);
+    if (!run) return rc;
     BatchShape sh;
-    rc = batch_shape(n_traj, uniform_segments, 0, seg_offsets, &sh);
+    rc = solved_shape(B, &sh);
     if (rc != UAVQP_OK) return rc;
     UAVQP_HIP(hipSetDevice(ctx->device));
     const size_t n = (size_t)n_traj, tot = (size_t)sh.total_seg;
     Stage st;
-    const int i_off = uniform_segments > 0 ? -1 : st.in(seg_offsets, sizeof(int32_t) * (n + 1));
-    const int i_t = st.in(times, sizeof(double) * tot);
-    const int i_c = st.in(coeff, sizeof(double) * 3 * 2 * r * tot);
-    const int i_st = status ? st.in(status, sizeof(int32_t) * n) : -1;
+    SolvedStage in;
+    in.declare(st, B, sh);
     const int i_bl = box_lo ? st.in(box_lo, sizeof(double) * 3 * tot) : -1;
     const int i_bh = box_hi ? st.in(box_hi, sizeof(double) * 3 * tot) : -1;
     const int i_r = range ? st.out(range, sizeof(double) * 48 * tot) : -1;
@@ -95,8 +76,7 @@ extern "C" int uavqp_envelope_host(uavqp_ctx* ctx, int r, int n_traj, int unifor
     const int i_v = verdict ? st.out(verdict, sizeof(int32_t) * n) : -1;
     rc = stage_begin(ctx, st);
     if (rc != UAVQP_OK) return rc;
-    rc = envelope_enqueue(ctx, r, n_traj, uniform_segments, st.at<int32_t>(i_off), st.at<double>(i_t), st.at<double>(i_c),
-                          st.at<int32_t>(i_st), *params, st.at<double>(i_bl), st.at<double>(i_bh), st.at<double>(i_r), st.at<double>(i_n),
+    rc = envelope_enqueue(ctx, in.device(st), *params, st.at<double>(i_bl), st.at<double>(i_bh), st.at<double>(i_r), st.at<double>(i_n),
                           st.at<double>(i_p), st.at<int32_t>(i_sv), st.at<int32_t>(i_v));
     if (rc != UAVQP_OK) return rc;
     return stage_end(ctx, st, "uavqp_envelope_host");

@@ -23,63 +23,57 @@ static bool limit_params_valid(const uavqp_limit_params* p) {
 }
 
 // (arguments checked by the callers)
-static int limit_penalty_enqueue(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
-                                 const double* d_coeff, const int32_t* d_status, const uavqp_limit_params& L, double* d_penalty,
-                                 double* d_grad_coeff, double* d_grad_times, double* d_peak) {
+static int limit_penalty_enqueue(uavqp_ctx* ctx, const SolvedBatch& B, const uavqp_limit_params& L, double* d_penalty, double* d_grad_coeff,
+                                 double* d_grad_times, double* d_peak) {
     uavqp::LimitArgs a;
-    a.n_traj = n_traj; a.uniform = uniform_segments; a.seg_offsets = d_seg_offsets; a.times = d_times; a.coeff = d_coeff; a.status = d_status;
+    solved_fill(a, B);
     a.penalty = d_penalty; a.grad_coeff = d_grad_coeff; a.grad_times = d_grad_times; a.peak = d_peak;
     a.K = L.samples_per_seg;
-    a.al16 = ((((uintptr_t)d_coeff) | ((uintptr_t)d_grad_coeff)) & 15u) == 0 ? 1 : 0;
+    a.al16 = coeff_al16(B.coeff, d_grad_coeff);
     a.v_max = L.v_max; a.a_max = L.a_max; a.inv_v2 = 1.0 / (L.v_max * L.v_max); a.inv_a2 = 1.0 / (L.a_max * L.a_max);
     a.wv = L.weight_v; a.wa = L.weight_a;
-    const int grid = topt_grid(ctx, n_traj);
-    if (r == 3)
-        hipLaunchKernelGGL(uavqp::limit_penalty_kernel<3>, dim3(grid), dim3(64), 0, ctx->stream, a);
-    else
-        hipLaunchKernelGGL(uavqp::limit_penalty_kernel<4>, dim3(grid), dim3(64), 0, ctx->stream, a);
-    UAVQP_HIP(hipGetLastError());
-    return UAVQP_OK;
+    const int grid = topt_grid(ctx, B.n_traj);
+    return dispatch_r(B.r, [&](auto R) {
+        hipLaunchKernelGGL(uavqp::limit_penalty_kernel<decltype(R)::value>, dim3(grid), dim3(64), 0, ctx->stream, a);
+    });
 }
 
 extern "C" int uavqp_limit_penalty_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
                                           const double* d_times, const double* d_coeff, const int32_t* d_status,
                                           const uavqp_limit_params* params, double* d_penalty, double* d_grad_coeff, double* d_grad_times,
                                           double* d_peak) {
-    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!limit_params_valid(params)) return UAVQP_ERR_INVALID_ARG;
-    if (n_traj == 0 || (!d_penalty && !d_grad_coeff && !d_grad_times && !d_peak)) return UAVQP_OK;
-    if (!d_times || !d_coeff || (uniform_segments == 0 && !d_seg_offsets)) return UAVQP_ERR_INVALID_ARG;
+    const SolvedBatch B{r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff, d_status};
+    bool run;
+    const int rc = solved_args_check(ctx, B, [&] { return limit_params_valid(params); },
+                                     d_penalty || d_grad_coeff || d_grad_times || d_peak, &run);
+    if (!run) return rc;
     UAVQP_HIP(hipSetDevice(ctx->device));
-    return limit_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff, d_status, *params, d_penalty, d_grad_coeff,
-                                 d_grad_times, d_peak);
+    return limit_penalty_enqueue(ctx, B, *params, d_penalty, d_grad_coeff, d_grad_times, d_peak);
 }
 
 extern "C" int uavqp_limit_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
                                         const double* coeff, const int32_t* status, const uavqp_limit_params* params, double* penalty,
                                         double* grad_coeff, double* grad_times, double* peak) {
-    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!limit_params_valid(params)) return UAVQP_ERR_INVALID_ARG;
-    if (n_traj == 0 || (!penalty && !grad_coeff && !grad_times && !peak)) return UAVQP_OK;
-    if (!times || !coeff || (uniform_segments == 0 && !seg_offsets)) return UAVQP_ERR_INVALID_ARG;
+    const SolvedBatch B{r, n_traj, uniform_segments, seg_offsets, times, coeff, status};
+    bool run;
+    int rc = solved_args_check(ctx, B, [&] { return limit_params_valid(params); },
+                               penalty || grad_coeff || grad_times || peak, &run);
+    if (!run) return rc;
     BatchShape sh;
-    int rc = batch_shape(n_traj, uniform_segments, 0, seg_offsets, &sh);
+    rc = solved_shape(B, &sh);
     if (rc != UAVQP_OK) return rc;
     UAVQP_HIP(hipSetDevice(ctx->device));
     const size_t n = (size_t)n_traj, tot = (size_t)sh.total_seg;
     Stage st;
-    const int i_off = uniform_segments > 0 ? -1 : st.in(seg_offsets, sizeof(int32_t) * (n + 1));
-    const int i_t = st.in(times, sizeof(double) * tot);
-    const int i_c = st.in(coeff, sizeof(double) * 3 * 2 * r * tot);
-    const int i_st = status ? st.in(status, sizeof(int32_t) * n) : -1;
+    SolvedStage in;
+    in.declare(st, B, sh);
     const int i_p = penalty ? st.out(penalty, sizeof(double) * n) : -1;
     const int i_g = grad_coeff ? st.out(grad_coeff, sizeof(double) * 3 * 2 * r * tot) : -1;
     const int i_gt = grad_times ? st.out(grad_times, sizeof(double) * tot) : -1;
     const int i_pk = peak ? st.out(peak, sizeof(double) * 2 * n) : -1;
     rc = stage_begin(ctx, st);
     if (rc != UAVQP_OK) return rc;
-    rc = limit_penalty_enqueue(ctx, r, n_traj, uniform_segments, st.at<int32_t>(i_off), st.at<double>(i_t), st.at<double>(i_c),
-                               st.at<int32_t>(i_st), *params, st.at<double>(i_p), st.at<double>(i_g), st.at<double>(i_gt), st.at<double>(i_pk));
+    rc = limit_penalty_enqueue(ctx, in.device(st), *params, st.at<double>(i_p), st.at<double>(i_g), st.at<double>(i_gt), st.at<double>(i_pk));
     if (rc != UAVQP_OK) return rc;
     return stage_end(ctx, st, "uavqp_limit_penalty_host");
 }

@@ -84,31 +84,23 @@ struct MovingStage {
 
 // (arguments checked by the callers)  accumulate (uavqp_moving_optimize_device only, not in the C ABI): penalty, grad_coeff and grad_times
 // are ADDED to what the arrays hold
-static int moving_penalty_enqueue(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
-                                  const double* d_coeff, const int32_t* d_status, const uavqp_moving_obstacles& O, const uavqp_moving_params& P,
+static int moving_penalty_enqueue(uavqp_ctx* ctx, const SolvedBatch& B, const uavqp_moving_obstacles& O, const uavqp_moving_params& P,
                                   double* d_penalty, double* d_grad_coeff, double* d_grad_times, double* d_grad_start, double* d_min_gap,
                                   int32_t* d_nearest, bool accumulate = false) {
     uavqp::MovingArgs a;
-    a.n_traj = n_traj; a.uniform = uniform_segments; a.seg_offsets = d_seg_offsets; a.times = d_times; a.coeff = d_coeff; a.status = d_status;
+    solved_fill(a, B);
     a.n_obs = O.n_obs; a.o_uniform = O.uniform_segments; a.n_sets = O.n_sets; a.o_seg_offsets = O.seg_offsets; a.o_times = O.times;
     a.o_coeff = O.coeff; a.o_start = O.start; a.o_radius = O.radius; a.set_offsets = O.set_offsets; a.traj_set = O.traj_set;
     a.traj_start = O.traj_start;
     a.penalty = d_penalty; a.grad_coeff = d_grad_coeff; a.grad_times = d_grad_times; a.grad_start = d_grad_start; a.min_gap = d_min_gap;
     a.nearest = d_nearest;
     a.K = P.samples_per_seg;
-    a.al16 = ((((uintptr_t)d_coeff) | ((uintptr_t)d_grad_coeff)) & 15u) == 0 ? 1 : 0;
+    a.al16 = coeff_al16(B.coeff, d_grad_coeff);
     a.d_safe = P.d_safe; a.inv_dw2 = 1.0 / (P.downwash * P.downwash); a.weight = P.weight;
-    const int grid = topt_grid(ctx, n_traj);
-    if (accumulate && r == 3)
-        hipLaunchKernelGGL((uavqp::moving_penalty_kernel<3, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
-    else if (accumulate)
-        hipLaunchKernelGGL((uavqp::moving_penalty_kernel<4, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
-    else if (r == 3)
-        hipLaunchKernelGGL((uavqp::moving_penalty_kernel<3, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
-    else
-        hipLaunchKernelGGL((uavqp::moving_penalty_kernel<4, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
-    UAVQP_HIP(hipGetLastError());
-    return UAVQP_OK;
+    const int grid = topt_grid(ctx, B.n_traj);
+    return dispatch_r_flag(B.r, accumulate, [&](auto R, auto ACC) {
+        hipLaunchKernelGGL((uavqp::moving_penalty_kernel<decltype(R)::value, decltype(ACC)::value>), dim3(grid), dim3(64), 0, ctx->stream, a);
+    });
 }
 
 extern "C" int uavqp_moving_penalty_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
@@ -116,34 +108,33 @@ extern "C" int uavqp_moving_penalty_device(uavqp_ctx* ctx, int r, int n_traj, in
                                            const uavqp_moving_obstacles* obstacles, const uavqp_moving_params* params, double* d_penalty,
                                            double* d_grad_coeff, double* d_grad_times, double* d_grad_start, double* d_min_gap,
                                            int32_t* d_nearest) {
-    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!moving_params_valid(params) || !moving_obstacles_valid(obstacles)) return UAVQP_ERR_INVALID_ARG;
-    if (n_traj == 0 || (!d_penalty && !d_grad_coeff && !d_grad_times && !d_grad_start && !d_min_gap && !d_nearest)) return UAVQP_OK;
-    if (!d_times || !d_coeff || (uniform_segments == 0 && !d_seg_offsets)) return UAVQP_ERR_INVALID_ARG;
+    const SolvedBatch B{r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff, d_status};
+    bool run;
+    const int rc = solved_args_check(ctx, B, [&] { return moving_params_valid(params) && moving_obstacles_valid(obstacles); },
+                                     d_penalty || d_grad_coeff || d_grad_times || d_grad_start || d_min_gap || d_nearest, &run);
+    if (!run) return rc;
     UAVQP_HIP(hipSetDevice(ctx->device));
-    return moving_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff, d_status, *obstacles, *params, d_penalty,
-                                  d_grad_coeff, d_grad_times, d_grad_start, d_min_gap, d_nearest);
+    return moving_penalty_enqueue(ctx, B, *obstacles, *params, d_penalty, d_grad_coeff, d_grad_times, d_grad_start, d_min_gap, d_nearest);
 }
 
 extern "C" int uavqp_moving_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets,
                                          const double* times, const double* coeff, const int32_t* status,
                                          const uavqp_moving_obstacles* obstacles, const uavqp_moving_params* params, double* penalty,
                                          double* grad_coeff, double* grad_times, double* grad_start, double* min_gap, int32_t* nearest) {
-    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!moving_params_valid(params) || !moving_obstacles_valid(obstacles)) return UAVQP_ERR_INVALID_ARG;
-    if (n_traj == 0 || (!penalty && !grad_coeff && !grad_times && !grad_start && !min_gap && !nearest)) return UAVQP_OK;
-    if (!times || !coeff || (uniform_segments == 0 && !seg_offsets)) return UAVQP_ERR_INVALID_ARG;
+    const SolvedBatch B{r, n_traj, uniform_segments, seg_offsets, times, coeff, status};
+    bool run;
+    int rc = solved_args_check(ctx, B, [&] { return moving_params_valid(params) && moving_obstacles_valid(obstacles); },
+                               penalty || grad_coeff || grad_times || grad_start || min_gap || nearest, &run);
+    if (!run) return rc;
     BatchShape sh, osh;
-    int rc = batch_shape(n_traj, uniform_segments, 0, seg_offsets, &sh);
+    rc = solved_shape(B, &sh);
     if (rc == UAVQP_OK) rc = moving_host_check(*obstacles, n_traj, &osh);
     if (rc != UAVQP_OK) return rc;
     UAVQP_HIP(hipSetDevice(ctx->device));
     const size_t n = (size_t)n_traj, tot = (size_t)sh.total_seg;
     Stage st;
-    const int i_off = uniform_segments > 0 ? -1 : st.in(seg_offsets, sizeof(int32_t) * (n + 1));
-    const int i_t = st.in(times, sizeof(double) * tot);
-    const int i_c = st.in(coeff, sizeof(double) * 3 * 2 * r * tot);
-    const int i_st = status ? st.in(status, sizeof(int32_t) * n) : -1;
+    SolvedStage in;
+    in.declare(st, B, sh);
     MovingStage ms;
     ms.declare(st, *obstacles, r, n_traj, osh);
     const int i_p = penalty ? st.out(penalty, sizeof(double) * n) : -1;
@@ -154,9 +145,7 @@ extern "C" int uavqp_moving_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int 
     const int i_nr = nearest ? st.out(nearest, sizeof(int32_t) * n) : -1;
     rc = stage_begin(ctx, st);
     if (rc != UAVQP_OK) return rc;
-    const uavqp_moving_obstacles dev = ms.device(st, *obstacles);
-    rc = moving_penalty_enqueue(ctx, r, n_traj, uniform_segments, st.at<int32_t>(i_off), st.at<double>(i_t), st.at<double>(i_c),
-                                st.at<int32_t>(i_st), dev, *params, st.at<double>(i_p), st.at<double>(i_g), st.at<double>(i_gt),
+    rc = moving_penalty_enqueue(ctx, in.device(st), ms.device(st, *obstacles), *params, st.at<double>(i_p), st.at<double>(i_g), st.at<double>(i_gt),
                                 st.at<double>(i_gs), st.at<double>(i_mg), st.at<int32_t>(i_nr));
     if (rc != UAVQP_OK) return rc;
     return stage_end(ctx, st, "uavqp_moving_penalty_host");

@@ -64,61 +64,56 @@ static bool flight_params_valid(const uavqp_ctx* ctx, const uavqp_esdf* esdf, co
 }
 
 // (arguments checked by the callers)
-static int flight_penalty_enqueue(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
-                                  const double* d_coeff, const int32_t* d_status, const uavqp_esdf* esdf, const uavqp_limit_params& L,
+static int flight_penalty_enqueue(uavqp_ctx* ctx, const SolvedBatch& B, const uavqp_esdf* esdf, const uavqp_limit_params& L,
                                   const uavqp_clearance_params& C, double* d_penalty, double* d_grad_coeff, double* d_grad_times, double* d_peak,
                                   double* d_min_dist, int32_t* d_outside) {
     uavqp::FlightArgs a;
-    a.n_traj = n_traj; a.uniform = uniform_segments; a.seg_offsets = d_seg_offsets; a.times = d_times; a.coeff = d_coeff; a.status = d_status;
+    solved_fill(a, B);
     a.penalty = d_penalty; a.grad_coeff = d_grad_coeff; a.grad_times = d_grad_times; a.peak = d_peak; a.min_dist = d_min_dist; a.outside = d_outside;
     a.K_lim = L.samples_per_seg; a.K_clr = C.samples_per_seg;
-    a.al16 = ((((uintptr_t)d_coeff) | ((uintptr_t)d_grad_coeff)) & 15u) == 0 ? 1 : 0;
+    a.al16 = coeff_al16(B.coeff, d_grad_coeff);
     a.do_lim = (L.weight_v > 0.0 || L.weight_a > 0.0 || d_peak) ? 1 : 0;
     a.do_clr = (C.weight > 0.0 || d_min_dist || d_outside) ? 1 : 0;
     a.v_max = L.v_max; a.a_max = L.a_max; a.inv_v2 = 1.0 / (L.v_max * L.v_max); a.inv_a2 = 1.0 / (L.a_max * L.a_max);
     a.wv = L.weight_v; a.wa = L.weight_a;
     a.d_safe = C.d_safe; a.inv_safe = 1.0 / C.d_safe; a.weight = C.weight;
     a.map = esdf_view(esdf);
-    const int grid = topt_grid(ctx, n_traj);
-    if (r == 3)
-        hipLaunchKernelGGL(uavqp::flight_penalty_kernel<3>, dim3(grid), dim3(64), 0, ctx->stream, a);
-    else
-        hipLaunchKernelGGL(uavqp::flight_penalty_kernel<4>, dim3(grid), dim3(64), 0, ctx->stream, a);
-    UAVQP_HIP(hipGetLastError());
-    return UAVQP_OK;
+    const int grid = topt_grid(ctx, B.n_traj);
+    return dispatch_r(B.r, [&](auto R) {
+        hipLaunchKernelGGL(uavqp::flight_penalty_kernel<decltype(R)::value>, dim3(grid), dim3(64), 0, ctx->stream, a);
+    });
 }
 
 extern "C" int uavqp_flight_penalty_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
                                            const double* d_times, const double* d_coeff, const int32_t* d_status, const uavqp_esdf* esdf,
                                            const uavqp_limit_params* limits, const uavqp_clearance_params* clearance, double* d_penalty,
                                            double* d_grad_coeff, double* d_grad_times, double* d_peak, double* d_min_dist, int32_t* d_outside) {
-    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!flight_params_valid(ctx, esdf, limits, clearance)) return UAVQP_ERR_INVALID_ARG;
-    if (n_traj == 0 || (!d_penalty && !d_grad_coeff && !d_grad_times && !d_peak && !d_min_dist && !d_outside)) return UAVQP_OK;
-    if (!d_times || !d_coeff || (uniform_segments == 0 && !d_seg_offsets)) return UAVQP_ERR_INVALID_ARG;
+    const SolvedBatch B{r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff, d_status};
+    bool run;
+    const int rc = solved_args_check(ctx, B, [&] { return flight_params_valid(ctx, esdf, limits, clearance); },
+                                     d_penalty || d_grad_coeff || d_grad_times || d_peak || d_min_dist || d_outside, &run);
+    if (!run) return rc;
     UAVQP_HIP(hipSetDevice(ctx->device));
-    return flight_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff, d_status, esdf, *limits, *clearance, d_penalty,
-                                  d_grad_coeff, d_grad_times, d_peak, d_min_dist, d_outside);
+    return flight_penalty_enqueue(ctx, B, esdf, *limits, *clearance, d_penalty, d_grad_coeff, d_grad_times, d_peak, d_min_dist, d_outside);
 }
 
 extern "C" int uavqp_flight_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
                                          const double* coeff, const int32_t* status, const uavqp_esdf* esdf, const uavqp_limit_params* limits,
                                          const uavqp_clearance_params* clearance, double* penalty, double* grad_coeff, double* grad_times,
                                          double* peak, double* min_dist, int32_t* outside) {
-    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!flight_params_valid(ctx, esdf, limits, clearance)) return UAVQP_ERR_INVALID_ARG;
-    if (n_traj == 0 || (!penalty && !grad_coeff && !grad_times && !peak && !min_dist && !outside)) return UAVQP_OK;
-    if (!times || !coeff || (uniform_segments == 0 && !seg_offsets)) return UAVQP_ERR_INVALID_ARG;
+    const SolvedBatch B{r, n_traj, uniform_segments, seg_offsets, times, coeff, status};
+    bool run;
+    int rc = solved_args_check(ctx, B, [&] { return flight_params_valid(ctx, esdf, limits, clearance); },
+                               penalty || grad_coeff || grad_times || peak || min_dist || outside, &run);
+    if (!run) return rc;
     BatchShape sh;
-    int rc = batch_shape(n_traj, uniform_segments, 0, seg_offsets, &sh);
+    rc = solved_shape(B, &sh);
     if (rc != UAVQP_OK) return rc;
     UAVQP_HIP(hipSetDevice(ctx->device));
     const size_t n = (size_t)n_traj, tot = (size_t)sh.total_seg;
     Stage st;
-    const int i_off = uniform_segments > 0 ? -1 : st.in(seg_offsets, sizeof(int32_t) * (n + 1));
-    const int i_t = st.in(times, sizeof(double) * tot);
-    const int i_c = st.in(coeff, sizeof(double) * 3 * 2 * r * tot);
-    const int i_st = status ? st.in(status, sizeof(int32_t) * n) : -1;
+    SolvedStage in;
+    in.declare(st, B, sh);
     const int i_p = penalty ? st.out(penalty, sizeof(double) * n) : -1;
     const int i_g = grad_coeff ? st.out(grad_coeff, sizeof(double) * 3 * 2 * r * tot) : -1;
     const int i_gt = grad_times ? st.out(grad_times, sizeof(double) * tot) : -1;
@@ -127,8 +122,7 @@ extern "C" int uavqp_flight_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int 
     const int i_o = outside ? st.out(outside, sizeof(int32_t) * n) : -1;
     rc = stage_begin(ctx, st);
     if (rc != UAVQP_OK) return rc;
-    rc = flight_penalty_enqueue(ctx, r, n_traj, uniform_segments, st.at<int32_t>(i_off), st.at<double>(i_t), st.at<double>(i_c),
-                                st.at<int32_t>(i_st), esdf, *limits, *clearance, st.at<double>(i_p), st.at<double>(i_g), st.at<double>(i_gt),
+    rc = flight_penalty_enqueue(ctx, in.device(st), esdf, *limits, *clearance, st.at<double>(i_p), st.at<double>(i_g), st.at<double>(i_gt),
                                 st.at<double>(i_pk), st.at<double>(i_md), st.at<int32_t>(i_o));
     if (rc != UAVQP_OK) return rc;
     return stage_end(ctx, st, "uavqp_flight_penalty_host");
@@ -170,6 +164,9 @@ struct JointRun {
     const double* t_at(const DescentPoint& p) const { return p.at == DescentAt::TRIAL ? trial_t(p.it) : d_times; }
     int32_t* status_at(const DescentPoint& p) const { return p.caller_status && d_status_out ? d_status_out : at<int32_t>(k.st); }
     int32_t* status_final() const { return status_at(DescentPoint{DescentAt::FINAL, -1, true}); }   // (of what is handed back)
+    // the solved batch at a point of the sequence, and the one that is handed back, as the penalties take it
+    SolvedBatch solved_at(const DescentPoint& p) const { return SolvedBatch{r, n_traj, uniform_segments, d_seg_offsets, t_at(p), d_coeff_out, status_at(p)}; }
+    SolvedBatch solved_final() const { return SolvedBatch{r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, status_final()}; }
 
     // the identically named fields of SpacetimeArgs and SwarmOptArgs, the ten scalar parameters included
     template <class Args, class Params>
@@ -206,8 +203,8 @@ struct JointRun {
     }
     // the penalty of the point `coeff` was solved at and its two partial gradients ...
     int flight_penalty(const DescentPoint& p) const {
-        return flight_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, t_at(p), d_coeff_out, status_at(p), esdf, *limits, *clearance,
-                                      at<double>(k.ph), at<double>(k.g), at<double>(k.ex), nullptr, nullptr, nullptr);
+        return flight_penalty_enqueue(ctx, solved_at(p), esdf, *limits, *clearance, at<double>(k.ph), at<double>(k.g), at<double>(k.ex), nullptr,
+                                      nullptr, nullptr);
     }
     // ... and the coefficient gradient taken through the minimiser to the waypoints and the durations by ONE backward pass
     int backward(const DescentPoint& p) const {
@@ -215,7 +212,7 @@ struct JointRun {
                                            d_coeff_out, status_at(p), at<double>(k.g), at<double>(k.tht), at<double>(k.thp), nullptr);
     }
     // The sequence of all three: `a` is the entry's step arguments, more_penalty(point) what it accumulates on the flight penalty before the
-    // backward pass, launch(R, INIT) its step kernel (step_dispatch).
+    // backward pass, launch(R, INIT) its step kernel (dispatch_r_flag).
     template <class Args, class Penalty, class Launch>
     int descend(Args& a, int max_iters, Penalty&& more_penalty, Launch&& launch) const {
         return descent_sequence(
@@ -227,14 +224,14 @@ struct JointRun {
             },
             [&](bool init, int it, bool propose) -> int {
                 before_step(a, init, it, propose);
-                return step_dispatch(r, init, launch);
+                return dispatch_r_flag(r, init, launch);
             });
     }
     // the penalty's diagnostics of what is handed back
     int flight_diagnostics(double* d_peak_out, double* d_min_dist_out, int32_t* d_outside_out) const {
         if (!d_peak_out && !d_min_dist_out && !d_outside_out) return UAVQP_OK;
-        return flight_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, status_final(), esdf, *limits, *clearance,
-                                      nullptr, nullptr, nullptr, d_peak_out, d_min_dist_out, d_outside_out);
+        return flight_penalty_enqueue(ctx, solved_final(), esdf, *limits, *clearance, nullptr, nullptr, nullptr, d_peak_out, d_min_dist_out,
+                                      d_outside_out);
     }
 };
 

@@ -99,11 +99,11 @@ static int spacetime_lbfgs_run(uavqp_ctx* ctx, int r, int n_traj, int uniform_se
     auto attitude_penalty = [&](const DescentPoint& p) -> int {
         int e = UAVQP_OK;
         if (with_attitude)
-            e = attitude_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, j.t_at(p), d_coeff_out, j.status_at(p), *attitude,
-                                         j.at<double>(j.k.ph), j.at<double>(j.k.g), j.at<double>(j.k.ex), nullptr, true);
+            e = attitude_penalty_enqueue(ctx, j.solved_at(p), *attitude, j.at<double>(j.k.ph), j.at<double>(j.k.g), j.at<double>(j.k.ex), nullptr,
+                                         true);
         if (e == UAVQP_OK && with_moving)
-            e = moving_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, j.t_at(p), d_coeff_out, j.status_at(p), *obstacles, *moving,
-                                       j.at<double>(j.k.ph), j.at<double>(j.k.g), j.at<double>(j.k.ex), nullptr, nullptr, nullptr, true);
+            e = moving_penalty_enqueue(ctx, j.solved_at(p), *obstacles, *moving, j.at<double>(j.k.ph), j.at<double>(j.k.g), j.at<double>(j.k.ex),
+                                       nullptr, nullptr, nullptr, true);
         return e;
     };
     rc = j.anchor_copies(P.max_iters);
@@ -115,11 +115,9 @@ static int spacetime_lbfgs_run(uavqp_ctx* ctx, int r, int n_traj, int uniform_se
         });
     if (rc == UAVQP_OK) rc = j.flight_diagnostics(d_peak_out, d_min_dist_out, d_outside_out);
     if (rc == UAVQP_OK && attitude && d_attitude_peak_out)
-        rc = attitude_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, j.status_final(), *attitude, nullptr,
-                                      nullptr, nullptr, d_attitude_peak_out);
+        rc = attitude_penalty_enqueue(ctx, j.solved_final(), *attitude, nullptr, nullptr, nullptr, d_attitude_peak_out);
     if (rc == UAVQP_OK && moving && (d_min_gap_out || d_nearest_out))
-        rc = moving_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, j.status_final(), *obstacles, *moving,
-                                    nullptr, nullptr, nullptr, nullptr, d_min_gap_out, d_nearest_out);
+        rc = moving_penalty_enqueue(ctx, j.solved_final(), *obstacles, *moving, nullptr, nullptr, nullptr, nullptr, d_min_gap_out, d_nearest_out);
     return rc;
 }
 

@@ -30,6 +30,7 @@ static int batch_shape(int n_traj, int uniform_segments, int max_segments, const
     return UAVQP_OK;
 }
 
+#ifdef UAVQP_HIP   // (as in uavqp_ws.h: batch_shape and the declarations of a Stage compile without the HIP runtime)
 // Completion of the latency paths without a stream synchronisation: a one-thread kernel behind the work stamps the word at the head of
 // the mapped page, the host polls it (await_host_word).
 static int await_mapped_page(uavqp_ctx* ctx, const char* who) {
@@ -40,6 +41,8 @@ static int await_mapped_page(uavqp_ctx* ctx, const char* who) {
     hipLaunchKernelGGL(uavqp::host_word_kernel, dim3(1), dim3(1), 0, ctx->stream, (const int32_t*)nullptr, (volatile unsigned long long*)ctx->d_axis, seq);
     return await_host_word(ctx->stream, h_word, seq, nullptr, who);
 }
+
+#endif
 
 // The arrays of one call: where each lies is the carver's business (uavqp_ws.h: declaration order, 256-byte boundaries, handle -1 = an
 // array this call does not have = a null pointer); Stage adds what is copied where.  The pointers are good for this call only.
@@ -68,6 +71,7 @@ struct Stage {
     T* at(int i) const { return lay.at<T>(i); }
 };
 
+#ifdef UAVQP_HIP
 // mapped: the latency route -- the batch lives in the pinned page that is mapped into the device (behind MAPPED_HEAD: the completion
 // word has a FIXED slot no payload ever aliases), an upload is a memcpy into the page and the kernels work over the host link.
 static int stage_begin(uavqp_ctx* ctx, Stage& st, bool mapped = false) {
@@ -105,3 +109,4 @@ static int stage_end(uavqp_ctx* ctx, const Stage& st, const char* who) {
     if (!mapped) UAVQP_HIP(hipStreamSynchronize(ctx->stream));
     return UAVQP_OK;
 }
+#endif

@@ -24,30 +24,26 @@ static bool swarm_params_valid(const uavqp_swarm_params* p) {
     return true;
 }
 
-// what both entries refuse before they look at a pointer's contents; *nothing = a valid call with nothing to do
-static int swarm_args_check(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
-                            const double* coeff, int n_groups, const int32_t* group_offsets, const uavqp_swarm_params* params, bool any_out,
-                            bool* nothing) {
-    *nothing = false;
-    if (!ctx || (r != 3 && r != 4) || n_traj < 0 || uniform_segments < 0 || n_groups < 0) return UAVQP_ERR_INVALID_ARG;
-    if (!swarm_params_valid(params)) return UAVQP_ERR_INVALID_ARG;
-    if (!group_offsets && n_groups != 1) return UAVQP_ERR_INVALID_ARG;
-    if (n_groups == 0 || !any_out) {
-        *nothing = true;
-        return UAVQP_OK;
+// What the _host swarm entries (this file, uavqp_separation_cert.h) check in the offsets the device trusts: ascending from 0 to n_traj,
+// no swarm larger than the kernel's lanes.
+static int swarm_groups_host_check(int n_traj, int n_groups, const int32_t* group_offsets) {
+    if (!group_offsets) return n_traj > UAVQP_SWARM_MAX_VEHICLES ? UAVQP_ERR_INVALID_ARG : UAVQP_OK;
+    if (group_offsets[0] != 0 || group_offsets[n_groups] != n_traj) return UAVQP_ERR_INVALID_ARG;
+    for (int g = 0; g < n_groups; ++g) {
+        const long long A = (long long)group_offsets[g + 1] - group_offsets[g];
+        if (A < 0 || A > UAVQP_SWARM_MAX_VEHICLES) return UAVQP_ERR_INVALID_ARG;
     }
-    if (n_traj > 0 && (!times || !coeff || (uniform_segments == 0 && !seg_offsets))) return UAVQP_ERR_INVALID_ARG;
     return UAVQP_OK;
 }
 
-// (arguments checked by the callers)
-static int swarm_penalty_enqueue(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
-                                 const double* d_coeff, const int32_t* d_status, int n_groups, const int32_t* d_group_offsets,
-                                 const double* d_start, const uavqp_swarm_params& S, double* d_penalty, double* d_grad_coeff,
-                                 double* d_grad_times, double* d_grad_start, double* d_min_sep, bool accumulate = false) {
+// (arguments checked by the callers)  accumulate (uavqp_swarm_opt.h only, not in the C ABI): grad_coeff and grad_times are ADDED to what
+// the arrays hold
+static int swarm_penalty_enqueue(uavqp_ctx* ctx, const SolvedBatch& B, int n_groups, const int32_t* d_group_offsets, const double* d_start,
+                                 const uavqp_swarm_params& S, double* d_penalty, double* d_grad_coeff, double* d_grad_times, double* d_grad_start,
+                                 double* d_min_sep, bool accumulate = false) {
     uavqp::SwarmArgs a;
-    a.n_traj = n_traj; a.uniform = uniform_segments; a.n_groups = n_groups; a.seg_offsets = d_seg_offsets; a.group_offsets = d_group_offsets;
-    a.times = d_times; a.coeff = d_coeff; a.status = d_status; a.start = d_start;
+    solved_fill(a, B);
+    a.n_groups = n_groups; a.group_offsets = d_group_offsets; a.start = d_start;
     a.penalty = d_penalty; a.grad_coeff = d_grad_coeff; a.grad_times = d_grad_times; a.grad_start = d_grad_start; a.min_sep = d_min_sep;
     a.N = S.n_samples; a.clock_start = S.clock_start; a.dt = S.dt; a.d_safe = S.d_safe;
     a.inv_d2 = 1.0 / (S.d_safe * S.d_safe); a.inv_dw2 = 1.0 / (S.downwash * S.downwash);
@@ -55,17 +51,10 @@ static int swarm_penalty_enqueue(uavqp_ctx* ctx, int r, int n_traj, int uniform_
     // one workgroup per swarm, grid-stride past 5 resident workgroups per CU (the LDS of qp_swarm.h)
     const int cap = ctx->num_cus * 5;
     const int grid = n_groups < cap ? n_groups : cap;
-    // accumulate (uavqp_swarm_opt.h only, not in the C ABI): grad_coeff and grad_times are ADDED to what the arrays hold
-    if (accumulate && r == 3)
-        hipLaunchKernelGGL((uavqp::swarm_penalty_kernel<3, true>), dim3(grid), dim3(uavqp::SWARM_BLOCK), 0, ctx->stream, a);
-    else if (accumulate)
-        hipLaunchKernelGGL((uavqp::swarm_penalty_kernel<4, true>), dim3(grid), dim3(uavqp::SWARM_BLOCK), 0, ctx->stream, a);
-    else if (r == 3)
-        hipLaunchKernelGGL(uavqp::swarm_penalty_kernel<3>, dim3(grid), dim3(uavqp::SWARM_BLOCK), 0, ctx->stream, a);
-    else
-        hipLaunchKernelGGL(uavqp::swarm_penalty_kernel<4>, dim3(grid), dim3(uavqp::SWARM_BLOCK), 0, ctx->stream, a);
-    UAVQP_HIP(hipGetLastError());
-    return UAVQP_OK;
+    return dispatch_r_flag(B.r, accumulate, [&](auto R, auto ACC) {
+        hipLaunchKernelGGL((uavqp::swarm_penalty_kernel<decltype(R)::value, decltype(ACC)::value>), dim3(grid), dim3(uavqp::SWARM_BLOCK), 0,
+                           ctx->stream, a);
+    });
 }
 
 extern "C" int uavqp_swarm_penalty_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
@@ -73,45 +62,36 @@ extern "C" int uavqp_swarm_penalty_device(uavqp_ctx* ctx, int r, int n_traj, int
                                           const int32_t* d_group_offsets, const double* d_start, const uavqp_swarm_params* params,
                                           double* d_penalty, double* d_grad_coeff, double* d_grad_times, double* d_grad_start,
                                           double* d_min_sep) {
-    bool nothing;
-    const int rc = swarm_args_check(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff, n_groups, d_group_offsets, params,
-                                    d_penalty || d_grad_coeff || d_grad_times || d_grad_start || d_min_sep, &nothing);
-    if (rc != UAVQP_OK || nothing) return rc;
+    const SolvedBatch B{r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff, d_status};
+    bool run;
+    const SolvedGroups G{n_groups, d_group_offsets};
+    const int rc = solved_args_check(ctx, B, [&] { return swarm_params_valid(params); },
+                                     d_penalty || d_grad_coeff || d_grad_times || d_grad_start || d_min_sep, &run, &G);
+    if (!run) return rc;
     UAVQP_HIP(hipSetDevice(ctx->device));
-    return swarm_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff, d_status, n_groups, d_group_offsets, d_start,
-                                 *params, d_penalty, d_grad_coeff, d_grad_times, d_grad_start, d_min_sep);
+    return swarm_penalty_enqueue(ctx, B, n_groups, d_group_offsets, d_start, *params, d_penalty, d_grad_coeff, d_grad_times, d_grad_start,
+                                 d_min_sep);
 }
 
 extern "C" int uavqp_swarm_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
                                         const double* coeff, const int32_t* status, int n_groups, const int32_t* group_offsets,
                                         const double* start, const uavqp_swarm_params* params, double* penalty, double* grad_coeff,
                                         double* grad_times, double* grad_start, double* min_sep) {
-    bool nothing;
-    int rc = swarm_args_check(ctx, r, n_traj, uniform_segments, seg_offsets, times, coeff, n_groups, group_offsets, params,
-                              penalty || grad_coeff || grad_times || grad_start || min_sep, &nothing);
-    if (rc != UAVQP_OK || nothing) return rc;
-    // the offsets the device trusts: ascending from 0 to n_traj, no swarm larger than the kernel's lanes
-    if (group_offsets) {
-        if (group_offsets[0] != 0 || group_offsets[n_groups] != n_traj) return UAVQP_ERR_INVALID_ARG;
-        for (int g = 0; g < n_groups; ++g) {
-            const long long A = (long long)group_offsets[g + 1] - group_offsets[g];
-            if (A < 0 || A > UAVQP_SWARM_MAX_VEHICLES) return UAVQP_ERR_INVALID_ARG;
-        }
-    } else if (n_traj > UAVQP_SWARM_MAX_VEHICLES) {
-        return UAVQP_ERR_INVALID_ARG;
-    }
-    BatchShape sh{0, 1};
-    if (n_traj > 0) {
-        rc = batch_shape(n_traj, uniform_segments, 0, seg_offsets, &sh);
-        if (rc != UAVQP_OK) return rc;
-    }
+    const SolvedBatch B{r, n_traj, uniform_segments, seg_offsets, times, coeff, status};
+    bool run;
+    const SolvedGroups G{n_groups, group_offsets};
+    int rc = solved_args_check(ctx, B, [&] { return swarm_params_valid(params); },
+                               penalty || grad_coeff || grad_times || grad_start || min_sep, &run, &G);
+    if (!run) return rc;
+    BatchShape sh;
+    rc = swarm_groups_host_check(n_traj, n_groups, group_offsets);
+    if (rc == UAVQP_OK) rc = solved_shape(B, &sh);
+    if (rc != UAVQP_OK) return rc;
     UAVQP_HIP(hipSetDevice(ctx->device));
     const size_t n = (size_t)n_traj, tot = (size_t)sh.total_seg, ng = (size_t)n_groups;
     Stage st;
-    const int i_off = (uniform_segments > 0 || n_traj == 0) ? -1 : st.in(seg_offsets, sizeof(int32_t) * (n + 1));
-    const int i_t = st.in(times, sizeof(double) * tot);
-    const int i_c = st.in(coeff, sizeof(double) * 3 * 2 * r * tot);
-    const int i_st = status ? st.in(status, sizeof(int32_t) * n) : -1;
+    SolvedStage in;
+    in.declare(st, B, sh);
     const int i_go = group_offsets ? st.in(group_offsets, sizeof(int32_t) * (ng + 1)) : -1;
     const int i_s = start ? st.in(start, sizeof(double) * n) : -1;
     const int i_p = penalty ? st.out(penalty, sizeof(double) * ng) : -1;
@@ -121,8 +101,7 @@ extern "C" int uavqp_swarm_penalty_host(uavqp_ctx* ctx, int r, int n_traj, int u
     const int i_ms = min_sep ? st.out(min_sep, sizeof(double) * n) : -1;
     rc = stage_begin(ctx, st);
     if (rc != UAVQP_OK) return rc;
-    rc = swarm_penalty_enqueue(ctx, r, n_traj, uniform_segments, st.at<int32_t>(i_off), st.at<double>(i_t), st.at<double>(i_c),
-                               st.at<int32_t>(i_st), n_groups, st.at<int32_t>(i_go), st.at<double>(i_s), *params, st.at<double>(i_p),
+    rc = swarm_penalty_enqueue(ctx, in.device(st), n_groups, st.at<int32_t>(i_go), st.at<double>(i_s), *params, st.at<double>(i_p),
                                st.at<double>(i_g), st.at<double>(i_gt), st.at<double>(i_gs), st.at<double>(i_ms));
     if (rc != UAVQP_OK) return rc;
     return stage_end(ctx, st, "uavqp_swarm_penalty_host");

@@ -82,9 +82,8 @@ extern "C" int uavqp_swarm_optimize_device(uavqp_ctx* ctx, int r, int n_traj, in
     // the partial gradients in ONE pair of arrays, for ONE backward pass
     auto swarm_penalty = [&](const DescentPoint& p) -> int {
         const double* d_s = p.at == DescentAt::TRIAL ? a.start_trial : d_start;   // (null without departures, either way)
-        return swarm_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, j.t_at(p), d_coeff_out, j.status_at(p), n_groups,
-                                     d_group_offsets, d_s, *swarm, c.at<double>(i_phs), j.at<double>(j.k.g), j.at<double>(j.k.ex),
-                                     c.at<double>(i_gs), nullptr, true);
+        return swarm_penalty_enqueue(ctx, j.solved_at(p), n_groups, d_group_offsets, d_s, *swarm, c.at<double>(i_phs), j.at<double>(j.k.g),
+                                     j.at<double>(j.k.ex), c.at<double>(i_gs), nullptr, true);
     };
     // one workgroup per swarm, grid-stride past eight resident workgroups per CU
     const int cap = ctx->num_cus * 8;
@@ -105,8 +104,8 @@ extern "C" int uavqp_swarm_optimize_device(uavqp_ctx* ctx, int r, int n_traj, in
         });
     if (rc == UAVQP_OK) rc = j.flight_diagnostics(d_peak_out, d_min_dist_out, d_outside_out);   // the penalties' diagnostics of what is handed back
     if (rc == UAVQP_OK && d_min_sep_out)
-        rc = swarm_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, j.status_final(), n_groups,
-                                   d_group_offsets, d_start, *swarm, nullptr, nullptr, nullptr, nullptr, d_min_sep_out);
+        rc = swarm_penalty_enqueue(ctx, j.solved_final(), n_groups, d_group_offsets, d_start, *swarm, nullptr, nullptr, nullptr, nullptr,
+                                   d_min_sep_out);
     return rc;
 }
 

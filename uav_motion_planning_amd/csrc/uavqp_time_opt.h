@@ -9,16 +9,14 @@
 // backward pass of its coefficient gradient:
 //     clamp -> solve(times) -> penalty, backward -> step<INIT> -> max_iters x { solve(trial) -> penalty, backward -> step<ITER> } -> solve(times)
 // The order itself is descent_sequence (uavqp_descent.h), here and in every optimiser included behind this file; what they share around it
-// is here too: descent_args_check, time_clamp_enqueue, step_dispatch and the staging of the _host entries (descent_run_host).
+// is here too: descent_args_check, time_clamp_enqueue and the staging of the _host entries (descent_run_host).
 #pragma once
-#include <type_traits>
 #include "uavqp_descent.h"
 static_assert(UAVQP_OK == 0, "descent_sequence goes on while its hooks return 0");
 
 // (uavqp_limits.h, included behind this file and uavqp_adjoint.h)
-static int limit_penalty_enqueue(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets, const double* d_times,
-                                 const double* d_coeff, const int32_t* d_status, const uavqp_limit_params& L, double* d_penalty,
-                                 double* d_grad_coeff, double* d_grad_times, double* d_peak);
+static int limit_penalty_enqueue(uavqp_ctx* ctx, const SolvedBatch& B, const uavqp_limit_params& L, double* d_penalty, double* d_grad_coeff,
+                                 double* d_grad_times, double* d_peak);
 
 extern "C" void uavqp_default_time_opt_params(uavqp_time_opt_params* p) {
     if (!p) return;
@@ -103,20 +101,6 @@ static int time_clamp_enqueue(uavqp_ctx* ctx, int r, int n_traj, int uniform_seg
     return UAVQP_OK;
 }
 
-// The four-way <R, INIT> dispatch of a step kernel and the error of its launch.  launch(R, INIT) gets the two as integral constants and
-// names its kernel with decltype(R)::value, decltype(INIT)::value (and whatever further template arguments it has).
-template <class Launch>
-static int step_dispatch(int r, bool init, Launch&& launch) {
-    using R3 = std::integral_constant<int, 3>;
-    using R4 = std::integral_constant<int, 4>;
-    if (r == 3 && init) launch(R3{}, std::true_type{});
-    else if (r == 3) launch(R3{}, std::false_type{});
-    else if (init) launch(R4{}, std::true_type{});
-    else launch(R4{}, std::false_type{});
-    UAVQP_HIP(hipGetLastError());
-    return UAVQP_OK;
-}
-
 // limits = null: uavqp_time_optimize_device.  Otherwise (validated by the caller) f and its gradient carry the limit penalty.
 static int time_optimize_run(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, int max_segments, int total_segments,
                              const int32_t* d_seg_offsets, const double* d_waypoints, double* d_times, const double* d_bc,
@@ -162,7 +146,7 @@ static int time_optimize_run(uavqp_ctx* ctx, int r, int n_traj, int uniform_segm
     // the penalty of the point `coeff` was solved at, its gradient in the coefficients, and that gradient taken through the minimiser
     auto penalty_and_backward = [&](const DescentPoint& p) -> int {
         if (!lim) return UAVQP_OK;
-        int e = limit_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, times_at(p), d_coeff_out, a.status, *limits,
+        int e = limit_penalty_enqueue(ctx, SolvedBatch{r, n_traj, uniform_segments, d_seg_offsets, times_at(p), d_coeff_out, a.status}, *limits,
                                       c.at<double>(i_lp), c.at<double>(i_lg), c.at<double>(i_le), nullptr);
         if (e != UAVQP_OK) return e;
         return uavqp_solve_backward_device(ctx, r, n_traj, uniform_segments, max_segments, total_segments, d_seg_offsets, d_waypoints, times_at(p),
@@ -170,7 +154,7 @@ static int time_optimize_run(uavqp_ctx* ctx, int r, int n_traj, int uniform_segm
     };
     auto step = [&](bool init, int, bool propose) -> int {
         a.propose = propose ? 1 : 0;
-        return step_dispatch(r, init, [&](auto R, auto INIT) {
+        return dispatch_r_flag(r, init, [&](auto R, auto INIT) {
             constexpr int R_ = decltype(R)::value;
             constexpr bool INIT_ = decltype(INIT)::value;
             if (lim) hipLaunchKernelGGL((uavqp::time_opt_step_kernel<R_, INIT_, true>), dim3(grid), dim3(64), 0, s, a);
@@ -182,8 +166,8 @@ static int time_optimize_run(uavqp_ctx* ctx, int r, int n_traj, int uniform_segm
     rc = descent_sequence(P.max_iters, solve, penalty_and_backward, step);
     if (rc != UAVQP_OK) return rc;
     if (lim && d_peak_out)   // the sampled peaks of what is handed back
-        rc = limit_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, d_st_final, *limits, nullptr, nullptr,
-                                   nullptr, d_peak_out);
+        rc = limit_penalty_enqueue(ctx, SolvedBatch{r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, d_st_final}, *limits, nullptr,
+                                   nullptr, nullptr, d_peak_out);
     return rc;
 }
 

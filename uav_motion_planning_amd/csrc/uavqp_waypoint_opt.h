@@ -109,6 +109,7 @@ extern "C" int uavqp_waypoint_optimize_device(uavqp_ctx* ctx, int r, int n_traj,
     hipStream_t s = ctx->stream;
     // the waypoints and the status of a point of the sequence; the step kernel reads the status of the solve before it
     auto waypoints_at = [&](const DescentPoint& p) { return p.at == DescentAt::TRIAL ? a.trial : d_waypoints; };
+    auto solved = [&](const int32_t* st) { return SolvedBatch{r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, st}; };
     auto solve = [&](const DescentPoint& p) -> int {
         a.status = p.caller_status ? d_st_final : d_st_loop;
         return uavqp_solve_batch_device(ctx, r, n_traj, uniform_segments, max_segments, d_seg_offsets, waypoints_at(p), d_times, d_bc, d_coeff_out,
@@ -116,15 +117,14 @@ extern "C" int uavqp_waypoint_optimize_device(uavqp_ctx* ctx, int r, int n_traj,
     };
     // the penalty of the point `coeff` was solved at, its gradient in the coefficients, and that gradient taken through the minimiser to the waypoints
     auto penalty_and_backward = [&](const DescentPoint& p) -> int {
-        int e = clearance_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, a.status, esdf, *clearance,
-                                          c.at<double>(i_ph), c.at<double>(i_g), nullptr, nullptr, nullptr);
+        int e = clearance_penalty_enqueue(ctx, solved(a.status), esdf, *clearance, c.at<double>(i_ph), c.at<double>(i_g), nullptr, nullptr, nullptr);
         if (e != UAVQP_OK) return e;
         return uavqp_solve_backward_device(ctx, r, n_traj, uniform_segments, max_segments, total_segments, d_seg_offsets, waypoints_at(p), d_times,
                                            d_bc, d_coeff_out, a.status, c.at<double>(i_g), nullptr, c.at<double>(i_th), nullptr);
     };
     auto step = [&](bool init, int, bool propose) -> int {
         a.propose = propose ? 1 : 0;
-        return step_dispatch(r, init, [&](auto R, auto INIT) {
+        return dispatch_r_flag(r, init, [&](auto R, auto INIT) {
             hipLaunchKernelGGL((uavqp::waypoint_opt_step_kernel<decltype(R)::value, decltype(INIT)::value>), dim3(grid), dim3(64), 0, s, a);
         });
     };
@@ -135,8 +135,7 @@ extern "C" int uavqp_waypoint_optimize_device(uavqp_ctx* ctx, int r, int n_traj,
     rc = descent_sequence(P.max_iters, solve, penalty_and_backward, step);
     if (rc != UAVQP_OK) return rc;
     if (d_min_dist_out || d_outside_out)   // the penalty's diagnostics of what is handed back
-        rc = clearance_penalty_enqueue(ctx, r, n_traj, uniform_segments, d_seg_offsets, d_times, d_coeff_out, d_st_final, esdf, *clearance, nullptr,
-                                       nullptr, nullptr, d_min_dist_out, d_outside_out);
+        rc = clearance_penalty_enqueue(ctx, solved(d_st_final), esdf, *clearance, nullptr, nullptr, nullptr, d_min_dist_out, d_outside_out);
     return rc;
 }
 

@@ -11,6 +11,7 @@ torch is used only for device memory and streams.  No CPU fallback: without libu
 GPU every solve raises / returns False exactly as the reference does on solver failure.
 """
 import ctypes
+import functools
 
 import numpy as np
 
@@ -24,6 +25,10 @@ def _ptr(x):
     if x is None or isinstance(x, int):
         return x
     return x.data_ptr()  # torch tensor
+
+
+def _unknown_field(c_name, k):
+    return ValueError(f"unknown uavqp_{c_name} field {k!r}")
 
 
 def _batch_shape(seg_offsets, times, uniform_segments):
@@ -112,22 +117,57 @@ class Context:
         rc = _lib.lib().uavqp_cost_time_gradient_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff), _ptr(cost), _ptr(grad))
         _lib.check(rc, "uavqp_cost_time_gradient_device")
 
+    _DEFAULTS = {}   # c_name -> the library's uavqp_default_<c_name>, looked up once
+
     @staticmethod
-    def _time_opt_params(params):
-        pp = _lib.TimeOptParams()
-        _lib.lib().uavqp_default_time_opt_params(ctypes.byref(pp))
-        for k, v in params.items():
-            if not hasattr(pp, k) or k == "struct_size":
-                raise ValueError(f"unknown uavqp_time_opt_params field {k!r}")
+    def _params(struct_cls, c_name, fields):
+        """A uavqp_<c_name> struct: uavqp_default_<c_name>, then the fields given (an unknown or reserved one is refused)."""
+        default = Context._DEFAULTS.get(c_name)
+        if default is None:
+            default = Context._DEFAULTS[c_name] = getattr(_lib.lib(), "uavqp_default_" + c_name)
+        pp = struct_cls()
+        default(ctypes.byref(pp))
+        for k, v in fields.items():
+            if not hasattr(pp, k) or k in ("struct_size", "reserved_"):
+                raise _unknown_field(c_name, k)
             setattr(pp, k, v)
         return pp
+
+    # (the names tests and autograd.py call)
+    _limit_params = staticmethod(functools.partial(_params.__func__, _lib.LimitParams, "limit_params"))
+    _swarm_params = staticmethod(functools.partial(_params.__func__, _lib.SwarmParams, "swarm_params"))
+    _clearance_params = staticmethod(functools.partial(_params.__func__, _lib.ClearanceParams, "clearance_params"))
+    _spacetime_params = staticmethod(functools.partial(_params.__func__, _lib.SpacetimeParams, "spacetime_params"))
+    _swarm_opt_params = staticmethod(functools.partial(_params.__func__, _lib.SwarmOptParams, "swarm_opt_params"))
+    _spacetime_lbfgs_params = staticmethod(functools.partial(_params.__func__, _lib.SpacetimeLbfgsParams, "spacetime_lbfgs_params"))
+    _attitude_params = staticmethod(functools.partial(_params.__func__, _lib.AttitudeParams, "attitude_params"))
+    _moving_params = staticmethod(functools.partial(_params.__func__, _lib.MovingParams, "moving_params"))
+
+    @staticmethod
+    def _solved_inputs(r, seg_offsets, times, coeff, uniform_segments, status):
+        """The solved batch of a _host wrapper as contiguous arrays, sizes checked: (seg_offsets or None, times, coeff, status or None,
+        n_traj, total segments)."""
+        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
+        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
+        assert times.size == total and coeff.size == 3 * 2 * r * total
+        return so, times, coeff, status, n_traj, total
+
+    @staticmethod
+    def _swarm_inputs(group_offsets, start, n_traj):
+        """(group_offsets or None, n_groups, start or None) of a _host swarm wrapper; no offsets: the whole batch is one swarm."""
+        go = None if group_offsets is None else np.ascontiguousarray(group_offsets, dtype=np.int32)
+        start = None if start is None else np.ascontiguousarray(start, dtype=np.float64).ravel()
+        assert start is None or start.size == n_traj
+        return go, (1 if go is None else go.size - 1), start
 
     def time_optimize_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc,
                              coeff_out, status_out, objective_out, accepted_out=None, **params):
         """uavqp_time_optimize_device on device buffers: `times` holds the start and receives the optimised durations, coeff_out the
         solve at them, objective_out [n_traj][2] f = cost + time_weight * sum T at the start and at the result.
         params: fields of uavqp_time_opt_params that differ from uavqp_default_time_opt_params.  Asynchronous."""
-        pp = self._time_opt_params(params)
+        pp = self._params(_lib.TimeOptParams, "time_opt_params", params)
         rc = _lib.lib().uavqp_time_optimize_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), _ptr(seg_offsets),
                                                    _ptr(waypoints), _ptr(times), _ptr(bc), ctypes.byref(pp), _ptr(coeff_out), _ptr(status_out),
                                                    _ptr(objective_out), _ptr(accepted_out))
@@ -142,7 +182,7 @@ class Context:
         assert times.size == total
         assert waypoints.size == 3 * (total + n_traj), "waypoints must hold sum(M_b + 1) xyz rows"
         assert bc.size == n_traj * 2 * (r - 1) * 3
-        pp = self._time_opt_params(params)
+        pp = self._params(_lib.TimeOptParams, "time_opt_params", params)
         coeff = np.zeros(3 * 2 * r * total, dtype=np.float64)
         status = np.zeros(n_traj, dtype=np.int32)
         objective = np.zeros((n_traj, 2), dtype=np.float64)
@@ -151,16 +191,6 @@ class Context:
                                                  _ptr(bc), ctypes.byref(pp), _ptr(coeff), _ptr(status), _ptr(objective), _ptr(accepted))
         _lib.check(rc, "uavqp_time_optimize_host")
         return times, coeff, status, objective, accepted
-
-    @staticmethod
-    def _limit_params(limits):
-        lp = _lib.LimitParams()
-        _lib.lib().uavqp_default_limit_params(ctypes.byref(lp))
-        for k, v in limits.items():
-            if not hasattr(lp, k) or k == "struct_size":
-                raise ValueError(f"unknown uavqp_limit_params field {k!r}")
-            setattr(lp, k, v)
-        return lp
 
     def limit_penalty_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, status=None, penalty=None, grad_coeff=None,
                              grad_times=None, peak=None, **limits):
@@ -176,11 +206,7 @@ class Context:
 
     def limit_penalty_host(self, r, seg_offsets, times, coeff, uniform_segments=0, status=None, **limits):
         """numpy in / numpy out (synchronous).  Returns (penalty [n_traj], grad_coeff, grad_times [sum M], peak [n_traj][2])."""
-        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
-        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
-        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
-        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
-        assert times.size == total and coeff.size == 3 * 2 * r * total
+        so, times, coeff, status, n_traj, total = self._solved_inputs(r, seg_offsets, times, coeff, uniform_segments, status)
         lp = self._limit_params(limits)
         penalty = np.zeros(n_traj, dtype=np.float64)
         g_c = np.zeros_like(coeff)
@@ -190,16 +216,6 @@ class Context:
                                                  ctypes.byref(lp), _ptr(penalty), _ptr(g_c), _ptr(g_t), _ptr(peak))
         _lib.check(rc, "uavqp_limit_penalty_host")
         return penalty, g_c, g_t, peak
-
-    @staticmethod
-    def _swarm_params(params):
-        sp = _lib.SwarmParams()
-        _lib.lib().uavqp_default_swarm_params(ctypes.byref(sp))
-        for k, v in params.items():
-            if not hasattr(sp, k) or k == "struct_size":
-                raise ValueError(f"unknown uavqp_swarm_params field {k!r}")
-            setattr(sp, k, v)
-        return sp
 
     def swarm_penalty_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, n_groups=1, group_offsets=None, start=None,
                              status=None, penalty=None, grad_coeff=None, grad_times=None, grad_start=None, min_sep=None, **params):
@@ -219,15 +235,8 @@ class Context:
     def swarm_penalty_host(self, r, seg_offsets, times, coeff, group_offsets=None, start=None, uniform_segments=0, status=None, **params):
         """numpy in / numpy out (synchronous).  group_offsets None: the whole batch is one swarm.  Returns (penalty [n_groups], grad_coeff,
         grad_times [sum M], grad_start [n_traj], min_sep [n_traj])."""
-        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
-        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
-        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
-        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
-        assert times.size == total and coeff.size == 3 * 2 * r * total
-        go = None if group_offsets is None else np.ascontiguousarray(group_offsets, dtype=np.int32)
-        n_groups = 1 if go is None else go.size - 1
-        start = None if start is None else np.ascontiguousarray(start, dtype=np.float64).ravel()
-        assert start is None or start.size == n_traj
+        so, times, coeff, status, n_traj, total = self._solved_inputs(r, seg_offsets, times, coeff, uniform_segments, status)
+        go, n_groups, start = self._swarm_inputs(group_offsets, start, n_traj)
         sp = self._swarm_params(params)
         penalty = np.zeros(n_groups, dtype=np.float64)
         g_c = np.zeros_like(coeff)
@@ -240,16 +249,6 @@ class Context:
         _lib.check(rc, "uavqp_swarm_penalty_host")
         return penalty, g_c, g_t, g_s, min_sep
 
-    @staticmethod
-    def _separation_params(params):
-        sp = _lib.SeparationParams()
-        _lib.lib().uavqp_default_separation_params(ctypes.byref(sp))
-        for k, v in params.items():
-            if not hasattr(sp, k) or k == "struct_size":
-                raise ValueError(f"unknown uavqp_separation_params field {k!r}")
-            setattr(sp, k, v)
-        return sp
-
     def separation_certificate_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, n_groups=1, group_offsets=None, start=None,
                                       status=None, lower_out=None, upper_out=None, where_out=None, verdict_out=None, group_verdict_out=None,
                                       **params):
@@ -259,7 +258,7 @@ class Context:
         witness index of upper}, verdict_out [n_traj] and group_verdict_out [n_groups] int32 (_lib.UAVQP_SEPARATION_CERTIFIED / _VIOLATED /
         _MOVING); each may be None.  params: fields of uavqp_separation_params that differ from uavqp_default_separation_params (depth,
         n_cells, clock_start, dt, downwash, d_req).  Asynchronous."""
-        sp = self._separation_params(params)
+        sp = self._params(_lib.SeparationParams, "separation_params", params)
         rc = _lib.lib().uavqp_separation_certificate_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff),
                                                             _ptr(status), int(n_groups), _ptr(group_offsets), _ptr(start), ctypes.byref(sp),
                                                             _ptr(lower_out), _ptr(upper_out), _ptr(where_out), _ptr(verdict_out),
@@ -269,16 +268,9 @@ class Context:
     def separation_certificate(self, r, seg_offsets, times, coeff, group_offsets=None, start=None, uniform_segments=0, status=None, **params):
         """uavqp_separation_certificate_host: numpy in / numpy out (synchronous).  group_offsets None: the whole batch is one swarm.  Returns
         (lower [n_traj], upper [n_traj], where [n_traj][4], verdict [n_traj], group_verdict [n_groups]); see separation_certificate_device."""
-        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
-        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
-        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
-        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
-        assert times.size == total and coeff.size == 3 * 2 * r * total
-        go = None if group_offsets is None else np.ascontiguousarray(group_offsets, dtype=np.int32)
-        n_groups = 1 if go is None else go.size - 1
-        start = None if start is None else np.ascontiguousarray(start, dtype=np.float64).ravel()
-        assert start is None or start.size == n_traj
-        sp = self._separation_params(params)
+        so, times, coeff, status, n_traj, total = self._solved_inputs(r, seg_offsets, times, coeff, uniform_segments, status)
+        go, n_groups, start = self._swarm_inputs(group_offsets, start, n_traj)
+        sp = self._params(_lib.SeparationParams, "separation_params", params)
         lower = np.zeros(n_traj, dtype=np.float64)
         upper = np.zeros(n_traj, dtype=np.float64)
         where = np.zeros((n_traj, 4), dtype=np.int32)
@@ -289,16 +281,6 @@ class Context:
                                                           _ptr(where), _ptr(verdict), _ptr(group_verdict))
         _lib.check(rc, "uavqp_separation_certificate_host")
         return lower, upper, where, verdict, group_verdict
-
-    @staticmethod
-    def _clearance_params(params):
-        cp = _lib.ClearanceParams()
-        _lib.lib().uavqp_default_clearance_params(ctypes.byref(cp))
-        for k, v in params.items():
-            if not hasattr(cp, k) or k == "struct_size":
-                raise ValueError(f"unknown uavqp_clearance_params field {k!r}")
-            setattr(cp, k, v)
-        return cp
 
     def clearance_penalty_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, esdf, status=None, penalty=None, grad_coeff=None,
                                  grad_times=None, min_dist=None, outside=None, **params):
@@ -316,11 +298,7 @@ class Context:
     def clearance_penalty_host(self, r, seg_offsets, times, coeff, esdf, uniform_segments=0, status=None, **params):
         """numpy in / numpy out (synchronous; the map stays on the device).  Returns (penalty [n_traj], grad_coeff, grad_times [sum M],
         min_dist [n_traj], outside [n_traj] int32)."""
-        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
-        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
-        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
-        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
-        assert times.size == total and coeff.size == 3 * 2 * r * total
+        so, times, coeff, status, n_traj, total = self._solved_inputs(r, seg_offsets, times, coeff, uniform_segments, status)
         cp = self._clearance_params(params)
         penalty = np.zeros(n_traj, dtype=np.float64)
         g_c = np.zeros_like(coeff)
@@ -332,16 +310,6 @@ class Context:
                                                      _ptr(min_dist), _ptr(outside))
         _lib.check(rc, "uavqp_clearance_penalty_host")
         return penalty, g_c, g_t, min_dist, outside
-
-    @staticmethod
-    def _waypoint_opt_params(params):
-        pp = _lib.WaypointOptParams()
-        _lib.lib().uavqp_default_waypoint_opt_params(ctypes.byref(pp))
-        for k, v in params.items():
-            if not hasattr(pp, k) or k == "struct_size":
-                raise ValueError(f"unknown uavqp_waypoint_opt_params field {k!r}")
-            setattr(pp, k, v)
-        return pp
 
     def cost_waypoint_gradient_device(self, r, n_traj, uniform_segments, seg_offsets, coeff, grad, status=None):
         """uavqp_cost_waypoint_gradient_device: grad [sum (M + 1)][3] = d cost / d p_k at the minimiser of the equality-constrained solve,
@@ -375,7 +343,7 @@ class Context:
         `esdf` (an esdf.EsdfMap, updated) at the start and at the result, min_dist_out / outside_out the penalty's diagnostics at the
         result.  clearance: dict of uavqp_clearance_params fields; params: fields of uavqp_waypoint_opt_params that differ from the
         defaults.  The penalty is soft and the result a local minimum (include/uavqp.h).  Asynchronous."""
-        pp = self._waypoint_opt_params(params)
+        pp = self._params(_lib.WaypointOptParams, "waypoint_opt_params", params)
         cp = self._clearance_params(clearance or {})
         rc = _lib.lib().uavqp_waypoint_optimize_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), _ptr(seg_offsets),
                                                        _ptr(waypoints), _ptr(times), _ptr(bc), getattr(esdf, "handle", esdf), ctypes.byref(cp),
@@ -393,7 +361,7 @@ class Context:
         assert times.size == total
         assert waypoints.size == 3 * (total + n_traj), "waypoints must hold sum(M_b + 1) xyz rows"
         assert bc.size == n_traj * 2 * (r - 1) * 3
-        pp = self._waypoint_opt_params(params)
+        pp = self._params(_lib.WaypointOptParams, "waypoint_opt_params", params)
         cp = self._clearance_params(clearance or {})
         coeff = np.zeros(3 * 2 * r * total, dtype=np.float64)
         status = np.zeros(n_traj, dtype=np.int32)
@@ -406,16 +374,6 @@ class Context:
                                                      _ptr(status), _ptr(objective), _ptr(accepted), _ptr(min_dist), _ptr(outside))
         _lib.check(rc, "uavqp_waypoint_optimize_host")
         return waypoints, coeff, status, objective, accepted, min_dist, outside
-
-    @staticmethod
-    def _spacetime_params(params):
-        pp = _lib.SpacetimeParams()
-        _lib.lib().uavqp_default_spacetime_params(ctypes.byref(pp))
-        for k, v in params.items():
-            if not hasattr(pp, k) or k == "struct_size":
-                raise ValueError(f"unknown uavqp_spacetime_params field {k!r}")
-            setattr(pp, k, v)
-        return pp
 
     def flight_penalty_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, esdf, status=None, penalty=None, grad_coeff=None,
                               grad_times=None, peak=None, min_dist=None, outside=None, limits=None, clearance=None):
@@ -432,11 +390,7 @@ class Context:
     def flight_penalty_host(self, r, seg_offsets, times, coeff, esdf, uniform_segments=0, status=None, limits=None, clearance=None):
         """numpy in / numpy out (synchronous; the map stays on the device).  Returns (penalty [n_traj], grad_coeff, grad_times [sum M],
         peak [n_traj][2], min_dist [n_traj], outside [n_traj] int32)."""
-        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
-        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
-        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
-        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
-        assert times.size == total and coeff.size == 3 * 2 * r * total
+        so, times, coeff, status, n_traj, total = self._solved_inputs(r, seg_offsets, times, coeff, uniform_segments, status)
         lp, cp = self._limit_params(limits or {}), self._clearance_params(clearance or {})
         penalty = np.zeros(n_traj, dtype=np.float64)
         g_c = np.zeros_like(coeff)
@@ -494,16 +448,6 @@ class Context:
         _lib.check(rc, "uavqp_spacetime_optimize_host")
         return waypoints, times, coeff, status, objective, accepted, peak, min_dist, outside
 
-    @staticmethod
-    def _swarm_opt_params(params):
-        pp = _lib.SwarmOptParams()
-        _lib.lib().uavqp_default_swarm_opt_params(ctypes.byref(pp))
-        for k, v in params.items():
-            if not hasattr(pp, k) or k == "struct_size":
-                raise ValueError(f"unknown uavqp_swarm_opt_params field {k!r}")
-            setattr(pp, k, v)
-        return pp
-
     def swarm_optimize_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc, esdf,
                               coeff_out, status_out, objective_out, n_groups=1, group_offsets=None, start=None, accepted_out=None,
                               peak_out=None, min_dist_out=None, outside_out=None, min_sep_out=None, limits=None, clearance=None, swarm=None,
@@ -558,16 +502,6 @@ class Context:
         _lib.check(rc, "uavqp_swarm_optimize_host")
         return waypoints, times, start, coeff, status, objective, accepted, peak, min_dist, outside, min_sep
 
-    @staticmethod
-    def _spacetime_lbfgs_params(params):
-        pp = _lib.SpacetimeLbfgsParams()
-        _lib.lib().uavqp_default_spacetime_lbfgs_params(ctypes.byref(pp))
-        for k, v in params.items():
-            if not hasattr(pp, k) or k == "struct_size":
-                raise ValueError(f"unknown uavqp_spacetime_lbfgs_params field {k!r}")
-            setattr(pp, k, v)
-        return pp
-
     def spacetime_lbfgs_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc, esdf,
                                coeff_out, status_out, objective_out, accepted_out=None, peak_out=None, min_dist_out=None, outside_out=None,
                                limits=None, clearance=None, **params):
@@ -608,16 +542,6 @@ class Context:
         _lib.check(rc, "uavqp_spacetime_lbfgs_host")
         return waypoints, times, coeff, status, objective, accepted, peak, min_dist, outside
 
-    @staticmethod
-    def _attitude_params(params):
-        ap = _lib.AttitudeParams()
-        _lib.lib().uavqp_default_attitude_params(ctypes.byref(ap))
-        for k, v in params.items():
-            if not hasattr(ap, k) or k == "struct_size":
-                raise ValueError(f"unknown uavqp_attitude_params field {k!r}")
-            setattr(ap, k, v)
-        return ap
-
     def attitude_penalty_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, status=None, penalty=None, grad_coeff=None,
                                 grad_times=None, peak=None, **params):
         """uavqp_attitude_penalty_device on device buffers: the thrust / tilt / body-rate penalty [n_traj] of solved trajectories, its
@@ -633,11 +557,7 @@ class Context:
 
     def attitude_penalty_host(self, r, seg_offsets, times, coeff, uniform_segments=0, status=None, **params):
         """numpy in / numpy out (synchronous).  Returns (penalty [n_traj], grad_coeff, grad_times [sum M], peak [n_traj][4])."""
-        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
-        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
-        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
-        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
-        assert times.size == total and coeff.size == 3 * 2 * r * total
+        so, times, coeff, status, n_traj, total = self._solved_inputs(r, seg_offsets, times, coeff, uniform_segments, status)
         ap = self._attitude_params(params)
         penalty = np.zeros(n_traj, dtype=np.float64)
         g_c = np.zeros_like(coeff)
@@ -648,16 +568,6 @@ class Context:
         _lib.check(rc, "uavqp_attitude_penalty_host")
         return penalty, g_c, g_t, peak
 
-    @staticmethod
-    def _envelope_params(params):
-        ep = _lib.EnvelopeParams()
-        _lib.lib().uavqp_default_envelope_params(ctypes.byref(ep))
-        for k, v in params.items():
-            if not hasattr(ep, k) or k == "struct_size":
-                raise ValueError(f"unknown uavqp_envelope_params field {k!r}")
-            setattr(ep, k, v)
-        return ep
-
     def envelope_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, status=None, box_lo=None, box_hi=None, range_out=None,
                         norm_out=None, peak_out=None, seg_verdict_out=None, verdict_out=None, **params):
         """uavqp_envelope_device on device buffers: certified bounds of solved trajectories over whole segments.  range_out
@@ -666,7 +576,7 @@ class Context:
         bit 2k + 1 violated, k indexing _lib.ENVELOPE_TESTS); each may be None.  box_lo / box_hi [sum M][3]: one box per segment, both or
         neither.  params: fields of uavqp_envelope_params (depth, v_max, a_max, j_max, f_min, f_max, tilt_max; a limit of 0 is off).
         Asynchronous."""
-        ep = self._envelope_params(params)
+        ep = self._params(_lib.EnvelopeParams, "envelope_params", params)
         rc = _lib.lib().uavqp_envelope_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff), _ptr(status),
                                               ctypes.byref(ep), _ptr(box_lo), _ptr(box_hi), _ptr(range_out), _ptr(norm_out), _ptr(peak_out),
                                               _ptr(seg_verdict_out), _ptr(verdict_out))
@@ -675,16 +585,12 @@ class Context:
     def envelope(self, r, seg_offsets, times, coeff, uniform_segments=0, status=None, box_lo=None, box_hi=None, **params):
         """uavqp_envelope_host: numpy in / numpy out (synchronous).  Returns (range [sum M][4][3][4], norm [sum M][5][4],
         peak [n_traj][5][4], seg_verdict [sum M], verdict [n_traj]); see envelope_device."""
-        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
-        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
-        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
-        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
-        assert times.size == total and coeff.size == 3 * 2 * r * total
+        so, times, coeff, status, n_traj, total = self._solved_inputs(r, seg_offsets, times, coeff, uniform_segments, status)
         if box_lo is not None:
             box_lo = np.ascontiguousarray(box_lo, dtype=np.float64).reshape(total, 3)
         if box_hi is not None:
             box_hi = np.ascontiguousarray(box_hi, dtype=np.float64).reshape(total, 3)
-        ep = self._envelope_params(params)
+        ep = self._params(_lib.EnvelopeParams, "envelope_params", params)
         rng = np.zeros((total, 4, 3, 4), dtype=np.float64)
         norm = np.zeros((total, 5, 4), dtype=np.float64)
         peak = np.zeros((n_traj, 5, 4), dtype=np.float64)
@@ -696,16 +602,6 @@ class Context:
         _lib.check(rc, "uavqp_envelope_host")
         return rng, norm, peak, seg_verdict, verdict
 
-    @staticmethod
-    def _clearance_cert_params(params):
-        cp = _lib.ClearanceCertParams()
-        _lib.lib().uavqp_default_clearance_cert_params(ctypes.byref(cp))
-        for k, v in params.items():
-            if not hasattr(cp, k) or k == "struct_size":
-                raise ValueError(f"unknown uavqp_clearance_cert_params field {k!r}")
-            setattr(cp, k, v)
-        return cp
-
     def clearance_certificate_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, esdf, status=None, clear_out=None,
                                      witness_out=None, peak_out=None, seg_verdict_out=None, verdict_out=None, **params):
         """uavqp_clearance_certificate_device on device buffers: certified clearance of solved trajectories against the distance field
@@ -713,7 +609,7 @@ class Context:
         witness_out [sum M] (int32 l: the witness is at t = l T_i / 2^depth), peak_out [n_traj][2] (the smallest lower / upper of the
         trajectory), seg_verdict_out [sum M] and verdict_out [n_traj] (int32: _lib.UAVQP_CLEARANCE_CERTIFIED / _VIOLATED / _OUTSIDE); each
         may be None.  params: depth (0..8, default 4), d_req (m, default 0.5).  Asynchronous."""
-        cp = self._clearance_cert_params(params)
+        cp = self._params(_lib.ClearanceCertParams, "clearance_cert_params", params)
         rc = _lib.lib().uavqp_clearance_certificate_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff),
                                                            _ptr(status), getattr(esdf, "handle", esdf), ctypes.byref(cp), _ptr(clear_out),
                                                            _ptr(witness_out), _ptr(peak_out), _ptr(seg_verdict_out), _ptr(verdict_out))
@@ -722,12 +618,8 @@ class Context:
     def clearance_certificate(self, r, seg_offsets, times, coeff, esdf, uniform_segments=0, status=None, **params):
         """uavqp_clearance_certificate_host: numpy in / numpy out (synchronous; the map stays on the device).  Returns (clear [sum M][2],
         witness [sum M], peak [n_traj][2], seg_verdict [sum M], verdict [n_traj]); see clearance_certificate_device."""
-        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
-        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
-        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
-        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
-        assert times.size == total and coeff.size == 3 * 2 * r * total
-        cp = self._clearance_cert_params(params)
+        so, times, coeff, status, n_traj, total = self._solved_inputs(r, seg_offsets, times, coeff, uniform_segments, status)
+        cp = self._params(_lib.ClearanceCertParams, "clearance_cert_params", params)
         clear = np.zeros((total, 2), dtype=np.float64)
         witness = np.zeros(total, dtype=np.int32)
         peak = np.zeros((n_traj, 2), dtype=np.float64)
@@ -782,16 +674,6 @@ class Context:
         _lib.check(rc, "uavqp_attitude_optimize_host")
         return waypoints, times, coeff, status, objective, accepted, peak, min_dist, outside, attitude_peak
 
-    @staticmethod
-    def _moving_params(params):
-        mp = _lib.MovingParams()
-        _lib.lib().uavqp_default_moving_params(ctypes.byref(mp))
-        for k, v in params.items():
-            if not hasattr(mp, k) or k == "struct_size":
-                raise ValueError(f"unknown uavqp_moving_params field {k!r}")
-            setattr(mp, k, v)
-        return mp
-
     _MOVING_POINTERS = ("seg_offsets", "times", "coeff", "start", "radius", "set_offsets", "traj_set", "traj_start")
 
     @classmethod
@@ -802,7 +684,7 @@ class Context:
         mo.struct_size = ctypes.sizeof(_lib.MovingObstacles)
         for k in obstacles:
             if k not in cls._MOVING_POINTERS and k not in ("n_obs", "uniform_segments", "n_sets"):
-                raise ValueError(f"unknown uavqp_moving_obstacles field {k!r}")
+                raise _unknown_field("moving_obstacles", k)
         mo.n_obs = int(obstacles.get("n_obs", 0))
         mo.uniform_segments = int(obstacles.get("uniform_segments", 0))
         mo.n_sets = int(obstacles.get("n_sets", 1))
@@ -851,11 +733,7 @@ class Context:
     def moving_penalty_host(self, r, seg_offsets, times, coeff, obstacles, uniform_segments=0, status=None, **params):
         """numpy in / numpy out (synchronous).  obstacles: dict of host arrays (_moving_obstacles_host).  Returns (penalty [n_traj],
         grad_coeff, grad_times [sum M], grad_start [n_traj], min_gap [n_traj], nearest [n_traj])."""
-        times = np.ascontiguousarray(times, dtype=np.float64).ravel()
-        coeff = np.ascontiguousarray(coeff, dtype=np.float64).ravel()
-        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
-        so, n_traj, total, _ = _batch_shape(seg_offsets, times, uniform_segments)
-        assert times.size == total and coeff.size == 3 * 2 * r * total
+        so, times, coeff, status, n_traj, total = self._solved_inputs(r, seg_offsets, times, coeff, uniform_segments, status)
         mp = self._moving_params(params)
         mo, keep = self._moving_obstacles_host(r, obstacles, n_traj)
         penalty = np.zeros(n_traj, dtype=np.float64)
@@ -931,7 +809,7 @@ class Context:
         """uavqp_time_optimize_limits_device on device buffers: time_optimize_device with the limit penalty inside the objective
         (objective_out includes it); peak_out [n_traj][2] receives the sampled |v| / v_max, |a| / a_max at the result.  limits: dict of
         uavqp_limit_params fields; params: fields of uavqp_time_opt_params.  The penalty is soft (include/uavqp.h).  Asynchronous."""
-        pp = self._time_opt_params(params)
+        pp = self._params(_lib.TimeOptParams, "time_opt_params", params)
         lp = self._limit_params(limits or {})
         rc = _lib.lib().uavqp_time_optimize_limits_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments),
                                                           _ptr(seg_offsets), _ptr(waypoints), _ptr(times), _ptr(bc), ctypes.byref(pp),
@@ -948,7 +826,7 @@ class Context:
         assert times.size == total
         assert waypoints.size == 3 * (total + n_traj), "waypoints must hold sum(M_b + 1) xyz rows"
         assert bc.size == n_traj * 2 * (r - 1) * 3
-        pp = self._time_opt_params(params)
+        pp = self._params(_lib.TimeOptParams, "time_opt_params", params)
         lp = self._limit_params(limits)
         coeff = np.zeros(3 * 2 * r * total, dtype=np.float64)
         status = np.zeros(n_traj, dtype=np.int32)
@@ -1049,22 +927,12 @@ class Context:
                                                           _ptr(first_hit), _ptr(flags))
         _lib.check(rc, "uavqp_ellipsoid_check_grid_device")
 
-    @staticmethod
-    def _pipeline_params(params):
-        pp = _lib.PipelineParams()
-        _lib.lib().uavqp_default_pipeline_params(ctypes.byref(pp))
-        for k, v in params.items():
-            if not hasattr(pp, k) or k in ("struct_size", "reserved_"):
-                raise ValueError(f"unknown uavqp_pipeline_params field {k!r}")
-            setattr(pp, k, v)
-        return pp
-
     def corridor_pipeline_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc,
                                  obstacles, n_obs, coeff_out, status_out, corr_lo, corr_hi, first_hit=None, grid=None, **params):
         """uavqp_corridor_pipeline_device: BASELINE config 5 as one C-ABI call on device buffers (times is stretched in place).
         params: fields of uavqp_pipeline_params that differ from uavqp_default_pipeline_params.  Returns the uavqp_pipeline_result
         fields as a dict (repair_rows is 0: the box repair places no rows).  Synchronous."""
-        pp = self._pipeline_params(params)
+        pp = self._params(_lib.PipelineParams, "pipeline_params", params)
         res = _lib.PipelineResult()
         rc = _lib.lib().uavqp_corridor_pipeline_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), _ptr(seg_offsets),
                                                        _ptr(waypoints), _ptr(times), _ptr(bc), _ptr(obstacles), int(n_obs), grid, ctypes.byref(pp),
@@ -1078,7 +946,7 @@ class Context:
         """uavqp_corridor_pipeline_rows_device: corridor_pipeline_device with the rows repair (between-knot hits become position rows,
         knot boxes stay).  row_tau / row_deriv [total_segments, 2], row_lo / row_hi [total_segments, 2, 3] device buffers: set to unused
         by the call, on return the rows of the final solve.  Returns the uavqp_pipeline_result fields as a dict.  Synchronous."""
-        pp = self._pipeline_params(params)
+        pp = self._params(_lib.PipelineParams, "pipeline_params", params)
         res = _lib.PipelineResult()
         rc = _lib.lib().uavqp_corridor_pipeline_rows_device(self._h, r, n_traj, uniform_segments, max_segments, int(total_segments), _ptr(seg_offsets),
                                                             _ptr(waypoints), _ptr(times), _ptr(bc), _ptr(obstacles), int(n_obs), grid, ctypes.byref(pp),
