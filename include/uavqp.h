@@ -1253,9 +1253,9 @@ int uavqp_swarm_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_seg
  * to n_traj or a swarm larger than UAVQP_SWARM_MAX_VEHICLES.
  * Out of scope: splitting a straddling leaf at the pair's merged knots (without it a straddling leaf falls back to boxes); a degree-2n
  * squared-distance polynomial per pair; adaptive subdivision; non-cooperative obstacles; wiring the verdict into uavqp_swarm_optimize_*.
- * Against obstacle tracks (uavqp_moving_penalty_device below) there is no certificate of its own yet: until there is, this entry on a batch
- * that concatenates a vehicle with its obstacle tracks as ONE group bounds the vehicle's separation from them for every t; it takes no
- * radii into account. */
+ * Against obstacle tracks (uavqp_moving_penalty_device below) use uavqp_moving_certificate_device: unlike this entry run on a vehicle and
+ * its tracks as ONE group, it takes radii into account, has no cap on a set, spends nothing on obstacle-obstacle pairs and certifies the
+ * trajectory's own flight instead of a clock window. */
 #define UAVQP_SEPARATION_CERTIFIED 1   /* lower >= d_req: holds for ALL t of the window */
 #define UAVQP_SEPARATION_VIOLATED 2    /* upper <  d_req: broken at the witness */
 #define UAVQP_SEPARATION_MOVING 4      /* still under way at the end of the window */
@@ -1326,15 +1326,15 @@ int uavqp_separation_certificate_host(uavqp_ctx* ctx, int r, int n_traj, int uni
  * runs from the LAST segment down): the same bytes run to run, for any grid, and for a trajectory alone or in the middle of a batch.
  * One launch, asynchronous on the ctx stream, no allocation, no workspace, no read-back.
  * WHAT THE RESULT IS: a SOFT penalty on SAMPLES.  d_min_gap is the check afterwards, on the samples only; between them nothing is bounded
- * (a certificate against obstacle tracks: see the note at uavqp_separation_certificate_device).  The obstacle's position is not smooth in
+ * (the bound for every t: uavqp_moving_certificate_device below).  The obstacle's position is not smooth in
  * t_abs where it departs or arrives with a non-zero velocity; the gradient is that of the piece the sample lies in.
  * UAVQP_ERR_INVALID_ARG: r not 3 / 4, a negative count, a wrong struct_size of either struct, samples_per_seg < 1, d_safe not finite or
  * <= 0, downwash not finite or < 1, weight not finite or < 0, NULL times / coeff, ragged without offsets, NULL obstacles, n_obs < 0, a
  * negative uniform_segments of the obstacles, NULL obstacle times / coeff with n_obs > 0, ragged obstacles without offsets, n_sets < 0,
  * NULL set_offsets or NULL traj_set with n_sets != 1; from the _host entry also set offsets that do not ascend from 0 to n_obs, a traj_set
  * outside [-1, n_sets), a radius that is negative or not finite, obstacle offsets that do not ascend from 0.
- * Out of scope: departures as optimisation variables, obstacles that appear or vanish inside a window, a per-obstacle cull, a
- * certificate of its own, wiring into uavqp_swarm_optimize_* or the corridor pipeline. */
+ * Out of scope: departures as optimisation variables, obstacles that appear or vanish inside a window, a per-obstacle cull, wiring into
+ * uavqp_swarm_optimize_* or the corridor pipeline. */
 typedef struct uavqp_moving_params {
     int32_t struct_size;
     int32_t samples_per_seg;   /* K: K + 1 sample points per segment (default 8) */
@@ -1399,6 +1399,80 @@ int uavqp_moving_optimize_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_se
                                const uavqp_spacetime_lbfgs_params* params, double* coeff_out, int32_t* status_out, double* objective_out,
                                int32_t* accepted_out, double* peak_out, double* min_dist_out, int32_t* outside_out, double* attitude_peak_out,
                                double* min_gap_out, int32_t* nearest_out);
+
+/* Certified continuous-time gap between solved trajectories and moving-obstacle tracks (no reference counterpart): the acceptance test
+ * after uavqp_moving_optimize_*.  d_min_gap of the penalty and d_min_gap_out of the optimiser SAMPLE: a vehicle and a track that close at
+ * 10 m/s move 1.25 m against each other between two of the default eight samples of a 1 s segment, so the samples can report a gap of
+ * 0.65 m where the true one is 0.2 m.  This BOUNDS, for every segment of every trajectory and every obstacle of its set, the minimum over
+ * the segment's flight time of
+ *       gap_o(t) = sqrt(dx^2 + dy^2 + (dz / downwash)^2) - radius_o     of q(t) - o(t_abs)
+ * from both sides: `lower` holds for EVERY t of the segment, `upper` is taken at a reported instant and obstacle.
+ * The batch is described as everywhere else; `obstacles` is taken exactly as uavqp_moving_penalty_* takes it (the same fields, the same
+ * NULL conventions, traj_start the departures of the batch; device pointers for _device, host pointers for _host).
+ * The certified curves.  Trajectory b departs at S = traj_start[b]; its clock knots are the DOUBLES K_0 = S, K_{m+1} = fl(K_m + T_m) (as in
+ * the penalty and in uavqp_separation_certificate_device); at local time s of segment m it is at q_m(s) and the clock shows K_m + s.
+ * Obstacle o is the curve of uavqp_separation_certificate_device on that clock, with its knots K^o_0 = start_o, K^o_{m+1} = fl(K^o_m +
+ * T^o_m): it waits at segment 0, local time 0, before start_o; follows CLOSED pieces (at a knot both values belong to the curve); stays at
+ * the end of its last segment after arrival.  It does NOT have the 1e-4 s of overhang of the penalty's sampling rule.
+ * Leaves.  Leaf l = 0..2^depth - 1 of segment m is the local time [l, l + 1] T_m / 2^depth; its clock ends are ta = fma(l 2^-depth, T_m,
+ * K_m) and tb = fma((l + 1) 2^-depth, T_m, K_m), one rounding each.  Witness l = 0..2^depth is the local time l T_m / 2^depth; with the
+ * default depth 3 the witnesses are the samples of the default uavqp_moving_params.
+ * Method (n = 2r - 1; csrc/qp_moving_cert.h derives the constants, tests/moving_cert_reference.py restates it in numpy).  The trajectory
+ * over a leaf: the Bernstein coefficients of uavqp_envelope_* and depth midpoint subdivisions, guard G_x = 16 (n + 1) 2^-53 S_x (the leaf
+ * of uavqp_clearance_certificate_*).  The obstacle over [ta, tb]: the entry of uavqp_separation_certificate_device -- SINGLE (its
+ * 3 x (n + 1) coefficients, Bernstein in the same parameter as the leaf's, so correlated motion cancels) when the leaf lies in one piece,
+ * otherwise BOX (per-axis [lo, hi] over the pieces the leaf meets) -- with the guard G^o_x = (64 (n + 1) + 4 n kappa_o) 2^-53 S_x, kappa_o =
+ * max(|K^o_m|, |K^o_{m+1}|, |ta|, |tb|) / T^o_m (the rounded ta, tb shift the restriction by at most 2^-53 max(|ta|, |tb|)); a held obstacle
+ * has the separation certificate's rule.  Pair (leaf, o), Gs_x = G_x + G^o_x: the range of q - o per axis is [min_k, max_k] of w_k - b^o_k
+ * (single) or the interval difference with the box of the leaf's coefficients (box), widened by Gs_x; g_x = max(0, lo_x, -hi_x);
+ *       L = max(0, sqrt(g_x^2 + g_y^2 + (g_z / downwash)^2) - R) - radius_o,        R = 16 2^-53 sum_x max(|lo_x|, |hi_x|)
+ *       U = |d|_downwash + sqrt(3) max_x Gs_x + 16 2^-53 (|d_x| + |d_y| + |d_z|) - radius_o,   d the difference at a witness
+ *   lower = min over obstacles and leaves of L (negative: the vehicle is inside a radius), upper = min over obstacles and witnesses of U;
+ *   min_t min_o gap_o(t) over the segment lies in [lower, upper].  A tie goes to the smaller obstacle, then the smaller leaf / witness.
+ * A rounded ta (tb) is not trusted to lie on the right side of an obstacle knot (a track may JUMP at a knot): an end that is not exactly
+ * l 2^-depth T_m + K_m stands for [t - 2^-52 |t|, t + 2^-52 |t|], which holds the real end; the pieces a leaf meets, and whether it lies in
+ * ONE, are decided on that widened leaf (a piece met through the margin alone comes in as its end point and makes the entry a BOX), and
+ * where an obstacle knot lies in the interval of an end of a leaf that is not in one piece, that obstacle gives no witness at that end.
+ * Exact ends (dyadic durations and departures) stand for themselves: a track that flies the trajectory's own dyadic knots is SINGLE on
+ * every leaf; with knots that are no dyadic numbers it is a BOX on the leaves that end at a knot.  Where a leaf end and an obstacle knot
+ * coincide exactly, each of the two values at the knot is seen by the leaf on its side (the rule of the separation certificate).
+ * Outputs (each may be NULL; all NULL: UAVQP_OK, nothing done; every element is written exactly once):
+ *   d_gap          [sum_b M_b][2]: lower, upper of the segment
+ *   d_where        [sum_b M_b][4] int32: {obstacle of lower, leaf of lower, obstacle of upper, witness index l of upper (local time
+ *                  l T_m / 2^depth)}; obstacles are indices into the obstacle batch; {-1, 0, -1, 0} when there is none
+ *   d_peak         [n_traj][2]: min of lower, min of upper over the segments
+ *   d_seg_verdict  [sum_b M_b] int32: UAVQP_MOVING_CERT_CERTIFIED (lower >= d_req: holds for ALL t of the segment),
+ *                  UAVQP_MOVING_CERT_VIOLATED (upper < d_req: broken at the witness), neither: undecided at this depth
+ *   d_verdict      [n_traj] int32: AND of the certified bits, OR of the violated bits of the segments
+ * A solved trajectory whose set is -1 or empty: INFINITY bounds, {-1, 0, -1, 0}, certified (the rule of the separation certificate for a
+ * vehicle without a partner; its coefficients are not looked at).  A trajectory that is not UAVQP_SOLVED (d_status NULL: all are) or has
+ * M < 1: INFINITY, INFINITY, {-1, 0, -1, 0}, word 0.  Non-finite coefficients or a duration <= 0 in the segment, or in an obstacle piece one
+ * of its leaves meets: NaN bounds, {-1, 0, -1, 0} and no bit for that segment; the trajectory's peak is NaN and its word 0.  A NaN duration
+ * loses the knot clock as well: every LATER segment of that trajectory gets the same (a duration <= 0 spoils its own segment alone).
+ * Every min is exact: the same bytes for any grid, run to run, and for a trajectory alone or in the middle of a batch.  One launch,
+ * asynchronous on the ctx stream, no allocation, no workspace, no atomics, no read-back.
+ * UAVQP_ERR_INVALID_ARG: what uavqp_moving_penalty_* refuses in the batch and in `obstacles`, with the same precedence; a wrong
+ * struct_size, depth outside 0..6, downwash not finite or < 1, d_req not finite or <= 0.
+ * Out of scope: adaptive subdivision; splitting a leaf at an obstacle's knots (a straddling leaf falls back to a box); a per-obstacle
+ * cull; the time before departure and after arrival; wiring the verdict into uavqp_moving_optimize_*. */
+#define UAVQP_MOVING_CERT_CERTIFIED 1   /* lower >= d_req: holds for ALL t of the segment */
+#define UAVQP_MOVING_CERT_VIOLATED 2    /* upper <  d_req: broken at the witness */
+typedef struct uavqp_moving_cert_params {
+    int32_t struct_size;
+    int32_t depth;      /* 0..6: 2^depth leaves per segment (default 3: the witnesses are then the default samples of the penalty) */
+    double downwash;    /* finite, >= 1 (default 1.0) */
+    double d_req;       /* required gap to an obstacle's surface, m, finite, > 0 (default 1.0) */
+} uavqp_moving_cert_params;
+void uavqp_default_moving_cert_params(uavqp_moving_cert_params* out);   /* callable without a device */
+int uavqp_moving_certificate_device(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* d_seg_offsets,
+                                    const double* d_times, const double* d_coeff, const int32_t* d_status,
+                                    const uavqp_moving_obstacles* obstacles, const uavqp_moving_cert_params* params, double* d_gap,
+                                    int32_t* d_where, double* d_peak, int32_t* d_seg_verdict, int32_t* d_verdict);
+/* The same from HOST pointers, those inside `obstacles` included (H2D copy, run, D2H copy, synchronous). */
+int uavqp_moving_certificate_host(uavqp_ctx* ctx, int r, int n_traj, int uniform_segments, const int32_t* seg_offsets, const double* times,
+                                  const double* coeff, const int32_t* status, const uavqp_moving_obstacles* obstacles,
+                                  const uavqp_moving_cert_params* params, double* gap, int32_t* where, double* peak, int32_t* seg_verdict,
+                                  int32_t* verdict);
 
 /* Batched evaluation of solved trajectories on a uniform time grid.
  * Replaces, for a whole batch, PolyTraj::evaluatePos / evaluateVel / evaluateAcc

@@ -106,6 +106,9 @@ SYMBOLS = (
     "uavqp_moving_penalty_host",
     "uavqp_moving_optimize_device",
     "uavqp_moving_optimize_host",
+    "uavqp_default_moving_cert_params",
+    "uavqp_moving_certificate_device",
+    "uavqp_moving_certificate_host",
     "uavqp_eval_batch_device",
     "uavqp_traj_length_device",
     "uavqp_ellipsoid_check_device",
@@ -276,6 +279,16 @@ class MovingObstacles(ctypes.Structure):
                 ("radius", ctypes.c_void_p), ("set_offsets", ctypes.c_void_p), ("traj_set", ctypes.c_void_p), ("traj_start", ctypes.c_void_p)]
 
 
+class MovingCertParams(ctypes.Structure):
+    """uavqp_moving_cert_params of include/uavqp.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("depth", ctypes.c_int32), ("downwash", ctypes.c_double), ("d_req", ctypes.c_double)]
+
+
+# the bits of a uavqp_moving_certificate_* verdict word (UAVQP_MOVING_CERT_* of include/uavqp.h)
+UAVQP_MOVING_CERT_CERTIFIED = 1
+UAVQP_MOVING_CERT_VIOLATED = 2
+
+
 def build(force=False):
     """Compile csrc/*.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
     csrc = os.path.join(_PKG, "csrc")
@@ -419,6 +432,12 @@ def lib():
                                              ctypes.POINTER(ClearanceParams), ctypes.POINTER(AttitudeParams), ctypes.POINTER(MovingObstacles),
                                              ctypes.POINTER(MovingParams), ctypes.POINTER(SpacetimeLbfgsParams), dp, ip, dp, ip, dp, dp, ip, dp,
                                              dp, ip]
+    L.uavqp_default_moving_cert_params.argtypes = [ctypes.POINTER(MovingCertParams)]
+    L.uavqp_default_moving_cert_params.restype = None
+    L.uavqp_moving_certificate_device.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, ctypes.POINTER(MovingObstacles),
+                                                  ctypes.POINTER(MovingCertParams), dp, ip, dp, ip, ip]
+    L.uavqp_moving_certificate_host.argtypes = [vp, i32, i32, i32, ip, dp, dp, ip, ctypes.POINTER(MovingObstacles),
+                                                ctypes.POINTER(MovingCertParams), dp, ip, dp, ip, ip]
     L.uavqp_default_swarm_opt_params.argtypes = [ctypes.POINTER(SwarmOptParams)]
     L.uavqp_default_swarm_opt_params.restype = None
     L.uavqp_swarm_optimize_device.argtypes = [vp, i32, i32, i32, i32, i32, ip, dp, dp, dp, i32, ip, dp, vp, ctypes.POINTER(LimitParams),

@@ -520,6 +520,36 @@ class TrajOptimizer {
     }
     const std::vector<double>& minGap() const { return min_gap_; }
     const std::vector<int32_t>& nearestObstacle() const { return nearest_; }
+    // Certified gap of every segment to the obstacles of setMovingObstacles, at the stored coefficients and durations, for EVERY t of the
+    // segment (after solve() or an optimiser; uavqp_moving_certificate_host): the hard test that the sampled minGap() is not.  Returns the
+    // verdict word per trajectory (UAVQP_MOVING_CERT_CERTIFIED: at least d_req from every obstacle's surface for ALL t,
+    // UAVQP_MOVING_CERT_VIOLATED: less at the witness, neither: undecided -- raise depth or replan) and fills movingGap() [sum M][2] (lower,
+    // upper), movingWhere() [sum M][4] ({obstacle of lower, leaf of lower, obstacle of upper, witness index of upper}), movingPeak()
+    // [n_traj][2] and movingSegVerdict() [sum M].  Empty on failure.
+    std::vector<int32_t> getMovingCertificate(const uavqp_moving_cert_params& params) {
+        std::vector<int32_t> verdict;
+        if (!moving_.set || n_traj_ <= 0 || !ctx_ || T_.size() != static_cast<size_t>(seg_offsets_[n_traj_]) ||
+            coef_.size() != static_cast<size_t>(3) * 2 * order_ * seg_offsets_[n_traj_] || status_.size() != static_cast<size_t>(n_traj_))
+            return verdict;
+        const size_t total = static_cast<size_t>(seg_offsets_[n_traj_]);
+        verdict.assign(n_traj_, 0);
+        moving_gap_.assign(2 * total, 0.0);
+        moving_where_.assign(4 * total, 0);
+        moving_peak_.assign(static_cast<size_t>(2) * n_traj_, 0.0);
+        moving_seg_verdict_.assign(total, 0);
+        const uavqp_moving_obstacles o = moving_.view();
+        if (uavqp_moving_certificate_host(ctx_, order_, n_traj_, 0, seg_offsets_.data(), T_.data(), coef_.data(), status_.data(), &o, &params,
+                                          moving_gap_.data(), moving_where_.data(), moving_peak_.data(), moving_seg_verdict_.data(),
+                                          verdict.data()) != UAVQP_OK) {
+            std::cout << "solver solve failed! (" << uavqp_last_error() << ")" << std::endl;
+            verdict.clear();
+        }
+        return verdict;
+    }
+    const std::vector<double>& movingGap() const { return moving_gap_; }
+    const std::vector<int32_t>& movingWhere() const { return moving_where_; }
+    const std::vector<double>& movingPeak() const { return moving_peak_; }
+    const std::vector<int32_t>& movingSegVerdict() const { return moving_seg_verdict_; }
     // Certified bounds of the stored coefficients at the stored durations over WHOLE segments (after solve() or an optimiser;
     // uavqp_envelope_host): the verdict word per trajectory (bit 2k certified for all t, bit 2k + 1 violated, UAVQP_ENVELOPE_* of
     // include/uavqp.h), and envelopeRange() [sum M][4][3][4], envelopeNorm() [sum M][5][4], envelopePeak() [n_traj][5][4],
@@ -911,6 +941,8 @@ class TrajOptimizer {
     MovingStore moving_;
     std::vector<double> min_gap_;
     std::vector<int32_t> nearest_;
+    std::vector<double> moving_gap_, moving_peak_;
+    std::vector<int32_t> moving_where_, moving_seg_verdict_;
     std::vector<int32_t> groups_;   // setSwarm: empty = the whole batch is one swarm
     std::vector<double> start_;     // setSwarm: empty = every vehicle departs at 0
     int rows_k_ = 0;

@@ -205,3 +205,7 @@ static inline bool uavqp_twisted_group_exists(int r, int M, int tile) {
 // ---- qp_separation_cert.h: certified separation between the vehicles of a swarm over a whole clock window
 #define UAVQP_SEPARATION_CERT_R(R_) UAVQP_INST __global__ void uavqp::separation_cert_kernel<R_>(uavqp::SeparationCertArgs);
 #define UAVQP_INSTANCES_SEPARATION_CERT UAVQP_SEPARATION_CERT_R(3) UAVQP_SEPARATION_CERT_R(4)
+
+// ---- qp_moving_cert.h: certified gap of whole segments to moving obstacle tracks
+#define UAVQP_MOVING_CERT_R(R_) UAVQP_INST __global__ void uavqp::moving_cert_kernel<R_>(uavqp::MovingCertArgs);
+#define UAVQP_INSTANCES_MOVING_CERT UAVQP_MOVING_CERT_R(3) UAVQP_MOVING_CERT_R(4)

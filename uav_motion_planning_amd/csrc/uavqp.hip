@@ -45,6 +45,7 @@
 #include "qp_envelope.h"
 #include "qp_clearance_cert.h"
 #include "qp_separation_cert.h"
+#include "qp_moving_cert.h"
 // Measured-slower alternatives kept as bit-identical cross-checks: `make experiments` (-DUAVQP_EXPERIMENTS) only
 #ifdef UAVQP_EXPERIMENTS
 #include "cloud_grid2d.h"
@@ -87,6 +88,7 @@ UAVQP_INSTANCES_MOVING
 UAVQP_INSTANCES_ENVELOPE
 UAVQP_INSTANCES_CLEARANCE_CERT
 UAVQP_INSTANCES_SEPARATION_CERT
+UAVQP_INSTANCES_MOVING_CERT
 #endif
 
 namespace uavqp {
@@ -2023,6 +2025,7 @@ extern "C" int uavqp_corridor_from_cloud_device(uavqp_ctx* ctx, int r, int n_tra
 // Moving-obstacle penalty: a trajectory against tracks that are not the batch's to move
 // ===================================================================================================
 #include "uavqp_moving.h"
+#include "uavqp_moving_cert.h"   // the certificate against the same tracks: bounds where the penalty samples
 
 // ===================================================================================================
 // Certified continuous-time bounds (Bernstein enclosure) of solved trajectories and the verdict against limits

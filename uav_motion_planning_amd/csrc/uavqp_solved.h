@@ -1,6 +1,6 @@
 // uavqp_solved.h -- what the entries of include/uavqp.h that EVALUATE a batch of solved trajectories share (included by uavqp.hip behind
-// uavqp_stage.h): the limit, clearance, flight, attitude, swarm and moving-obstacle penalties, the envelope and the clearance and
-// separation certificates, each as a _device and a _host entry.  One description of the batch (SolvedBatch), one argument check, one
+// uavqp_stage.h): the limit, clearance, flight, attitude, swarm and moving-obstacle penalties, the envelope and the clearance,
+// separation and moving-obstacle certificates, each as a _device and a _host entry.  One description of the batch (SolvedBatch), one argument check, one
 // staging of its four arrays, one fill of the kernel arguments, one alignment test, one dispatch of the kernel's template arguments.
 // Host only; everything but the dispatch is plain C++ and compiles without the HIP runtime (tests/cpp/test_solved_args.cpp).
 #pragma once
@@ -24,11 +24,11 @@ struct SolvedGroups {
     const int32_t* offsets;
 };
 
-// The refusal precedence of the eighteen entries, in this order; everything refused is UAVQP_ERR_INVALID_ARG and nothing is touched.
+// The refusal precedence of the twenty entries, in this order; everything refused is UAVQP_ERR_INVALID_ARG and nothing is touched.
 // groups null: the PER-TRAJECTORY rule; groups given: the SWARM rule.
 //   1. ctx, r (3 or 4) and the counts: n_traj, uniform_segments and (SWARM) n_groups must not be negative;
 //   2. params_ok(), called only behind 1: the entry's parameter structs and its own preconditions (the distance field of the map
-//      entries, the obstacle struct of the moving penalty, "both boxes or neither" of the envelope) -- so a bad struct is refused
+//      entries, the obstacle struct of the moving penalty and certificate, "both boxes or neither" of the envelope) -- so a bad struct is refused
 //      even where there is nothing to do;
 //   3. SWARM only: without offsets n_groups must be 1 -- refused even where no output is asked for;
 //   4. nothing to do: UAVQP_OK, *run stays false.  PER-TRAJECTORY: n_traj == 0 or no output asked for.  SWARM: n_groups == 0 or no

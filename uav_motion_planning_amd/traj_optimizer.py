@@ -804,6 +804,40 @@ class Context:
         _lib.check(rc, "uavqp_moving_optimize_host")
         return waypoints, times, coeff, status, objective, accepted, peak, min_dist, outside, attitude_peak, min_gap, nearest
 
+    def moving_certificate_device(self, r, n_traj, uniform_segments, seg_offsets, times, coeff, obstacles, status=None, gap_out=None,
+                                  where_out=None, peak_out=None, seg_verdict_out=None, verdict_out=None, **params):
+        """uavqp_moving_certificate_device on device buffers: the certified gap of every segment to the obstacle tracks of its trajectory's
+        set (obstacles: the dict moving_penalty_device takes) for EVERY t of the segment, not at samples.  gap_out [sum M][2] = lower (holds
+        for all t), upper (taken at a witness); where_out [sum M][4] int32 = {obstacle of lower, leaf of lower, obstacle of upper, witness
+        index of upper}; peak_out [n_traj][2] their minima over the segments; seg_verdict_out [sum M] and verdict_out [n_traj] int32
+        (_lib.UAVQP_MOVING_CERT_CERTIFIED / _VIOLATED); each may be None.  params: fields of uavqp_moving_cert_params that differ from
+        uavqp_default_moving_cert_params (depth, downwash, d_req).  Asynchronous."""
+        cp = self._params(_lib.MovingCertParams, "moving_cert_params", params)
+        mo = self._moving_obstacles(obstacles)
+        rc = _lib.lib().uavqp_moving_certificate_device(self._h, r, n_traj, uniform_segments, _ptr(seg_offsets), _ptr(times), _ptr(coeff),
+                                                        _ptr(status), ctypes.byref(mo), ctypes.byref(cp), _ptr(gap_out), _ptr(where_out),
+                                                        _ptr(peak_out), _ptr(seg_verdict_out), _ptr(verdict_out))
+        _lib.check(rc, "uavqp_moving_certificate_device")
+
+    def moving_certificate_host(self, r, seg_offsets, times, coeff, obstacles, uniform_segments=0, status=None, **params):
+        """uavqp_moving_certificate_host: numpy in / numpy out (synchronous).  obstacles: dict of host arrays (_moving_obstacles_host).
+        Returns (gap [sum M][2], where [sum M][4], peak [n_traj][2], seg_verdict [sum M], verdict [n_traj]); see
+        moving_certificate_device."""
+        so, times, coeff, status, n_traj, total = self._solved_inputs(r, seg_offsets, times, coeff, uniform_segments, status)
+        cp = self._params(_lib.MovingCertParams, "moving_cert_params", params)
+        mo, keep = self._moving_obstacles_host(r, obstacles, n_traj)
+        gap = np.zeros((total, 2), dtype=np.float64)
+        where = np.zeros((total, 4), dtype=np.int32)
+        peak = np.zeros((n_traj, 2), dtype=np.float64)
+        seg_verdict = np.zeros(total, dtype=np.int32)
+        verdict = np.zeros(n_traj, dtype=np.int32)
+        rc = _lib.lib().uavqp_moving_certificate_host(self._h, r, n_traj, uniform_segments, _ptr(so), _ptr(times), _ptr(coeff), _ptr(status),
+                                                      ctypes.byref(mo), ctypes.byref(cp), _ptr(gap), _ptr(where), _ptr(peak),
+                                                      _ptr(seg_verdict), _ptr(verdict))
+        del keep
+        _lib.check(rc, "uavqp_moving_certificate_host")
+        return gap, where, peak, seg_verdict, verdict
+
     def time_optimize_limits_device(self, r, n_traj, uniform_segments, max_segments, total_segments, seg_offsets, waypoints, times, bc,
                                     coeff_out, status_out, objective_out, accepted_out=None, peak_out=None, limits=None, **params):
         """uavqp_time_optimize_limits_device on device buffers: time_optimize_device with the limit penalty inside the objective
@@ -1176,6 +1210,7 @@ class TrajOptimizer:
     setMovingObstacles(times, coeff, ...)   obstacle tracks that are not this batch's to move (uavqp_moving_obstacles): their sets, which
                                      set each trajectory avoids, the departures on the common clock
     getMovingPenalty(...)            [n_traj] penalty against those tracks; fills .min_gap and .nearest
+    getMovingCertificate(...)        certified gap of every segment to those tracks for EVERY t of its flight (lower / upper bounds, verdict)
     optimizeTrajectoryMoving(esdf, ...)   optimizeTrajectoryAttitude with that penalty in the objective (uavqp_moving_optimize_host;
                                      attitude=None: no attitude term); .min_gap / .nearest at the result
     getEnvelope(depth, box, **limits)  certified bounds over whole segments and the certified / violated / undecided masks per limit
@@ -1413,6 +1448,22 @@ class TrajOptimizer:
         phi, _, _, _, self.min_gap, self.nearest = self._ctx.moving_penalty_host(self._r, self._so, self._T, self._coef, self._moving,
                                                                                   status=self.status, **params)
         return phi
+
+    def getMovingCertificate(self, depth=3, d_req=1.0, downwash=1.0):
+        """Certified gap of every segment to the obstacles of setMovingObstacles(), at the stored coefficients and durations, for EVERY t of
+        the segment (uavqp_moving_certificate_host; after solve() or an optimiser): the hard test that the sampled .min_gap is not.
+        Returns a dict: gap [sum M][2] (lower, upper), where [sum M][4] ({obstacle of lower, leaf of lower, obstacle of upper, witness
+        index of upper}), peak [n_traj][2], seg_verdict [sum M], verdict [n_traj] (the int32 words) and, per trajectory, the boolean
+        masks certified (>= d_req for ALL t), violated (< d_req at the witness) and undecided (raise depth, or replan)."""
+        if self._moving is None:
+            raise _lib.UavqpError("getMovingCertificate: no obstacles (call setMovingObstacles() first)")
+        if self._ctx is None or self._coef.size != 3 * 2 * self._r * int(self._so[-1]) or self.status.size != self._so.size - 1:
+            raise _lib.UavqpError("getMovingCertificate: no solved coefficients (call solve() or an optimiser first)")
+        gap, where, peak, seg_verdict, verdict = self._ctx.moving_certificate_host(
+            self._r, self._so, self._T, self._coef, self._moving, status=self.status, depth=depth, d_req=d_req, downwash=downwash)
+        c, v = verdict & _lib.UAVQP_MOVING_CERT_CERTIFIED != 0, verdict & _lib.UAVQP_MOVING_CERT_VIOLATED != 0
+        return dict(gap=gap, where=where, peak=peak, seg_verdict=seg_verdict, verdict=verdict, certified=c, violated=v,
+                    undecided=~c & ~v & (self.status == _lib.UAVQP_SOLVED))
 
     def optimizeTrajectoryMoving(self, esdf, limits=None, clearance=None, attitude=None, moving=None, **params):
         """optimizeTrajectoryAttitude with the penalty against the obstacles of setMovingObstacles() inside the objective
